@@ -11,6 +11,9 @@ Inputs (query crops, gallery shard) are resident in HBM before the timed region.
 
 Contract: python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run)
 prints ONE JSON line on rank 0.  See DESIGN.md "Measurement".
+A plain run sets up, warms up, times the K steps and prints the headline; --full adds, after the timed region,
+the per-kernel / roofline figures, the side measurements and the CPU baseline.  --dump-outputs DIR writes the
+last timed step's result.
 """
 import argparse
 import json
@@ -56,6 +59,13 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip batch_sweep / vendor yardstick / PCIe-inclusive side measurements (profiling runs)")
     ap.add_argument("--cpu-sample", type=int, default=32, help="query images in the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel attribution and roofline figures, the side measurements "
+                         "(PCIe- and decode-inclusive rates, batch sweep, vendor yardstick, BASELINE's other configs) "
+                         "and the CPU baseline + parity; a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result (top-k values and gallery indices of every query of the "
+                         "step, as a caller of the path receives them) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -467,7 +477,7 @@ def main():
     import contextlib
     with contextlib.redirect_stdout(sys.stderr):  # the reference's ctor prints; keep stdout = one JSON line
         model = SHAM2("vit_b_16").eval()
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if (rank == 0 and args.full) else None
     model = model.to(dev)
     vit = model.backbone
 
@@ -529,14 +539,15 @@ def main():
         pipe = StreamPipeline(vit, gallery, args.topk, depth=in_flight, device=dev)
 
     def run_steps(count):
+        """Runs `count` steps; returns the (values, indices) of the last one."""
         if pipe is None:
             for _ in range(count):
                 step()
-            drain()
-        else:
-            for _ in range(count):
-                pipe.submit(x)
-            pipe.drain()
+            return drain()
+        for _ in range(count):
+            pipe.submit(x)
+        outs = pipe.drain()   # in submission order
+        return outs[-1] if outs else None
 
     run_steps(max(args.warmup, in_flight))
     torch.cuda.synchronize()
@@ -544,7 +555,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -554,6 +565,33 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = tt.item()
+
+    if args.dump_outputs and rank == 0:   # every rank holds the merged result of the global query batch
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        val, idx = last
+        np.save(os.path.join(args.dump_outputs, "topk_values.npy"), val.float().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "topk_indices.npy"), idx.double().cpu().numpy())
+
+    headline = {
+        "metric": METRIC, "value": args.batch * world * args.steps / elapsed, "unit": "query-images/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+        "config": {"workload": f"ViT-B/16 (HSimCLR ViTWrapper, random init) embed + top-{args.topk} over "
+                               f"{args.gallery} x 768 {args.gallery_dtype} gallery row-sharded over {world} GPU(s)",
+                   "query_batch_per_gpu": args.batch, "global_query_batch": args.batch * world,
+                   "gallery_rows": args.gallery, "gallery_dtype": args.gallery_dtype, "topk": args.topk,
+                   "sim_mode": args.sim_mode, "residual_stream": args.resid,
+                   "steps_in_flight": in_flight,
+                   "parallelism": f"gallery-shard{world}+query-dp{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel attribution (same workload, HIP events on the launch stream), after the timed region
     nprof = 3
@@ -836,7 +874,6 @@ def main():
 
         gemm_traffic = recorded("pmc_traffic.json", "gemm_f16_big_kernel_avg_bytes_per_launch")
         scan_traffic = recorded("pmc_scan.json", "whole_call_bytes")
-        total_imgs = args.batch * world * args.steps
         gemm_f, attn_f, patch_f = vit_flops(args.batch)
         gemm_ms = sum(per_step.get(k, 0.0) for k in gemm_f)
         gemm_tf = sum(gemm_f.values()) / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
@@ -848,17 +885,7 @@ def main():
         sim_tf = 2.0 * nq_all * shard.shape[0] * 768 / (sim_ms * 1e-3) / 1e12
         attn_ms = per_step.get("attn", 0.0)
         out = {
-            "metric": METRIC, "value": total_imgs / elapsed, "unit": "query-images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"ViT-B/16 (HSimCLR ViTWrapper, random init) embed + top-{args.topk} over "
-                                   f"{args.gallery} x 768 {args.gallery_dtype} gallery row-sharded over {world} GPU(s)",
-                       "query_batch_per_gpu": args.batch, "global_query_batch": nq_all,
-                       "gallery_rows": args.gallery, "gallery_dtype": args.gallery_dtype, "topk": args.topk,
-                       "sim_mode": args.sim_mode, "residual_stream": args.resid,
-                       "steps_in_flight": in_flight,
-                       "parallelism": f"gallery-shard{world}+query-dp{world}"},
+            **headline,
             # dominant kernel by time: the fp16 MFMA GEMM (4 per layer x 12 layers per step)
             "roofline": {"kernel": "gemm_f16_big_kernel (qkv, proj, fc1, fc2)", "bound": "mfma",
                          "achieved": gemm_tf, "peak": MFMA_F16_PEAK_TF, "unit": "TFLOP/s",

@@ -61,7 +61,8 @@ def test_multi_rank_sharded_search_equals_single_scan(tmp_path, nproc):
 
 
 def test_bench_two_ranks_rehearsal():
-    r = _run(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--gallery", "100000"],
+    r = _run(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--gallery", "100000",
+              "--full"],
              {"HCIR_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -54,7 +54,7 @@ def main():
     big = {k: v for k, v in kernels.items() if k.startswith("gemm_f16_big_kernel")}
     tot_n = sum(v["launches"] for v in big.values())
     avg = sum(v["bytes_per_launch"] * v["launches"] for v in big.values()) / max(tot_n, 1)
-    res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in SEPARATE passes of `python3 bench.py --steps 3 "
+    res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in SEPARATE passes of `python3 bench.py --full --steps 3 "
                    "--warmup 1 --no-cpu-baseline`. KB units; read bytes = 2*FETCH_SIZE*1024 (gfx950 half-count of wide "
                    "reads, MI355X_MICROARCH.md HBM section), WRITE_SIZE exact; L2->fabric requests, Infinity-Cache "
                    "hits included. gemm_f16_big_kernel<0> first qkv, <8> LayerNorm-folded qkv, <9> LayerNorm-folded "

@@ -12,9 +12,9 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/${1:-gpurun_out/prof}
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$O/stats" --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-pipeline > "$O/bench_stats.json" 2> "$O/stats.err"; echo "stats done"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$O/fetch" --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$O/fetch.err"; echo "fetch done"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$O/write" --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$O/write.err"; echo "write done"
+rocprofv3 --kernel-trace --stats -d "$O/stats" --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-pipeline > "$O/bench_stats.json" 2> "$O/stats.err"; echo "stats done"
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$O/fetch" --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$O/fetch.err"; echo "fetch done"
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$O/write" --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2> "$O/write.err"; echo "write done"
 rocprofv3 --pmc FETCH_SIZE -d "$O/sfetch" --output-format csv -- python3 "$R/tools/scan_point.py" c4 > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE -d "$O/swrite" --output-format csv -- python3 "$R/tools/scan_point.py" c4 > /dev/null 2>&1; echo "scan pmc done"
 cd "$R"
