@@ -1171,7 +1171,7 @@ int make_plan(const hcir_png_header* hdrs, int64_t b, int32_t win_h, int32_t win
     const hcir_png_header& h = hdrs[i];
     if (h.width == 0) continue;
     if (h.width < 0 || h.height <= 0 || h.bpp != png_host::bytes_per_pixel(h.color_type) || h.bpp == 0 ||
-        (h.stage_offset & 15) || h.width > png_host::kMaxWidth ||
+        (h.stage_offset & 15) || h.width > png_host::kMaxWidth || h.stream_bytes >= png_host::kMaxStreamBytes ||
         (1 + (uint64_t)h.width * h.bpp) * (uint64_t)h.height >= (1ull << 31))
       return HCIR_ERR_INVALID;
     png_host::Win w;

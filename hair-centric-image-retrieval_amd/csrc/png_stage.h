@@ -57,6 +57,14 @@ inline uint32_t crc32(const uint8_t* p, size_t n) {
 
 constexpr int32_t kMaxWidth = 8192;
 
+// Longest zlib stream the device takes (HCIR_PNG_MAX_STREAM_BYTES).  The inflate wavefronts keep bit positions in
+// 32 bits: total_bits = stream_bytes * 8, and a position may run past total_bits before it is compared with it - by
+// a symbol or a header field (<= 64 bits), by the next lookup pass that is requested ahead (wbase + 256) and the
+// words that pass reads (+ 352 bits).  That is < 1024 bits past the end; a margin of 256 bytes (2048 bits) below
+// 2^29 keeps every bp / wbase + pos / bp + 32 expression of png.hip below 2^32.
+constexpr uint32_t kMaxStreamBytes = HCIR_PNG_MAX_STREAM_BYTES;
+static_assert((uint64_t)kMaxStreamBytes * 8u + 2048u <= (1ull << 32), "bit positions of the stream must fit 32 bits");
+
 struct Idat {  // where the IDAT payloads lie in the file
   static const int kMax = 4096;
   uint32_t off[kMax], len[kMax];
@@ -126,7 +134,7 @@ inline int parse(const uint8_t* f, size_t n, int32_t flags, hcir_png_header* h, 
   if (h->color_type == 3 && !plte) return HCIR_ERR_INVALID;
   // the device keeps byte positions in 32 bits and one row of packed pixels (4 B each) in LDS
   const uint64_t row = 1 + (uint64_t)h->width * h->bpp;
-  if (h->width > kMaxWidth || row * (uint64_t)h->height >= (1ull << 31) || id->total >= (1ull << 31))
+  if (h->width > kMaxWidth || row * (uint64_t)h->height >= (1ull << 31) || id->total >= kMaxStreamBytes)
     return HCIR_ERR_UNSUPPORTED;
   h->stream_bytes = (uint32_t)id->total;
   return HCIR_OK;

@@ -189,7 +189,9 @@ class HairEncoder:
 
     def device_windows(self, files) -> torch.Tensor:
         """Compressed files (bytes / uint8 arrays) -> the transform's RGB8 windows [B, 224, 224, 3] on the device:
-        whole-image device decode per (codec, size) group, then ONE device resize + crop over the batch."""
+        whole-image device decode per (codec, size) group, then ONE device resize + crop over the batch.
+        A file the device decoder flags (corrupt stream) is decoded by PIL on the host, as the reference does: PIL
+        raises for it, or its pixels replace the device's.  The flags of the whole batch come back in one copy."""
         import io
         from PIL import Image
         from . import jpeg, png, resize
@@ -200,7 +202,13 @@ class HairEncoder:
         for i, a in enumerate(raw):
             groups.setdefault(_sniff(a), []).append(i)
         images = [None] * len(raw)
+
+        def host_image(i):  # the reference's own decoder for this file
+            with Image.open(io.BytesIO(raw[i])) as im:
+                return torch.from_numpy(np.asarray(im.convert("RGB")).copy()).to(self.device)
+
         threads = min(16, os.cpu_count() or 8)
+        statuses, on_device = [], []  # device status of every device-decoded group; its files (batch indices)
         for (kind, h, w), idx in groups.items():
             sub = [raw[i] for i in idx]
             whole = None
@@ -224,13 +232,27 @@ class HairEncoder:
                     on_dev = staged.to(self.device)
                     ring["copied"][t] = torch.cuda.Event()
                     ring["copied"][t].record(torch.cuda.current_stream(self.device))
-                    whole = mod.decode_windows(on_dev, (h, w), _skip_rejected_check=True)
+                    whole, st = mod.decode_windows(on_dev, (h, w), _skip_rejected_check=True, return_status=True)
+                    keep = [k for k in range(len(sub)) if k not in host]
+                    statuses.append(st if len(keep) == len(sub) else st[keep])
+                    on_device += [idx[k] for k in keep]
             for k, i in enumerate(idx):
-                if k in host:  # the reference's own decoder for this file
-                    with Image.open(io.BytesIO(sub[k])) as im:
-                        images[i] = torch.from_numpy(np.asarray(im.convert("RGB")).copy()).to(self.device)
-                else:
-                    images[i] = whole[k]
+                images[i] = host_image(i) if k in host else whole[k]
+        if not statuses:
+            return resize.resize_center_crop(images, 224)
+        # the one device-to-host copy of the batch, read after the resize is enqueued behind it
+        st = torch.cat(statuses) if len(statuses) > 1 else statuses[0]
+        st_host = torch.empty(st.shape, dtype=st.dtype, pin_memory=True)
+        st_host.copy_(st, non_blocking=True)
+        read = torch.cuda.Event()
+        read.record(torch.cuda.current_stream(self.device))
+        out = resize.resize_center_crop(images, 224)
+        read.synchronize()
+        flagged = torch.nonzero(st_host).flatten().tolist()
+        if not flagged:
+            return out
+        for j in flagged:
+            images[on_device[j]] = host_image(on_device[j])
         return resize.resize_center_crop(images, 224)
 
     def extract_dataset_features(self, data_path, batch_size=64, num_workers=8, save_dir="embeddings"):

@@ -16,7 +16,12 @@ import torch
 
 class StreamPipeline:
     """submit(x) enqueues embed + top-k of one query batch on the next stream and returns the result of the batch
-    submitted `depth` calls earlier (None while the pipeline fills); drain() returns what is still in flight."""
+    submitted `depth` calls earlier (None while the pipeline fills); drain() returns what is still in flight.
+
+    A returned (values, indices) pair is ready on the CALLER's current stream: it waits for the slot's stream, which
+    also ran the exact-scan fallback of the batch's uncertified queries.  Stream i of the pipeline runs the engine's
+    buffer slot i + 1 (slot 0 is left to direct forward_cls calls on the caller's stream).  Drain rule: two
+    pipelines over one backbone share those slots, so one must be drained before the other submits."""
 
     def __init__(self, backbone, gallery, k: int, depth: int = 2, device=None):
         self.backbone, self.gallery, self.k = backbone, gallery, int(k)
@@ -30,8 +35,15 @@ class StreamPipeline:
         if h is None:
             return None
         self.pending[slot] = None
-        with torch.cuda.stream(self.streams[slot]):
-            return h.finish() if hasattr(h, "finish") else self.gallery.search_finish(h)
+        s = self.streams[slot]
+        with torch.cuda.stream(s):
+            out = h.finish() if hasattr(h, "finish") else self.gallery.search_finish(h)
+        # the fallback's writes into (values, indices) were enqueued on `s`, and so were their allocations
+        caller = torch.cuda.current_stream(self.device)
+        caller.wait_stream(s)
+        for t in out:
+            t.record_stream(caller)
+        return out
 
     def submit(self, x: torch.Tensor):
         slot = self.turn
@@ -40,7 +52,7 @@ class StreamPipeline:
         s = self.streams[slot]
         s.wait_stream(torch.cuda.current_stream(self.device))  # x was produced on the caller's stream
         with torch.cuda.stream(s), torch.no_grad():
-            e32, e16 = self.backbone.forward_cls(x, l2_normalize=True, want_f16=True, slot=slot)
+            e32, e16 = self.backbone.forward_cls(x, l2_normalize=True, want_f16=True, slot=slot + 1)
             x.record_stream(s)
             self.pending[slot] = self.gallery.search_begin(e32, self.k, q16=e16)
         return out

@@ -116,9 +116,11 @@ _ws = {}
 
 def decode_windows(staged: StagedBatch, size: Union[int, Tuple[int, int]] = 224, files: Optional[Sequence[Bytes]] = None,
                    host_fallback_for_rejected: bool = False, check_status: bool = False,
-                   _skip_rejected_check: bool = False) -> torch.Tensor:
+                   _skip_rejected_check: bool = False, return_status: bool = False):
     """[B, win_h, win_w, 3] uint8 on the blob's device: CenterCrop(size) of every decoded image (zero where the
-    window leaves the image, as torchvision pads).  Asynchronous on the current stream unless `check_status`."""
+    window leaves the image, as torchvision pads).  Asynchronous on the current stream unless `check_status`.
+    `return_status`: return (windows, status) with the device's per-file status [B] int32 (0 or negative; not read
+    here), for a caller that checks a whole batch with one copy."""
     if not staged.blob.is_cuda:
         raise HcirError(f"the staging blob is on {staged.blob.device}; hcir_png_decode_window_u8 runs on a HIP "
                         "device only (no CPU fallback) — call staged.to(device) first")
@@ -137,7 +139,7 @@ def decode_windows(staged: StagedBatch, size: Union[int, Tuple[int, int]] = 224,
     ws = _ws.get(key)
     if ws is None or ws.numel() < wsb:
         ws = _ws[key] = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    st = torch.empty(staged.b, dtype=torch.int32, device=dev) if check_status else None
+    st = torch.empty(staged.b, dtype=torch.int32, device=dev) if check_status or return_status else None
     check(L.hcir_png_decode_window_u8(staged.blob.data_ptr(), hdrs, staged.b, win_h, win_w, out.data_ptr(),
                                       None if st is None else st.data_ptr(), ws.data_ptr(), ws.numel(), stream),
           "hcir_png_decode_window_u8")
@@ -147,8 +149,8 @@ def decode_windows(staged: StagedBatch, size: Union[int, Tuple[int, int]] = 224,
                             "(pass files= and host_fallback_for_rejected=True to decode those on the host)")
         for i in rej:
             out[i].copy_(host_window(files[i], (win_h, win_w)), non_blocking=True)
-    if st is not None:
+    if check_status:
         bad = [i for i in torch.nonzero(st != 0).flatten().tolist() if i not in staged.rejected]
         if bad:
             raise HcirError(f"corrupt PNG data in files {bad}")
-    return out
+    return (out, st) if return_status else out

@@ -146,7 +146,9 @@ class VitEngine:
     # -- buffers ---------------------------------------------------------------
     def _buffers(self, b: int, t: int, slot: int = 0):
         """Work buffers of one forward in flight.  `slot`: which of several forwards in flight at once (one per HIP
-        stream, hcir.pipeline.StreamPipeline); buffers of another shape are dropped."""
+        stream).  Slot 0 belongs to direct calls on the caller's stream, slots 1.. to hcir.pipeline.StreamPipeline's
+        streams; two forwards that may overlap must not share a slot.  A new shape drops the buffers of the requesting
+        slot only: another slot's buffers may still be read by work in flight on its stream."""
         key = (b, t, slot)
         bufs = self._bufs.get(key)
         if bufs is None:
@@ -165,7 +167,7 @@ class VitEngine:
                 stats_part=torch.empty((max(d // 64, 1), m, 2), dtype=torch.float32, device=dev),
                 stats=torch.empty((m, 2), dtype=torch.float32, device=dev),
             )
-            self._bufs = {k: v for k, v in self._bufs.items() if k[:2] == (b, t)}  # keep one shape resident
+            self._bufs = {k: v for k, v in self._bufs.items() if k[2] != slot}  # one shape resident per slot
             self._bufs[key] = bufs
         return bufs
 

@@ -560,6 +560,11 @@ typedef struct hcir_png_header {
   uint8_t palette[768];  /* PLTE, RGB triples (colour type 3)                             */
 } hcir_png_header;
 
+/* Longest zlib stream (IDAT payloads joined) the device decodes: 2^29 - 256 bytes, so that the inflate's 32-bit bit
+ * positions cannot wrap.  hcir_png_stage reports a longer stream as HCIR_ERR_UNSUPPORTED (the loader keeps its host
+ * decoder for it); hcir_png_workspace_bytes / hcir_png_decode_window_u8 reject a header with stream_bytes at or
+ * above it. */
+#define HCIR_PNG_MAX_STREAM_BYTES ((1u << 29) - 256u)
 #define HCIR_PNG_VERIFY_CRC 1 /* flags: verify the CRC-32 of every chunk while staging (Pillow's default)   */
 
 /* HOST.  Bytes of staging blob needed for this file's stream (0 if it is not a PNG of the subset above). */

@@ -4,9 +4,7 @@ windows (tests/golden/png_streams.npz: the reference's four hair-region PNGs + f
 synthetic files) and live Pillow decodes of seeded files — and against oracle/png.py, the pinned CPU restatement."""
 import io
 import os
-import struct
 import sys
-import zlib
 
 import numpy as np
 import pytest
@@ -14,7 +12,8 @@ import torch
 from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from png_writer import chunk, filter_rows, synth_image, write_png  # noqa: E402
+from corrupt_streams import png_corrupt_cases, png_mutants  # noqa: E402
+from png_writer import synth_image  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -120,28 +119,11 @@ def test_big_batches_and_determinism(streams, hcir_built, count):
         np.testing.assert_array_equal(a[k], wins[i], err_msg=f"{k}: {names[i]}")
 
 
-def _rebuild(data, new_idat):
-    """the same file with another IDAT payload (CRCs valid, so only the decoder can notice)"""
-    i = data.index(b"IDAT") - 4
-    return data[:i] + chunk(b"IDAT", new_idat) + chunk(b"IEND", b"")
-
-
 def test_corrupt_streams_are_flagged_not_fatal(streams, hcir_built):
     from hcir import png
     names, files, wins = streams
     good = files[names.index("filter4_rgb")]
-    rng = np.random.default_rng(4)
-    img = synth_image(rng, 261, 297, 3)
-    raw = filter_rows(img, [4] * 261)
-    z = zlib.compress(raw, 6)
-    cases = {
-        "truncated": _rebuild(good, z[:len(z) // 3]),
-        "bad block type": _rebuild(good, b"\x78\x9c\x07" + bytes(40)),
-        "distance before start": _rebuild(good, b"\x78\x9c\x03\x02\x00" + bytes(40)),
-        "bad zlib header": _rebuild(good, b"\x79\x9c" + z[2:]),
-        "filter type 7": _rebuild(good, zlib.compress(raw[:200 * 892] + b"\x07" + raw[200 * 892 + 1:], 6)),
-        "garbage": _rebuild(good, b"\x78\x9c" + bytes(rng.integers(0, 256, 5000).astype(np.uint8))),
-    }
+    cases = png_corrupt_cases(good, np.random.default_rng(4))
     batch = [good] + list(cases.values()) + [good]
     staged = png.stage_batch(batch)
     assert staged.rejected == []
@@ -241,24 +223,7 @@ def test_mutated_streams_never_fault_and_agree_with_pillow(streams, hcir_built):
     rng = np.random.default_rng(77)
     bases = [files[names.index(n)] for n in ("filter4_rgb", "mixed_blocks", "grey_l1", "palette", "mixed_filters_rgba_l9",
                                              "fixed_blocks")]
-    muts = []
-    for k in range(384):
-        f = bases[k % len(bases)]
-        i = f.index(b"IDAT")
-        n = struct.unpack(">I", f[i - 4:i])[0]
-        z = bytearray(f[i + 4:i + 4 + n])
-        kind = k % 4
-        for _ in range(int(rng.integers(1, 4))):
-            at = int(rng.integers(2, len(z)))
-            if kind == 0:
-                z[at] ^= 1 << int(rng.integers(0, 8))          # one bit
-            elif kind == 1:
-                z[at] = int(rng.integers(0, 256))               # one byte
-            elif kind == 2:
-                z[at:at + 8] = bytes(rng.integers(0, 256, 8).astype(np.uint8))[:len(z) - at]   # a burst
-            else:
-                del z[at:at + int(rng.integers(1, 40))]         # bytes lost: everything behind shifts
-        muts.append(f[:i - 4] + chunk(b"IDAT", bytes(z)) + chunk(b"IEND", b""))
+    muts = png_mutants(bases, rng)
     staged = png.stage_batch(muts)
     assert staged.rejected == []
     dev = staged.to("cuda")

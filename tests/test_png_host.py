@@ -130,6 +130,54 @@ def test_stage_rejects(hcir_built):
     assert _hdr_of(L, wide)[0] == -2  # wider than the device's line buffer
 
 
+# HCIR_PNG_MAX_STREAM_BYTES (include/hcir.h): the device keeps bit positions of the zlib stream in 32 bits
+PNG_MAX_STREAM_BYTES = (1 << 29) - 256
+
+
+def _png_with_idat_total(total: int, width: int = 8192, height: int = 16384, color_type: int = 6) -> np.ndarray:
+    """A PNG file whose IDAT payloads add up to `total` bytes, as a uint8 array.  Only the signature and the chunk
+    headers are written: the payloads stay np.zeros pages that are never touched, and the CRCs are not valid (the
+    callers stage without CRC verification)."""
+    step = 1 << 20
+    sizes = [step] * (total // step) + ([total % step] if total % step else [])
+    a = np.zeros(8 + 25 + 12 * len(sizes) + total + 12, np.uint8)
+    a[:8] = np.frombuffer(b"\x89PNG\r\n\x1a\n", np.uint8)
+    ihdr = chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, color_type, 0, 0, 0))
+    a[8:8 + 25] = np.frombuffer(ihdr, np.uint8)
+    o = 8 + 25
+    for n in sizes:
+        a[o:o + 8] = np.frombuffer(struct.pack(">I", n) + b"IDAT", np.uint8)
+        o += 12 + n
+    a[o:o + 12] = np.frombuffer(chunk(b"IEND", b""), np.uint8)
+    assert o + 12 == a.size
+    return a
+
+
+def test_stage_rejects_streams_past_the_32bit_bit_positions(hcir_built):
+    """A zlib stream of HCIR_PNG_MAX_STREAM_BYTES or more cannot be decoded on the device without its 32-bit bit
+    positions wrapping: the stager reports it unsupported (the loader's host decoder takes it) and the workspace
+    sizing refuses a header that claims one.  8-bit RGBA 8192 x 16384 stays inside kMaxWidth and the 2^31 bound of
+    the raw scanlines, so the stream length is the only thing that decides."""
+    from hcir import png
+    L = hcir_built
+    at = _png_with_idat_total(PNG_MAX_STREAM_BYTES)
+    assert L.hcir_png_stage_bytes(at.ctypes.data, at.size) == 0
+    st = png.stage_batch([at], pin=False, threads=1, verify_crc=False)
+    assert st.rejected == [0] and int(st.status[0]) == -2 and st.headers()[0].width == 0  # HCIR_ERR_UNSUPPORTED
+    del st, at
+    below = _png_with_idat_total(PNG_MAX_STREAM_BYTES - 16)
+    assert L.hcir_png_stage_bytes(below.ctypes.data, below.size) >= PNG_MAX_STREAM_BYTES - 16 + 16
+    del below
+    # a hand-built header (as a caller that stages by itself would pass it)
+    for n, ok in ((PNG_MAX_STREAM_BYTES, False), (PNG_MAX_STREAM_BYTES + 4096, False), (0xFFFFFFF0, False),
+                  (PNG_MAX_STREAM_BYTES - 16, True)):
+        h = png.PngHeader(width=64, height=64, color_type=2, bpp=3, stream_bytes=n, stage_offset=png.HEADER_BYTES)
+        ws = L.hcir_png_workspace_bytes(ctypes.byref(h), 1, 224, 224)
+        assert (ws > 0) == ok, (n, ws)
+    assert "HCIR_PNG_MAX_STREAM_BYTES ((1u << 29) - 256u)" in open(
+        os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hcir.h")).read()
+
+
 def test_stage_batch_and_workspace(streams, hcir_built):
     from hcir import png
     names, files, _, _ = streams
