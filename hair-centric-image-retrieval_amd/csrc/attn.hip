@@ -99,14 +99,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     if (qt + 4 < nqt) load_q(qt + 4, qn);
 
     // ---- S^T = K . Q^T ----
-#ifdef HCIR_ATTN_ABL   // timing ablation (wrong results): one key tile of compute, all memory traffic
-    constexpr int NKC = 1;
-#else
-    constexpr int NKC = NKT;
-#endif
     f32x16 sc[NKT];
 #pragma unroll
-    for (int kt = 0; kt < NKC; ++kt) {
+    for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
       const int key = kt * 32 + r;
@@ -124,11 +119,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     float mx = ninf;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int key = (NKC - 1) * 32 + acc_row(i, h);
-      sc[NKC - 1][i] = key < a.t ? sc[NKC - 1][i] : ninf;
+      const int key = (NKT - 1) * 32 + acc_row(i, h);
+      sc[NKT - 1][i] = key < a.t ? sc[NKT - 1][i] : ninf;
     }
 #pragma unroll
-    for (int kt = 0; kt < NKC; ++kt)
+    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sc[kt][i]);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
       for (int i = 0; i < 16; ++i) oacc[t2][i] = 0.f;
     HCIR_EXP_TILE(0)
 #pragma unroll
-    for (int kt = 0; kt < NKC; ++kt) {
+    for (int kt = 0; kt < NKT; ++kt) {
       f16x8 pf[2], vf[2][2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -174,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
           }
         }
       }
-      if (kt + 1 < NKC) {
+      if (kt + 1 < NKT) {
         HCIR_EXP_TILE(kt + 1)
       }
 #pragma unroll
@@ -182,15 +177,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int hdt = 0; hdt < 2; ++hdt)
           oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s][hdt], pf[s], oacc[hdt], 0, 0, 0);
-#ifdef HCIR_ATTN_SGB   // build flag (A/B): force one MFMA per 12 VALU of the neighbouring exponentials
-      if (kt + 1 < NKC) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);
-        }
-      }
-#endif
     }
 #undef HCIR_EXP_TILE
     sum += __shfl_xor(sum, 32);
@@ -599,14 +585,12 @@ static int attn_fwd_launch(const void* qkv, int64_t b, int32_t t, int32_t h, int
     HCIR_LAUNCH_CHECK();
     return HCIR_OK;
   }
-#ifndef HCIR_ATTN_FWD_V1   // build flag: the 4-wave kernel at every T (A/B runs)
   if (nqt == kF2NKT && nq == t && b * h >= 512) {
     const int items = (int)(b * h);
     hipLaunchKernelGGL(attn_fwd2_kernel, dim3(256), dim3(64 * kF2NKT), 0, st, a, items);
     HCIR_LAUNCH_CHECK();
     return HCIR_OK;
   }
-#endif
 #define LAUNCH(N) hipLaunchKernelGGL(attn_fwd_kernel<N>, grid, dim3(256), 0, st, a)
   // the kernel is built for NKT key tiles; 4 waves walk the query tiles
   switch (nqt) {

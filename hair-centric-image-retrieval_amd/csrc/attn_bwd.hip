@@ -4,11 +4,11 @@
 // torchvision's EncoderBlock (HP/src/main_backbone.py:554) in the training step (HP/src/pretrain_engine.py:745):
 //   P = softmax(scale q k^T)   dV = P^T dO   dP = dO V^T   dS = P o (dP - D),  D_q = sum_d dO[q][d] O[q][d]
 //   dQ = scale dS K            dK = scale dS^T Q
-// One workgroup per (batch, head) of 8 / KT waves; wave w owns keys [32 KT w, 32 KT (w + 1)) (T <= 256) and keeps dK^T
-// and dV^T of its keys in registers for the whole sweep over the query tiles.  KT = 1 (eight waves of one 32-key tile,
-// two per SIMD) is what runs: with four waves of two tiles (the first version: ~350 registers, one wave per SIMD)
-// every LDS round trip and exp2 chain of the per-tile sequence stood exposed and the fourth wave owned 5 real keys of
-// 64 at T = 197 - 1.56 ms per launch at batch 1024 against the forward's 0.31 (cdna_hip_programming.md Appendix B, "Attention
+// One workgroup per (batch, head) of 8 waves; wave w owns keys [32 w, 32 (w + 1)) (T <= 256) and keeps dK^T and dV^T
+// of its keys in registers for the whole sweep over the query tiles.  Eight waves of one 32-key tile, two per SIMD:
+// with four waves of two tiles (the first version, removed: ~350 registers, one wave per SIMD) every LDS round trip
+// and exp2 chain of the per-tile sequence stood exposed and the fourth wave owned 5 real keys of 64 at T = 197 -
+// 1.56 ms per launch at batch 1024 against the forward's 0.31 (cdna_hip_programming.md Appendix B, "Attention
 // backward": the KEY sits on the MFMA lane):
 //   S  = Q . K^T  and  dP = dO . V^T   MFMA 32x32x16, query on the row, key on the column: the accumulators
 //                                      ARE the B operands (contraction over their row index = the query) of
@@ -17,7 +17,7 @@
 //                                      (cdna_hip_programming.md §3);
 //   dQ^T = K^T . dS^T                  contracts over the key = the lane index: dS crosses LDS once ([q][key] image,
 //                                      private to the wave), the per-wave partial dQ tiles (its keys) meet in four
-//                                      padded fp32 LDS slabs (KT = 1: wave 2j writes slab j, wave 2j+1 adds to it),
+//                                      padded fp32 LDS slabs (wave 2j writes slab j, wave 2j+1 adds to it),
 //                                      summed in slab order, and leave as whole fp16 rows: deterministic.
 // P is recomputed from the forward's per-row log2-sum-exp (hcir_attn_fwd_lse); D from dO and O at kernel start.
 // LDS: Q, dO, K images (3 x 32 KB), dS staging 16 KB, dQ slabs 4 x 8.3 KB, row constants 2 KB: 1 workgroup per CU.
@@ -46,8 +46,10 @@ __device__ __forceinline__ int img_off(int row, int c16) { return row * 128 + ((
 // byte address of element column e0 (a multiple of 4) of `row`: a transposed read's 8-byte piece
 __device__ __forceinline__ int img_off_e(int row, int e0) { return img_off(row, e0 >> 3) + (e0 & 7) * 2; }
 
-template <int KT>
-__global__ __launch_bounds__(64 * (8 / KT), 1) void attn_bwd_kernel(AttnBwdArgs a) {
+__global__ __launch_bounds__(512, 1) void attn_bwd_kernel(AttnBwdArgs a) {
+  // KT: 32-key tiles per wave.  The loops over them stay written out: folded by hand they move the register
+  // allocation (198 -> 196 VGPRs) away from the code that was measured.
+  constexpr int KT = 1;
   constexpr int NW = 8 / KT;        // waves
   constexpr int NT = 64 * NW;       // threads
   constexpr int KW = 32 * KT;       // keys per wave
@@ -328,10 +330,6 @@ __device__ __forceinline__ int swz2(int row) {
 __device__ __forceinline__ int img2_off(int row, int c16) { return row * 128 + ((c16 ^ swz2(row)) << 4); }
 __device__ __forceinline__ int img2_off_e(int row, int e0) { return img2_off(row, e0 >> 3) + (e0 & 7) * 2; }
 
-#ifndef HCIR_AB2_STAGGER
-#define HCIR_AB2_STAGGER 0   // s_sleep units (64 cycles) the second wave of each SIMD starts a pass late (A/B flag)
-#endif
-
 __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, int items) {
   __shared__ __attribute__((aligned(16))) char lds[5 * kImg2 + 2 * 256 * 4];
   char* const qs = lds;                 // R0
@@ -364,12 +362,7 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
     const int src = row < a.t ? row : a.t - 1;
     lds_dma16(g, (uint32_t)(src * stride * 2 + ((pc ^ swz2(row)) << 4)), lds0 + (uint32_t)(img - lds) + ii * 1024);
   };
-#if defined(HCIR_AB2_ABL) && HCIR_AB2_ABL == 5   // timing ablation (wrong results): one tile per pass, all memory traffic
-  const int nwl = 1;
-#else
-  const int nwl = nw;
-#endif
-  auto piece_tile = [&](int u) { return u < nwl - 1 ? u : nwl - 1; };
+  auto piece_tile = [&](int u) { return u < nw - 1 ? u : nw - 1; };
   auto qkv_base = [&](int item) { return ((int64_t)(item / a.h) * a.t) * qkv_stride + (item % a.h) * 64; };
   auto o_base = [&](int item) { return ((int64_t)(item / a.h) * a.t) * o_stride + (item % a.h) * 64; };
   auto issue_r0 = [&](int item, int u) {
@@ -481,9 +474,6 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
     }
     __syncthreads();
     AB2_STAMP(2)
-#if HCIR_AB2_STAGGER > 0
-    if (wave >= 4) __builtin_amdgcn_s_sleep(HCIR_AB2_STAGGER);
-#endif
 
     // ---- pass 1: this wave's keys against every query tile; the K / V images (R1) go out under its first tiles
     f32x16 dkt[2], dvt[2];
@@ -491,7 +481,7 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
     for (int x = 0; x < 2; ++x)
 #pragma unroll
       for (int i = 0; i < 16; ++i) dkt[x][i] = dvt[x][i] = 0.f;
-    for (int qt = 0; qt < nwl; ++qt) {
+    for (int qt = 0; qt < nw; ++qt) {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (piece_tile(u) == qt) {
@@ -555,42 +545,27 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
       __builtin_amdgcn_sched_barrier(0);
       f16x8 pf[2], dsf[2];   // [16-query k-step], accumulator-operand k order
       // (keys past T - this lane's column - need no mask here: they only reach dK^T / dV^T columns that are never stored)
-      // (-DHCIR_AB2_HALVES: the exp chain of the second 16-query k-step issued in the shadow of the first k-step's four
-      // MFMAs - measured 2659 against 2662 us per launch, i.e. nothing: the two waves of a SIMD already cover each
-      // other's phases; the plain order is what ships)
+      // (The exp chain of the second 16-query k-step issued in the shadow of the first k-step's four MFMAs was
+      // measured 2659 against 2662 us per launch, i.e. nothing: the two waves of a SIMD already cover each other's
+      // phases; the plain order is what ships)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float p = __builtin_amdgcn_exp2f(sc[i] * a.scale_log2e);
         pf[0][i] = (_Float16)p;
         dsf[0][i] = (_Float16)(p * dp[i]);
       }
-#ifndef HCIR_AB2_HALVES
 #pragma unroll
       for (int i = 8; i < 16; ++i) {
         const float p = __builtin_amdgcn_exp2f(sc[i] * a.scale_log2e);
         pf[1][i & 7] = (_Float16)p;
         dsf[1][i & 7] = (_Float16)(p * dp[i]);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dotf[0][dt], pf[0], dvt[dt], 0, 0, 0);
         dkt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qtff[0][dt], dsf[0], dkt[dt], 0, 0, 0);
       }
-#ifdef HCIR_AB2_HALVES
-#pragma unroll
-      for (int i = 8; i < 16; ++i) {
-        const float p = __builtin_amdgcn_exp2f(sc[i] * a.scale_log2e);
-        pf[1][i & 7] = (_Float16)p;
-        dsf[1][i & 7] = (_Float16)(p * dp[i]);
-      }
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {   // one MFMA, then a quarter of the chain (8 x (mul, exp, mul) + 8 cvt = 32 VALU)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-      }
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
@@ -615,9 +590,6 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // R1 has landed (issued under the first tiles of pass 1)
     __syncthreads();                                   // ... and every wave is done with R0
     AB2_STAMP(4)
-#if HCIR_AB2_STAGGER > 0
-    if (wave >= 4) __builtin_amdgcn_s_sleep(HCIR_AB2_STAGGER);
-#endif
     const int next = item + gridDim.x;
     const bool has_next = next < items;
     // the next item's register fragments: here, not inside the loop below - there the compiler guards the rewrite of
@@ -693,8 +665,8 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
           dqa[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ktf[s][dt], dsb[s], dqa[dt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     };
-    for (int kt = 0; kt + 1 < nwl; ++kt) key_tile(kt, std::false_type{});
-    key_tile(nwl - 1, std::true_type{});
+    for (int kt = 0; kt + 1 < nw; ++kt) key_tile(kt, std::false_type{});
+    key_tile(nw - 1, std::true_type{});
     pack_rows(dqa, a.scale, dqo);   // dQ = scale dQ^T: lane = query
     AB2_STAMP(6)
     prev = item;
@@ -725,7 +697,6 @@ extern "C" int hcir_attn_bwd(const void* qkv, const void* out, const void* d_out
   AttnBwdArgs a{static_cast<const _Float16*>(qkv), static_cast<const _Float16*>(out),
                 static_cast<const _Float16*>(d_out), lse, static_cast<_Float16*>(d_qkv), t, h, scale,
                 scale * 1.44269504088896340736f};
-#ifndef HCIR_ATTN_BWD_V1   // build flag: the single-pass kernel at every T, for A/B runs
   if (t <= kRows2) {
     const int items = (int)(b * h), nw = (t + 31) / 32;
     hipLaunchKernelGGL(attn_bwd2_kernel, dim3((unsigned)(items < 256 ? items : 256)), dim3(64 * nw), 0,
@@ -733,12 +704,7 @@ extern "C" int hcir_attn_bwd(const void* qkv, const void* out, const void* d_out
     HCIR_LAUNCH_CHECK();
     return HCIR_OK;
   }
-#endif
-#ifdef HCIR_ATTN_BWD_KT2   // build flag: the first version (four waves of two key tiles), for A/B runs
-  hipLaunchKernelGGL(attn_bwd_kernel<2>, dim3((unsigned)(b * h)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-#else
-  hipLaunchKernelGGL(attn_bwd_kernel<1>, dim3((unsigned)(b * h)), dim3(512), 0, static_cast<hipStream_t>(stream), a);
-#endif
+  hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)(b * h)), dim3(512), 0, static_cast<hipStream_t>(stream), a);
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

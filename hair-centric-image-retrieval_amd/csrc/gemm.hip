@@ -136,25 +136,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
 // stores of a tile were fully serialised (seen in the .s; 40 % of GEMM time).
 __device__ __forceinline__ void launder(f32x4& v) { asm volatile("" : "+v"(v)); }
 
-// Accumulators of one wave tile (128 n x 64 m), either MFMA shape:
-//   MF16 = false: acc32[nt 0..3][mt 0..1], f32x16: n = 32nt + 8(i>>2) + 4(lane>>5) + (i&3), m = 32mt + (lane&31)
-//   MF16 = true : acc16[nt 0..7][mt 0..3], f32x4 : n = 16nt + 4(lane>>4) + i,            m = 16mt + (lane&15)
-template <bool MF16>
-struct WaveAcc;
-template <>
-struct WaveAcc<false> {
-  f32x16 a[4][2];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-      for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) a[x][y][i] = 0.f;
-  }
-};
-template <>
-struct WaveAcc<true> {
+// Accumulators of one wave tile (128 n x 64 m), MFMA 16x16x32:
+//   a[nt 0..7][mt 0..3], f32x4: n = 16nt + 4(lane>>4) + i, m = 16mt + (lane&15)
+struct WaveAcc {
   f32x4 a[8][4];
   __device__ __forceinline__ void zero() {
 #pragma unroll
@@ -174,33 +158,28 @@ __device__ __forceinline__ float sum8_dpp(float v) {
   return v;
 }
 
-template <int EPI, bool FULL, bool MF16>
-__device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, const WaveAcc<MF16>& acc,
-                                                          char* region, int64_t m0w, int nbase,
-                                                          int lane) {
-  const int r = lane & 31, h = lane >> 5;
+template <int EPI, bool FULL>
+__device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, const WaveAcc& acc, char* region,
+                                                          int64_t m0w, int nbase, int lane) {
   constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kGelu = (EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kResidH = (EPI == HCIR_EPI_BIAS_RESID_F16 || EPI == EPI_RESID_F16_STATS);
   constexpr bool kDual = (EPI == EPI_BIAS_F16_DUAL_GELU);
-  static_assert(MF16 || !kDual, "the dual-output epilogue exists for the 16x16x32 accumulator layout only");
   constexpr bool kF16 = (EPI == HCIR_EPI_BIAS_F16 || kGelu || kLn ||
                          EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH || kDual);
   constexpr bool kAffine = (EPI == HCIR_EPI_AFFINE_RELU_F16 || EPI == HCIR_EPI_AFFINE_F32);
   constexpr int NPASS = kF16 ? 2 : 4;  // 64 or 32 output features (128 B) per pass
-  constexpr int NB = kF16 ? 2 : 1;     // float4 of bias per lane per pass
   const int rrow = lane >> 3, rchunk = lane & 7;
 
-  // 16x16x32 accumulators, fp16 outputs: bias / scale / activation / LayerNorm fold run on the ACCUMULATOR side, in
-  // fp32, before the one rounding to fp16 - the row side only moves 16-B pieces (and adds the fp16 residual).  The
-  // earlier form rounded the raw accumulator to fp16, widened it again behind the transposition, did the math
-  // there and rounded a second time: five VALU instructions per output pair instead of two, and the epilogue phase
-  // of a tile is VALU / LDS-issue time (in-kernel stamps: 4.6 us per qkv tile, 8.6 us per fc1 tile).
-  constexpr bool kAccSide = MF16 && kF16;
-  constexpr bool kScaleA = kAccSide && (EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH);
-  f32x4 biasA[kAccSide ? 8 : 1], scaleA[kScaleA ? 8 : 1];
+  // fp16 outputs: bias / scale / activation / LayerNorm fold run on the ACCUMULATOR side, in fp32, before the one
+  // rounding to fp16 - the row side only moves 16-B pieces (and adds the fp16 residual).  The earlier form rounded
+  // the raw accumulator to fp16, widened it again behind the transposition, did the math there and rounded a second
+  // time: five VALU instructions per output pair instead of two, and the epilogue phase of a tile is VALU / LDS-issue
+  // time (in-kernel stamps: 4.6 us per qkv tile, 8.6 us per fc1 tile).
+  constexpr bool kScaleA = kF16 && (EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH);
+  f32x4 biasA[kF16 ? 8 : 1], scaleA[kScaleA ? 8 : 1];
   bool has_scale = false;
-  if constexpr (kAccSide) {
+  if constexpr (kF16) {
     has_scale = kScaleA && (EPI == HCIR_EPI_AFFINE_RELU_F16 || g.scale != nullptr);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -213,49 +192,38 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
       }
     }
   }
-  // per-lane bias / scale of every pass (row side: fp32 outputs and the 32x32x16 variant), loaded once, retired
-  // once, then laundered
+  // fp32 outputs: per-lane bias / scale of every pass on the row side, loaded once, retired once, then laundered.
+  // (Flattening these [pass][j] arrays to [pass] reschedules the address arithmetic of the fp32 epilogues.)
+  constexpr int NB = kF16 ? 2 : 1;
   f32x4 bias[NPASS][NB], scale[NPASS][NB];
 #pragma unroll
   for (int pass = 0; pass < NPASS; ++pass) {
-    if constexpr (kAccSide) break;
+    if constexpr (kF16) break;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const int n = nbase + pass * (kF16 ? 64 : 32) + rchunk * (kF16 ? 8 : 4) + 4 * j;
       bias[pass][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       scale[pass][j] = (f32x4){1.f, 1.f, 1.f, 1.f};
       if (g.bias) bias[pass][j] = *reinterpret_cast<const f32x4*>(g.bias + n);
-      if (kAffine || ((EPI == HCIR_EPI_BIAS_RESID_F32 || kResidH) && g.scale))
+      if (kAffine || (EPI == HCIR_EPI_BIAS_RESID_F32 && g.scale))
         scale[pass][j] = *reinterpret_cast<const f32x4*>(g.scale + n);
     }
   }
-  // LayerNorm fold, out = rstd[m] (acc - mean[m] c1[n]) + bias[n].  The CENTERING runs on the accumulator side,
-  // in fp32, before the fp16 image: rounding the raw accumulator first loses the result under the cancellation
-  // acc - mean c1 when |mean| >> std (measured: 20x the error at mean/std = 50, 2.4x at 5; equal at 0).  The
-  // scaling by rstd[row] and the bias run on the row side.
-  //   accumulator layout: mean of the 4 (2) rows this lane owns there, c1 of its features there
-  //   (16x16x32: n = 16 t + 4 (lane>>4) + e, t < 8;  32x32x16: n = 32 nt + 8 grp + 4 h + e)
-  float ln_rs[8], ln_mean[4];
-  f32x4 c1a[MF16 ? 8 : 16];
+  // LayerNorm fold, out = rstd[m] (acc - mean[m] c1[n]) + bias[n], all on the accumulator side in fp32: rounding the
+  // raw accumulator first loses the result under the cancellation acc - mean c1 when |mean| >> std (measured: 20x
+  // the error at mean/std = 50, 2.4x at 5; equal at 0).  mean / rstd of the 4 rows this lane owns, c1 of its features.
+  float ln_rs[4], ln_mean[4];
+  f32x4 c1a[8];
   if constexpr (kLn) {
 #pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      if constexpr (kAccSide) break;
-      int64_t mm = m0w + it * 8 + rrow;
-      mm = mm < g.m ? mm : g.m - 1;
-      ln_rs[it] = g.ln_stats[2 * mm + 1];
-    }
-#pragma unroll
-    for (int mt = 0; mt < (MF16 ? 4 : 2); ++mt) {
-      int64_t mm = m0w + (MF16 ? 16 * mt + (lane & 15) : 32 * mt + r);
+    for (int mt = 0; mt < 4; ++mt) {
+      int64_t mm = m0w + 16 * mt + (lane & 15);
       mm = mm < g.m ? mm : g.m - 1;
       ln_mean[mt] = g.ln_stats[2 * mm];
-      if constexpr (kAccSide) ln_rs[mt] = g.ln_stats[2 * mm + 1];  // (the row-side rstd above is unused then)
+      ln_rs[mt] = g.ln_stats[2 * mm + 1];
     }
 #pragma unroll
-    for (int t = 0; t < (MF16 ? 8 : 16); ++t)
-      c1a[t] = *reinterpret_cast<const f32x4*>(
-          g.ln_c1 + nbase + (MF16 ? 16 * t + 4 * (lane >> 4) : 32 * (t >> 2) + 8 * (t & 3) + 4 * h));
+    for (int t = 0; t < 8; ++t) c1a[t] = *reinterpret_cast<const f32x4*>(g.ln_c1 + nbase + 16 * t + 4 * (lane >> 4));
   }
   // (Issuing the next tile's first stage from here, behind these constant loads and with vmcnt(8), instead of from
   // inside the tile's last k-step - so that this wait does not sit out the rest of the stage's round trip - was
@@ -263,13 +231,13 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (kLn) {
 #pragma unroll
-    for (int it = 0; it < (kAccSide ? 4 : 8); ++it) asm volatile("" : "+v"(ln_rs[it]));
+    for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(ln_rs[mt]));
 #pragma unroll
-    for (int mt = 0; mt < (MF16 ? 4 : 2); ++mt) asm volatile("" : "+v"(ln_mean[mt]));
+    for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(ln_mean[mt]));
 #pragma unroll
-    for (int t = 0; t < (MF16 ? 8 : 16); ++t) launder(c1a[t]);
+    for (int t = 0; t < 8; ++t) launder(c1a[t]);
   }
-  if constexpr (kAccSide) {
+  if constexpr (kF16) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       launder(biasA[t]);
@@ -293,87 +261,51 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
     const int pass = kDual ? iter >> 1 : iter;
     const bool second = kDual && (iter & 1);
     // ---- accumulators -> LDS (lane = output row m, registers = features n)
-    if constexpr (!MF16) {
+    const int r16 = lane & 15, q16 = lane >> 4;
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int row = mt * 32 + r;
-        if constexpr (kF16) {
+    for (int mt = 0; mt < 4; ++mt) {
+      const int row = mt * 16 + r16;
+      if constexpr (kF16) {
 #pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            const int nt = 2 * pass + q;
+        for (int q = 0; q < 4; ++q) {   // 64 features per pass = 4 n-tiles of 16
+          const int nt = 4 * pass + q;
+          f16x4 o;
+          float xs[4];
 #pragma unroll
-            for (int grp = 0; grp < 4; ++grp) {
-              f16x4 o;
-              if constexpr (kLn) {
+          for (int e = 0; e < 4; ++e) {
+            float x = acc.a[nt][mt][e];
+            const float bb = biasA[nt][e];
+            if constexpr (kLn) {
+              // out = rstd[m] (acc - mean[m] c1[n]) + bias[n]: centered first (cancellation when |mean| >> std)
+              x = __builtin_fmaf(ln_rs[mt], __builtin_fmaf(-ln_mean[mt], c1a[nt][e], x), bb);
+            } else if constexpr (EPI == HCIR_EPI_AFFINE_RELU_F16) {
+              x = fmaxf(__builtin_fmaf(x, scaleA[nt][e], bb), 0.f);
+            } else if constexpr (kResidH) {
+              x = scaleA[nt][e] * (x + bb);
+            } else {
+              x += bb;
+            }
+            xs[e] = x;
+          }
+          if (kGelu || second) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  o[e] = (_Float16)__builtin_fmaf(-ln_mean[mt], c1a[4 * nt + grp][e], acc.a[nt][mt][4 * grp + e]);
-              } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc.a[nt][mt][4 * grp + e];
-              }
-              const int chunk = q * 4 + grp;
-              *reinterpret_cast<f16x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4) + 8 * h) = o;
+            for (int e = 0; e < 4; e += 2) {
+              const gelu_f32x2 y = gelu_erf2((gelu_f32x2){xs[e], xs[e + 1]});
+              xs[e] = y[0];
+              xs[e + 1] = y[1];
             }
           }
-        } else {
 #pragma unroll
-          for (int grp = 0; grp < 4; ++grp) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = acc.a[pass][mt][4 * grp + e];
-            const int chunk = 2 * grp + h;
-            *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = o;
-          }
+          for (int e = 0; e < 4; ++e) o[e] = (_Float16)xs[e];
+          const int chunk = 2 * q + (q16 >> 1);
+          *reinterpret_cast<f16x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4) + 8 * (q16 & 1)) = o;
         }
-      }
-    } else {
-      const int r16 = lane & 15, q16 = lane >> 4;
+      } else {
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int row = mt * 16 + r16;
-        if constexpr (kF16) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {   // 64 features per pass = 4 n-tiles of 16
-            const int nt = 4 * pass + q;
-            f16x4 o;
-            float xs[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float x = acc.a[nt][mt][e];
-              const float bb = biasA[nt][e];
-              if constexpr (kLn) {
-                // out = rstd[m] (acc - mean[m] c1[n]) + bias[n]: centered first (cancellation when |mean| >> std)
-                x = __builtin_fmaf(ln_rs[mt], __builtin_fmaf(-ln_mean[mt], c1a[nt][e], x), bb);
-              } else if constexpr (EPI == HCIR_EPI_AFFINE_RELU_F16) {
-                x = fmaxf(__builtin_fmaf(x, scaleA[nt][e], bb), 0.f);
-              } else if constexpr (kResidH) {
-                x = scaleA[nt][e] * (x + bb);
-              } else {
-                x += bb;
-              }
-              xs[e] = x;
-            }
-            if (kGelu || second) {
-#pragma unroll
-              for (int e = 0; e < 4; e += 2) {
-                const gelu_f32x2 y = gelu_erf2((gelu_f32x2){xs[e], xs[e + 1]});
-                xs[e] = y[0];
-                xs[e + 1] = y[1];
-              }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (_Float16)xs[e];
-            const int chunk = 2 * q + (q16 >> 1);
-            *reinterpret_cast<f16x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4) + 8 * (q16 & 1)) = o;
-          }
-        } else {
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {   // 32 features per pass = 2 n-tiles of 16
-            const int nt = 2 * pass + q;
-            const int chunk = 4 * q + q16;
-            *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = acc.a[nt][mt];
-          }
+        for (int q = 0; q < 2; ++q) {   // 32 features per pass = 2 n-tiles of 16
+          const int nt = 2 * pass + q;
+          const int chunk = 4 * q + q16;
+          *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = acc.a[nt][mt];
         }
       }
     }
@@ -382,7 +314,12 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
       const int n = nbase + pass * 64 + rchunk * 8;
 #pragma unroll
       for (int it0 = 0; it0 < 8; it0 += 4) {
-        // fp16 residual: the four old rows of a group are requested back to back (counted waits)
+        // fp16 residual: the four old rows of a group are requested back to back (counted waits).  (Not reading them
+        // at all - a timing ablation, wrong results - took proj 237 -> 201 us, fc2 709 -> 686 us at batch 880.
+        // Requesting all sixteen pieces of the tile during its last k-step instead (registers freed by keeping the
+        // bias in LDS; bit-identical) made proj 3.5 % and fc2 1.3 % SLOWER: the 128 KB a tile reads here go through
+        // the same L2 -> CU path as its stages, and that path is what bounds the main loop -
+        // profiles/r4_gemm_resid_prefetch.txt)
         f16x8 oldh[4];
         if constexpr (kResidH) {
 #pragma unroll
@@ -390,57 +327,21 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
             const int64_t mm = m0w + (it0 + u) * 8 + rrow;
 #pragma unroll
             for (int e = 0; e < 8; ++e) oldh[u][e] = (_Float16)0.f;
-            // (-DHCIR_EPI_ABL_NOOLD: timing ablation, WRONG results - the residual rows are not read: proj 237 -> 201 us,
-            // fc2 709 -> 686 us at batch 880.  Requesting all sixteen pieces of the tile during its last k-step instead
-            // (registers freed by keeping the bias in LDS; bit-identical) made proj 3.5 % and fc2 1.3 % SLOWER: the
-            // 128 KB a tile reads here go through the same L2 -> CU path as its stages, and that path is what bounds
-            // the main loop - profiles/r4_gemm_resid_prefetch.txt)
-#ifndef HCIR_EPI_ABL_NOOLD
             if (FULL || mm < g.m)
               oldh[u] = *reinterpret_cast<const f16x8*>(static_cast<const _Float16*>(g.resid) + mm * g.ldo + n);
-#endif
           }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int row = (it0 + u) * 8 + rrow;
           const f16x8 v = *reinterpret_cast<const f16x8*>(region + row * 128 + ((rchunk ^ (row & 7)) << 4));
+          // the image already holds the finished fp16 values; the fp16 residual is one packed add per pair (the
+          // exact sum of two fp16 numbers, rounded once)
           f16x8 o;
-          if constexpr (kAccSide) {
-            // the image already holds the finished fp16 values; the fp16 residual is one packed add per pair
-            // (the exact sum of two fp16 numbers, rounded once)
-            if constexpr (kResidH)
-              o = v + oldh[u];
-            else
-              o = v;
-          } else {
-          float xs[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            float x = (float)v[e];
-            const float bb = bias[pass][e >> 2][e & 3];
-            if constexpr (EPI == HCIR_EPI_AFFINE_RELU_F16) {
-              x = fmaxf(__builtin_fmaf(x, scale[pass][e >> 2][e & 3], bb), 0.f);
-            } else if constexpr (kResidH) {
-              x = __builtin_fmaf(scale[pass][e >> 2][e & 3], x + bb, (float)oldh[u][e]);
-            } else if constexpr (kLn) {
-              x = __builtin_fmaf(ln_rs[it0 + u], x, bb);
-            } else {
-              x += bb;
-            }
-            xs[e] = x;
-          }
-          if constexpr (kGelu) {
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) {
-              const gelu_f32x2 y = gelu_erf2((gelu_f32x2){xs[e], xs[e + 1]});
-              xs[e] = y[0];
-              xs[e + 1] = y[1];
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (_Float16)xs[e];
-          }
+          if constexpr (kResidH)
+            o = v + oldh[u];
+          else
+            o = v;
           const int64_t m = m0w + row;
           // non-temporal: the 128 KB a workgroup writes per tile would otherwise push the W panels out of the
           // XCD's L2 (W is re-fetched ~50x from the Infinity Cache per qkv launch); +1.4 % end to end
@@ -516,19 +417,19 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
 // through a private 8 KB piece of the LDS slot that the tile's last k-step has just released,
 // 128 B of one output row at a time, so that a lane ends up with 16 contiguous bytes of ONE output
 // row and 8 lanes cover a whole 128-B line (the direct layout gives every lane 8 B of a different
-// row: 1.6-1.9 TB/s effective on the fp16 outputs).  Bias / GELU / residual run on the
+// row: 1.6-1.9 TB/s effective on the fp16 outputs).  The fp32 outputs take bias / residual on the
 // row-contiguous side.  [64 rows][128 B] image, 16-B chunks XOR-swizzled with row & 7.
 // Full tiles (all 64 rows of the wave inside M) take a branch-free path.
-template <int EPI, bool MF16>
-__device__ __forceinline__ void gemm_epilogue256_lds(const GemmArgs& g, const WaveAcc<MF16>& acc,
+template <int EPI>
+__device__ __forceinline__ void gemm_epilogue256_lds(const GemmArgs& g, const WaveAcc& acc,
                                                      char* region, int64_t m0w, int nbase, int lane) {
   // opaque lane id: the epilogue's ~60 loop-invariant LDS / global addresses all derive from it, so hipcc
   // cannot hoist them out of the persistent tile loop into long-lived registers
   asm volatile("" : "+v"(lane));
   if (m0w + 64 <= g.m)
-    gemm_epilogue256_lds_impl<EPI, true, MF16>(g, acc, region, m0w, nbase, lane);
+    gemm_epilogue256_lds_impl<EPI, true>(g, acc, region, m0w, nbase, lane);
   else
-    gemm_epilogue256_lds_impl<EPI, false, MF16>(g, acc, region, m0w, nbase, lane);
+    gemm_epilogue256_lds_impl<EPI, false>(g, acc, region, m0w, nbase, lane);
 }
 
 template <int EPI, bool GLDS>
@@ -587,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmArgs g, int tiles_
 
 // ---------------------------------------------------------------------------
 // Big-tile GEMM: 256(n) x 256(m) per workgroup, 8 waves as 2(n) x 4(m), each wave
-// 128(n) x 64(m) = 4 x 2 MFMA 32x32x16 tiles (128 accumulator registers), persistent
+// 128(n) x 64(m) = 8 x 4 MFMA 16x16x32 tiles (128 accumulator registers), persistent
 // over tiles.  Why this geometry (measured, DESIGN.md "GEMM ablation"): with 64 x 64
 // wave tiles the LDS pipe (fragment reads + DMA writes, ~170 B/clk of 256) is the limit
 // and compute alone tops out at 1.24 PF; 128 x 64 wave tiles cut LDS reads per MFMA by
@@ -596,7 +497,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmArgs g, int tiles_
 //
 // A stage is 512 rows x 128 B = 64 KB; two slots.  Step s: wait for stage s (vmcnt(0)),
 // barrier, then the eight DMA pieces of stage s+1 are issued between the fragment reads
-// and the MFMAs of the FIRST two k-substeps, so that they have the rest of the step (24+
+// and the MFMAs of the FIRST 32-k substep, so that they have the rest of the step (32+
 // MFMAs per wave) to land.  Stages run on across tile boundaries: the next tile's first
 // stage flies under the epilogue.  Requires K % 64 == 0.
 // ---------------------------------------------------------------------------
@@ -609,30 +510,17 @@ __device__ unsigned long long g_gemm_stamps[256 * 8];
     if ((cond) && threadIdx.x == 0 && blockIdx.x < 256)                                        \
       g_gemm_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime();                  \
   } while (0)
-// per-wavefront stamps of the overlapped boundary (gemm_f16_ov_kernel): [0..7] start, [8..15] end, [16..23] next step
-__device__ unsigned long long g_gemm_wstamps[256 * 24];
-#define HCIR_WSTAMP(cond, i)                                                                              \
-  do {                                                                                                    \
-    if ((cond) && (threadIdx.x & 63) == 0 && blockIdx.x < 256)                                            \
-      g_gemm_wstamps[blockIdx.x * 24 + 8 * (i) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();  \
-  } while (0)
 #else
 #define HCIR_GSTAMP(cond, i) \
   do {                       \
   } while (0)
-#define HCIR_WSTAMP(cond, i) \
-  do {                       \
-  } while (0)
 #endif
 
-#ifndef HCIR_GEMM_NGROUP
-#define HCIR_GEMM_NGROUP 3  // tools/ab_gemm.py, batch 880: fc1 908 -> 890 us, qkv 574 -> 568 us (0 = n fastest over the whole N)
-#endif
-#ifndef HCIR_GEMM_NGROUP_WIDE
-#define HCIR_GEMM_NGROUP_WIDE 6  // group size when it divides tiles_n (fc1: 12 n-tiles): the activation panels are
-                                 // then fetched by two XCD sets instead of four (PMC: fc1 reads x5.3 -> see DESIGN);
-                                 // time flat against 3 (profiles/r3_diag_ab_gemm_ngroup.txt), fabric bytes -20 %
-#endif
+constexpr int kGemmNGroup = 3;      // tools/ab_gemm.py, batch 880: fc1 908 -> 890 us, qkv 574 -> 568 us against n
+                                    // fastest over the whole N
+constexpr int kGemmNGroupWide = 6;  // group size when it divides tiles_n (fc1: 12 n-tiles): the activation panels are
+                                    // then fetched by two XCD sets instead of four (PMC: fc1 reads x5.3 -> see DESIGN);
+                                    // time flat against 3 (profiles/r3_diag_ab_gemm_ngroup.txt), fabric bytes -20 %
 
 struct G256 {
   static constexpr int NT = 512;
@@ -641,13 +529,12 @@ struct G256 {
   static constexpr int NLOAD = ROWS * 8 / NT;    // 16-B pieces per thread per stage = 8
 };
 
-template <int EPI, bool MF16>
+template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int tiles_n, int tiles_m) {
   __shared__ __attribute__((aligned(16))) char lds[2 * G256::STAGE_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_n = wave >> 2, wave_m = wave & 3;
-  const int r = lane & 31, h = lane >> 5;
   const int ntiles = tiles_n * tiles_m;
   const int nkc = g.k / 64;
   const int my_tiles =
@@ -656,12 +543,9 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
 
   auto tile_origin = [&](int ti, int& n0, int64_t& m0) {
     const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
-#if HCIR_GEMM_NGROUP > 0
-    // n-grouped order: the W panels of one group of HCIR_GEMM_NGROUP n-tiles stay in the XCD's L2 while every
-    // m-tile streams past them (a W set wider than the 4 MB L2 - fc1: 12 panels, 4.7 MB - is otherwise re-fetched
-    // for every row of tiles)
-    const int ngrp = (HCIR_GEMM_NGROUP_WIDE > 0 && tiles_n % HCIR_GEMM_NGROUP_WIDE == 0 && tiles_n > HCIR_GEMM_NGROUP_WIDE)
-                         ? HCIR_GEMM_NGROUP_WIDE : HCIR_GEMM_NGROUP;
+    // n-grouped order: the W panels of one group of n-tiles stay in the XCD's L2 while every m-tile streams past
+    // them (a W set wider than the 4 MB L2 - fc1: 12 panels, 4.7 MB - is otherwise re-fetched for every row of tiles)
+    const int ngrp = (tiles_n % kGemmNGroupWide == 0 && tiles_n > kGemmNGroupWide) ? kGemmNGroupWide : kGemmNGroup;
     if (tiles_n % ngrp == 0 && tiles_n > ngrp) {
       const int per = ngrp * tiles_m;
       const int grp = t / per, rem = t - grp * per;
@@ -669,7 +553,6 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       m0 = (int64_t)(rem / ngrp) * 256;
       return;
     }
-#endif
     n0 = (t % tiles_n) * 256;
     m0 = (int64_t)(t / tiles_n) * 256;
   };
@@ -708,26 +591,10 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
   auto issue_piece = [&](int slot, int i) {
     // pieces 0..3 are W rows, 4..7 activation rows (i is a constant after unrolling).  Default cache policy
     // on both operands: `nt` (aux 2) on the activation rows measured +-1 %, on the W rows -9..-13 %
-    // (every CU of an XCD re-reads them from L2)
-#ifndef HCIR_GEMM_BUILTIN_DMA   // the transfer issued outside the compiler's view (common.h lds_dma16): +1.3 % over
-                                // the layer against the builtin (qkv +2.6 %), which stays behind this flag for A/B runs
-#ifdef HCIR_GEMM_A_NT   // EXPERIMENT (build flag): activation rows with the non-temporal policy, so that the streamed
-                        // A panels do not push the W panels out of the XCD's L2
-    if (i >= 4)
-      lds_dma16_nt(abase + issue_kc * 128, soff[i],
-                   lds_addr(lds) + slot * G256::STAGE_BYTES + ((tid & ~63) + G256::NT * i) * 16);
-    else
-#endif
+    // (every CU of an XCD re-reads them from L2).  The transfer is issued outside the compiler's view (common.h
+    // lds_dma16): +1.3 % over the layer against __builtin_amdgcn_global_load_lds (qkv +2.6 %)
     lds_dma16((i < 4 ? wbase : abase) + issue_kc * 128, soff[i],
               lds_addr(lds) + slot * G256::STAGE_BYTES + ((tid & ~63) + G256::NT * i) * 16);
-#else
-    const char* sp = (i < 4 ? wbase : abase) + issue_kc * 128 + soff[i];
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)sp,
-        (__attribute__((address_space(3))) void*)(lds + slot * G256::STAGE_BYTES +
-                                                   ((tid & ~63) + G256::NT * i) * 16),
-        16, 0, 0);
-#endif
   };
   auto issue_advance = [&]() {
     if (++issue_kc == nkc) {
@@ -737,18 +604,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
     }
   };
 
-  WaveAcc<MF16> acc;
+  WaveAcc acc;
   acc.zero();
-
-#ifdef HCIR_GEMM_SKEW_CLK
-  // EXPERIMENT (build flag): every other workgroup of an XCD starts half a tile late, so that the epilogue
-  // store bursts of the two halves of an XCD's CUs do not coincide
-  if ((blockIdx.x >> 3) & 1) {
-    const uint64_t t0 = __builtin_amdgcn_s_memtime();
-    const uint64_t wait = (uint64_t)HCIR_GEMM_SKEW_CLK * (uint64_t)nkc;
-    while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
 
   if (nsteps > 0) {
     set_sources(0);
@@ -773,57 +630,33 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
     const char* st = lds + (step & 1) * G256::STAGE_BYTES;
     const bool do_issue = step + 1 < nsteps;
     const int islot = (step + 1) & 1;
-    if constexpr (!MF16) {
+    // 16x16x32: lane (r16 = lane&15, kq = lane>>4) holds row r16, k = 32*ks2 + 8*kq .. +7
+    const int r16 = lane & 15, kq = lane >> 4;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int chunk = 2 * ks + h;
-        u32x4 af[4], bf[2];
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      const int chunk = 4 * ks2 + kq;
+      u32x4 bf[4];
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          af[nt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(wave_n * 128 + nt * 32 + r, chunk));
+      for (int mt = 0; mt < 4; ++mt)
+        bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(256 + wave_m * 64 + mt * 16 + r16, chunk));
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-          bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(256 + wave_m * 64 + mt * 32 + r, chunk));
-        if (do_issue && ks < 2) {  // four of the eight DMA pieces of stage step+1 per early k-substep
+      for (int half = 0; half < 2; ++half) {
+        u32x4 af[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) issue_piece(islot, 4 * ks + i);
+        for (int q = 0; q < 4; ++q)
+          af[q] = *reinterpret_cast<const u32x4*>(
+              st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
+        if (do_issue && ks2 == 0) {  // the eight DMA pieces of stage step+1 in the first 32-k substep
+#pragma unroll
+          for (int i = 0; i < 4; ++i) issue_piece(islot, 4 * half + i);
         }
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
+        for (int q = 0; q < 4; ++q)
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt)
-            acc.a[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(
-                __builtin_bit_cast(f16x8, af[nt]), __builtin_bit_cast(f16x8, bf[mt]), acc.a[nt][mt], 0, 0, 0);
-      }
-    } else {
-      // 16x16x32: lane (r16 = lane&15, kq = lane>>4) holds row r16, k = 32*ks2 + 8*kq .. +7
-      const int r16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        const int chunk = 4 * ks2 + kq;
-        u32x4 bf[4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-          bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(256 + wave_m * 64 + mt * 16 + r16, chunk));
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          u32x4 af[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            af[q] = *reinterpret_cast<const u32x4*>(
-                st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
-          if (do_issue && ks2 == 0) {  // the eight DMA pieces of stage step+1 in the first 32-k substep
-#pragma unroll
-            for (int i = 0; i < 4; ++i) issue_piece(islot, 4 * half + i);
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-              acc.a[4 * half + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                  __builtin_bit_cast(f16x8, af[q]), __builtin_bit_cast(f16x8, bf[mt]), acc.a[4 * half + q][mt],
-                  0, 0, 0);
-        }
+          for (int mt = 0; mt < 4; ++mt)
+            acc.a[4 * half + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                __builtin_bit_cast(f16x8, af[q]), __builtin_bit_cast(f16x8, bf[mt]), acc.a[4 * half + q][mt],
+                0, 0, 0);
       }
     }
     if (do_issue) issue_advance();
@@ -838,8 +671,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       // the slot stays free until the DMA of stage step+2 is issued behind the next step's barrier
       __builtin_amdgcn_s_barrier();
       HCIR_GSTAMP(ti == 1, 2);
-      gemm_epilogue256_lds<EPI, MF16>(g, acc, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
-                                      m0 + wave_m * 64, n0 + wave_n * 128, lane);
+      gemm_epilogue256_lds<EPI>(g, acc, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
+                                m0 + wave_m * 64, n0 + wave_n * 128, lane);
       HCIR_GSTAMP(ti == 1, 3);
       acc.zero();
       kc = 0;
@@ -847,338 +680,6 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       // the DMA source offsets of the tile being issued are RE-DERIVED here instead of living through the epilogue:
       // the dual-output variant spilled them, and its reload made the compiler put vmcnt(0) in front of every DMA
       // group of the main loop (MFMA busy 39 % against 57 % for the other variants)
-      if (issue_ti < my_tiles) set_sources(issue_ti);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// EXPERIMENT (build flag HCIR_GEMM_OVERLAP, round 4; NOT the default - measured flat to 5 % slower):
-// the 256 x 256 kernel with the epilogue of tile t run INSIDE the first k-step of tile t+1 ("overlapped boundary"),
-// for the fp16-output epilogues without a residual read (qkv, fc1: 62 % of the encoder's GEMM time).
-//
-// Idea: at K = 768 a tile is 12 k-steps of 1.65 us plus 5-6 us (qkv) to 9-10 us (fc1 + GELU) in which the matrix
-// pipes and the L2 -> LDS fill both stand still.  There is no room to park a finished tile (the accumulators are half
-// of the CU's registers, the two stages 128 of its 160 KB of LDS), so the boundary is cut into EIGHT sub-passes of 4
-// accumulator blocks (64 features x 16 rows): finish the blocks in fp32 on the accumulator side -> start the SAME
-// blocks of the next tile (their MFMAs of k-step 0 with C = 0, fragments from the stage that has landed) -> store.
-// An accumulator register is re-used by the next tile the moment its old value has been packed; the step behind the
-// boundary waits with vmcnt(16) (its stage was issued BEFORE the sixteen stores; vector-memory operations retire in
-// issue order); per-tile vectors (bias, c1, LayerNorm mean / rstd) are staged in 4 KB of LDS during the tile's last
-// k-step so that they are read with ds_read instead of queueing behind the stores.  The k order of every
-// accumulator is unchanged: results are bit-identical to gemm_f16_big_kernel / gemm_f16_mid_kernel
-// (tools/cmp_gemm_variants.py, tests/test_vit_gpu.py::test_gemm_overlapped_tile_boundary).
-//
-// What the stamps say (tools/diag_gemm_stamps.py ... ov, profiles/r4_gemm_boundary_stamps.txt; batch 880):
-//   * the boundary step takes 5.6 us (qkv) / 9.4 us (fc1) against 6.5 / 11 for "barrier + epilogue + wait + first
-//     k-step" of the plain kernel, and the launch is flat: qkv 594 vs 592 us, fc1 932 vs 918 us with an LDS
-//     transposition image (first form), 613 vs 580 / 922 vs 901 us with the register exchange below;
-//   * per wavefront: the SIMD's first wavefront runs its boundary at full speed (2.4 us qkv, 4.6 us fc1), the
-//     second one only THEN (leaves at 4.5 / 8.3 us): the two instruction streams of a SIMD serialise, so the step
-//     costs the SUM of both, ~6.7 cycles per instruction, 3.5 x the essential VALU + MFMA issue time;
-//   * it is not the stores' destination (every tile storing to the same 256 rows: unchanged), not HBM, not the
-//     instruction count alone (1000 -> 700 per wavefront moved the first wavefront, not the step);
-//   * with the finish arithmetic and the stores compiled out the tile period is 20.5 us (qkv and fc1: 1.21-1.23 PF)
-//     against 24-25 / 27-28: that, not more, is what a perfect boundary would buy (-15 % on the two shapes).
-// Tiles that are not followed by another tile of the workgroup, and the ragged last row of tiles, take the plain
-// boundary (gemm_epilogue256_lds).  Requires K >= 128.
-// ---------------------------------------------------------------------------
-struct GOv {
-  static constexpr int VEC_OFF = 2 * G256::STAGE_BYTES;   // bias[256] | c1[256] | (mean, rstd)[256]
-  [[maybe_unused]] static constexpr int LDS_BYTES = VEC_OFF + 4096;   // 132 KB
-};
-
-// Second form, written for instruction count (the first one - LDS transposition image, per-store 64-bit address
-// arithmetic - spent ~1000 instructions per wavefront on 128 x 64 outputs, this one ~650):
-//   * no LDS image: two v_permlane16_swap_b32 per pair of 16-feature blocks leave every lane with 16 contiguous
-//     bytes of one output row (lanes 0-15 <-> 16-31 and 32-47 <-> 48-63 trade halves: a lane then holds features
-//     8 (q16 >> 1) .. +7 of block nt + (q16 & 1)), stored as 16 rows x 64 B per instruction;
-//   * store addresses = wave-uniform base (SGPRs) + ONE per-lane 32-bit offset for the whole boundary;
-//   * every LDS address = one of six per-lane bases + an immediate.
-__device__ __forceinline__ f16x2 cvt_pk_rne(float a, float b) {
-  return __builtin_convertvector((f32x2){a, b}, f16x2);
-}
-
-template <int EPI>
-__device__ __forceinline__ void gemm_ov_boundary(const GemmArgs& g, WaveAcc<true>& acc, const char* st,
-                                                 const char* vec, int64_t m0w, int nbase, int wave_n, int wave_m,
-                                                 int lane) {
-  constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
-  constexpr bool kGelu = (EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_GELU_F16);
-  asm volatile("" : "+v"(lane));   // opaque: none of the addresses below may be hoisted into the main loop
-  const int r16 = lane & 15, q16 = lane >> 4;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  // per-lane bases; everything else is an immediate (row blocks are 16 rows = 2048 B apart, and a block's swizzle
-  // only depends on r16: sim_slot_off(row + 16 j, c) = sim_slot_off(row, c) + 2048 j)
-  const char* af0 = st + sim_slot_off(wave_n * 128 + r16, q16);
-  const char* af1 = st + sim_slot_off(wave_n * 128 + r16, 4 + q16);
-  const char* bf0 = st + sim_slot_off(256 + wave_m * 64 + r16, q16);
-  const char* bf1 = st + sim_slot_off(256 + wave_m * 64 + r16, 4 + q16);
-  const char* vb = vec + (wave_n * 128 + 4 * q16) * 4;
-  const char* lnb = vec + 2048 + (wave_m * 64 + r16) * 8;
-  const uint32_t voff = (uint32_t)(((int64_t)r16 * g.ldo + 16 * (q16 & 1) + 8 * (q16 >> 1)) * 2);
-#ifndef HCIR_OV_ABL
-#define HCIR_OV_ABL 0   // timing ablations (WRONG results): 3 = every tile stores to the first 256 rows, 4 = plain (not nt) stores
-#endif
-  char* const obase = reinterpret_cast<char*>(static_cast<_Float16*>(g.out) + (HCIR_OV_ABL == 3 ? (m0w & 255) : m0w) * g.ldo + nbase);
-#pragma unroll
-  for (int hn = 0; hn < 2; ++hn) {
-    // W fragments of the next tile's k-step 0 for these four n-blocks (both 32-k halves) and the blocks' bias / c1,
-    // kept over the four row blocks
-    u32x4 afH[2][4];
-    f32x4 bH[4], cH[kLn ? 4 : 1];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      afH[0][q] = *reinterpret_cast<const u32x4*>(af0 + 2048 * (4 * hn + q));
-      afH[1][q] = *reinterpret_cast<const u32x4*>(af1 + 2048 * (4 * hn + q));
-      bH[q] = *reinterpret_cast<const f32x4*>(vb + 64 * (4 * hn + q));
-      if constexpr (kLn) cH[q] = *reinterpret_cast<const f32x4*>(vb + 1024 + 64 * (4 * hn + q));
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const u32x4 b0 = *reinterpret_cast<const u32x4*>(bf0 + 2048 * mt);
-      const u32x4 b1 = *reinterpret_cast<const u32x4*>(bf1 + 2048 * mt);
-      f32x2 ln = {0.f, 1.f};
-      if constexpr (kLn) ln = *reinterpret_cast<const f32x2*>(lnb + 128 * mt);
-      // ---- finish the four blocks (same arithmetic, same order as gemm_epilogue256_lds_impl)
-      u32x2 o[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int nt = 4 * hn + q;
-        float xs[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float x = acc.a[nt][mt][e];
-          if constexpr (kLn)
-            x = __builtin_fmaf(ln[1], __builtin_fmaf(-ln[0], cH[q][e], x), bH[q][e]);
-          else
-            x += bH[q][e];
-          xs[e] = x;
-        }
-        if constexpr (kGelu) {
-#pragma unroll
-          for (int e = 0; e < 4; e += 2) {
-            const gelu_f32x2 y = gelu_erf2((gelu_f32x2){xs[e], xs[e + 1]});
-            xs[e] = y[0];
-            xs[e + 1] = y[1];
-          }
-        }
-        o[q][0] = __builtin_bit_cast(uint32_t, cvt_pk_rne(xs[0], xs[1]));
-        o[q][1] = __builtin_bit_cast(uint32_t, cvt_pk_rne(xs[2], xs[3]));
-      }
-      // ---- the same blocks of the next tile: k-step 0
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc.a[4 * hn + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-            __builtin_bit_cast(f16x8, afH[0][q]), __builtin_bit_cast(f16x8, b0), zero4, 0, 0, 0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc.a[4 * hn + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-            __builtin_bit_cast(f16x8, afH[1][q]), __builtin_bit_cast(f16x8, b1), acc.a[4 * hn + q][mt], 0, 0, 0);
-      // ---- 16 rows x 64 B per store: blocks (nt, nt + 1) side by side
-      char* const orow = obase + ((int64_t)(16 * mt) * g.ldo + 64 * hn) * 2;   // wave-uniform
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const auto s0 = __builtin_amdgcn_permlane16_swap(o[2 * j][0], o[2 * j + 1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane16_swap(o[2 * j][1], o[2 * j + 1][1], false, false);
-        const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};
-#if HCIR_OV_ABL == 4
-        *reinterpret_cast<u32x4*>(orow + 64 * j + voff) = v;
-#else
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(orow + 64 * j + voff));
-#endif
-      }
-      // keep hipcc from hoisting the next sub-passes' reads up here (registers); the hardware overlaps the next
-      // sub-pass's arithmetic with these MFMAs anyway (in-order issue, asynchronous matrix pipe)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_f16_ov_kernel(GemmArgs g, int tiles_n, int tiles_m) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: everything derived from it stays in SGPRs
-  const int wave_n = wave >> 2, wave_m = wave & 3;
-  const int ntiles = tiles_n * tiles_m;
-  const int nkc = g.k / 64;
-  const int my_tiles =
-      (int)blockIdx.x < ntiles ? (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-  const int nsteps = my_tiles * nkc;
-
-  auto tile_origin = [&](int ti, int& n0, int64_t& m0) {
-    const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
-#if HCIR_GEMM_NGROUP > 0
-    const int ngrp = (HCIR_GEMM_NGROUP_WIDE > 0 && tiles_n % HCIR_GEMM_NGROUP_WIDE == 0 && tiles_n > HCIR_GEMM_NGROUP_WIDE)
-                         ? HCIR_GEMM_NGROUP_WIDE : HCIR_GEMM_NGROUP;
-    if (tiles_n % ngrp == 0 && tiles_n > ngrp) {
-      const int per = ngrp * tiles_m;
-      const int grp = t / per, rem = t - grp * per;
-      n0 = (grp * ngrp + rem % ngrp) * 256;
-      m0 = (int64_t)(rem / ngrp) * 256;
-      return;
-    }
-#endif
-    n0 = (t % tiles_n) * 256;
-    m0 = (int64_t)(t / tiles_n) * 256;
-  };
-
-  uint32_t soff[G256::NLOAD];
-  const char* wbase = nullptr;
-  const char* abase = nullptr;
-  auto set_sources = [&](int t_i) {
-    int n0;
-    int64_t m0;
-    tile_origin(t_i, n0, m0);
-    wbase = reinterpret_cast<const char*>(g.w + (int64_t)n0 * g.ldw);
-    abase = reinterpret_cast<const char*>(g.a + m0 * g.lda);
-    int otid = tid;
-    asm volatile("" : "+v"(otid));
-#pragma unroll
-    for (int i = 0; i < G256::NLOAD; ++i) {
-      const int piece = otid + G256::NT * i;
-      const int row = piece >> 3, chunk = (piece & 7) ^ ((row >> 1) & 7);
-      if (row < 256) {
-        const int nr = n0 + row > g.n - 1 ? g.n - 1 - n0 : row;
-        soff[i] = (uint32_t)(((int64_t)nr * g.ldw + chunk * 8) * 2);
-      } else {
-        int64_t mr = row - 256;
-        mr = m0 + mr > g.m - 1 ? g.m - 1 - m0 : mr;
-        soff[i] = (uint32_t)((mr * g.lda + chunk * 8) * 2);
-      }
-    }
-  };
-  int issue_ti = 0, issue_kc = 0;  // next stage to issue
-  auto issue_piece = [&](int slot, int i) {
-    lds_dma16((i < 4 ? wbase : abase) + issue_kc * 128, soff[i],
-              lds_addr(lds) + slot * G256::STAGE_BYTES + ((tid & ~63) + G256::NT * i) * 16);
-  };
-  auto issue_advance = [&]() {
-    if (++issue_kc == nkc) {
-      issue_kc = 0;
-      ++issue_ti;
-      if (issue_ti < my_tiles) set_sources(issue_ti);
-    }
-  };
-
-  WaveAcc<true> acc;
-  acc.zero();
-
-  if (nsteps > 0) {
-    set_sources(0);
-#pragma unroll
-    for (int i = 0; i < G256::NLOAD; ++i) issue_piece(0, i);
-    issue_advance();
-  }
-
-  // tile ti ends in the overlapped boundary when the workgroup has another tile behind it and all 256 rows exist
-  int n0c = 0;
-  int64_t m0c = 0;
-  bool ov = false;
-  auto enter_tile = [&](int ti) {
-    tile_origin(ti, n0c, m0c);
-    ov = ti + 1 < my_tiles && m0c + 256 <= g.m;
-  };
-  if (my_tiles > 0) enter_tile(0);
-
-  const int r16 = lane & 15, kq = lane >> 4;
-  int kc = 0, ti = 0;
-  bool stores_behind = false;   // the step follows a boundary step: its stage is older than that step's 16 stores
-  for (int step = 0; step < nsteps; ++step) {
-    if (stores_behind)
-      asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stores_behind = false;
-    __builtin_amdgcn_s_barrier();
-    HCIR_GSTAMP(ti == 1 && kc == 1, 0);   // diagnostic build: first ordinary k-step of the workgroup's second tile
-    HCIR_GSTAMP(ti == 2 && kc == 1, 5);
-    HCIR_WSTAMP(ti == 2 && kc == 1, 2);
-#ifdef HCIR_DIAG_GSTAMPS
-    if (kc == 1 && (ti == 1 || ti == 2) && threadIdx.x == 0 && blockIdx.x < 256)
-      g_gemm_stamps[blockIdx.x * 8 + (ti == 1 ? 6 : 7)] = __builtin_amdgcn_s_memtime();
-#endif
-
-    const char* st = lds + (step & 1) * G256::STAGE_BYTES;
-    const bool do_issue = step + 1 < nsteps;
-    const int islot = (step + 1) & 1;
-    // last k-step of a tile that ends in the overlapped boundary: request its per-tile vectors (older than this step's
-    // transfers, so they are back before the boundary's wait); they go to LDS at the top of the boundary step
-    const bool fetch_vec = ov && kc == nkc - 1;
-    float v0 = 0.f, v1 = 0.f;
-    if (fetch_vec) {
-      if (tid < 256) {
-        if (g.bias) v0 = g.bias[n0c + tid];
-      } else if constexpr (kLn) {
-        v0 = g.ln_c1[n0c + tid - 256];
-      }
-      if constexpr (kLn) v1 = g.ln_stats[2 * m0c + tid];   // 256 full rows: in range
-    }
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2) {
-      const int chunk = 4 * ks2 + kq;
-      u32x4 bf[4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-        bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(256 + wave_m * 64 + mt * 16 + r16, chunk));
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        u32x4 af[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          af[q] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
-        if (do_issue && ks2 == 0) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) issue_piece(islot, 4 * half + i);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt)
-            acc.a[4 * half + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                __builtin_bit_cast(f16x8, af[q]), __builtin_bit_cast(f16x8, bf[mt]), acc.a[4 * half + q][mt], 0, 0, 0);
-      }
-    }
-    if (do_issue) issue_advance();
-
-    if (++kc == nkc) {
-      if (ov) {
-        // ---- boundary step = epilogue of tile ti + k-step 0 of tile ti+1 (step + 1)
-        ++step;
-        HCIR_GSTAMP(ti == 1, 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        char* vec = lds + GOv::VEC_OFF;
-        reinterpret_cast<float*>(vec)[tid] = v0;
-        if constexpr (kLn) reinterpret_cast<float*>(vec)[512 + tid] = v1;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        HCIR_GSTAMP(ti == 1, 2);
-        const char* st1 = lds + (step & 1) * G256::STAGE_BYTES;
-        if (step + 1 < nsteps) {   // always: nkc >= 2
-#pragma unroll
-          for (int i = 0; i < G256::NLOAD; ++i) issue_piece((step + 1) & 1, i);
-          issue_advance();
-        }
-        HCIR_GSTAMP(ti == 1, 3);
-        HCIR_WSTAMP(ti == 1, 0);
-        gemm_ov_boundary<EPI>(g, acc, st1, vec,
-                              m0c + wave_m * 64, n0c + wave_n * 128, wave_n, wave_m, lane);
-        HCIR_GSTAMP(ti == 1, 4);
-        HCIR_WSTAMP(ti == 1, 1);
-        stores_behind = true;
-        kc = 1;
-      } else {
-        __builtin_amdgcn_s_barrier();
-        gemm_epilogue256_lds<EPI, true>(g, acc, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
-                                        m0c + wave_m * 64, n0c + wave_n * 128, lane);
-        acc.zero();
-        kc = 0;
-      }
-      ++ti;
-      if (ti < my_tiles) enter_tile(ti);
       if (issue_ti < my_tiles) set_sources(issue_ti);
     }
   }
@@ -1236,7 +737,7 @@ __device__ __forceinline__ void gemm_epilogue16_lds_impl(const GemmArgs& g, cons
       bias[pass][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       scale[pass][j] = (f32x4){1.f, 1.f, 1.f, 1.f};
       if (g.bias) bias[pass][j] = *reinterpret_cast<const f32x4*>(g.bias + n);
-      if (kAffine || ((EPI == HCIR_EPI_BIAS_RESID_F32 || kResidH) && g.scale))
+      if (kAffine || (EPI == HCIR_EPI_BIAS_RESID_F32 && g.scale))
         scale[pass][j] = *reinterpret_cast<const f32x4*>(g.scale + n);
     }
   }
@@ -1480,16 +981,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
   };
   int issue_ti = 0, issue_kc = 0;
   auto issue_piece = [&](int slot, int i) {  // i constant after unrolling: pieces 0..3 W rows, 4..9 activation rows
-#ifndef HCIR_GEMM_BUILTIN_DMA
     lds_dma16((i < GMid::NW ? wbase : abase) + issue_kc * 128, soff[i],
               lds_addr(lds) + slot * GMid::STAGE_BYTES + ((tid & ~63) + GMid::NT * i) * 16);
-#else
-    const char* sp = (i < GMid::NW ? wbase : abase) + issue_kc * 128 + soff[i];
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)sp,
-        (__attribute__((address_space(3))) void*)(lds + slot * GMid::STAGE_BYTES + ((tid & ~63) + GMid::NT * i) * 16),
-        16, 0, 0);
-#endif
   };
   auto issue_advance = [&]() {
     if (++issue_kc == nkc) {
@@ -1772,48 +1265,21 @@ inline bool gemm_takes_big(int64_t m, int n, int k) { return k % 64 == 0 && m >=
 template <int EPI>
 void launch_gemm_mid(const GemmArgs& g, hipStream_t st);
 
-// The 256 x 256 persistent kernel over tn x tm tiles (with -DHCIR_GEMM_OVERLAP: the overlapped-boundary experiment
-// for the epilogues it covers, when some workgroup gets a second tile).
+// The 256 x 256 persistent kernel over tn x tm tiles
 template <int EPI>
 void launch_big_tiles(const GemmArgs& g, int tn, int tm, hipStream_t st) {
   const int grid = tn * tm < 256 ? tn * tm : 256;  // persistent: one workgroup per CU
-#ifdef HCIR_GEMM_MFMA32
-  hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, false>), dim3(grid), dim3(512), 0, st, g, tn, tm);
-#else
-#ifdef HCIR_GEMM_OVERLAP   // EXPERIMENT (build flag; measured flat to -5 %, see the kernel's header): off by default
-  if constexpr (EPI == HCIR_EPI_BIAS_F16 || EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_F16 ||
-                EPI == EPI_LN_BIAS_GELU_F16) {
-    if (g.k >= 128 && tn * tm > grid) {
-      // 148 KB of dynamic LDS: one attribute call per instantiation; a refusal falls back to the plain kernel
-      static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16_ov_kernel<EPI>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   GOv::LDS_BYTES) == hipSuccess;
-      if (attr) {
-        hipLaunchKernelGGL((gemm_f16_ov_kernel<EPI>), dim3(grid), dim3(512), GOv::LDS_BYTES, st, g, tn, tm);
-        return;
-      }
-    }
-  }
-#endif
-  hipLaunchKernelGGL((gemm_f16_big_kernel<EPI, true>), dim3(grid), dim3(512), 0, st, g, tn, tm);
-#endif
+  hipLaunchKernelGGL((gemm_f16_big_kernel<EPI>), dim3(grid), dim3(512), 0, st, g, tn, tm);
 }
 
 template <int EPI>
 void launch_gemm_big(const GemmArgs& g, hipStream_t st) {
-#ifdef HCIR_GEMM_MID
-  if (g.n % 128 == 0) {   // EXPERIMENT (build flag): every persistent-kernel shape on the 2-workgroups-per-CU kernel
-    launch_gemm_mid<EPI>(g, st);
-    return;
-  }
-#endif
   const int tn = (int)hcir_cdiv(g.n, 256), tm = (int)hcir_cdiv(g.m, 256);
-#if !defined(HCIR_GEMM_NO_TAIL_SPLIT) && !defined(HCIR_GEMM_MFMA32)
-  // Tail split: when the last round of 256 x 256 tiles would be less than half full (64 images: fc1 = 600 tiles = 2.34
-  // rounds; ViT-L/14 at 128 images: 516 / 1548 / 2064 tiles = 2.02 / 6.05 / 8.06 rounds - a whole round for a sliver),
-  // the m-tiles that fill whole rounds run here and the remaining ROWS go to the 128 x 192 kernel as a second launch
-  // (pointers advanced to the row range; the per-row statistics keep the full matrix's slice pitch).
   if constexpr (EPI != EPI_BIAS_F16_DUAL_GELU) {
+    // Tail split: when the last round of 256 x 256 tiles would be less than half full (64 images: fc1 = 600 tiles = 2.34
+    // rounds; ViT-L/14 at 128 images: 516 / 1548 / 2064 tiles = 2.02 / 6.05 / 8.06 rounds - a whole round for a sliver),
+    // the m-tiles that fill whole rounds run on the 256 x 256 kernel and the remaining ROWS go to the 128 x 192 kernel
+    // as a second launch (pointers advanced to the row range; the per-row statistics keep the full matrix's slice pitch).
     const int ntiles = tn * tm;
     const int tm1 = (ntiles / 256) * 256 / tn;          // m-tiles of the whole rounds
     const int tail_tiles = ntiles - tm1 * tn;
@@ -1836,21 +1302,14 @@ void launch_gemm_big(const GemmArgs& g, hipStream_t st) {
       launch_gemm_mid<EPI>(g2, st);
       return;
     }
-  }
-#endif
-#if !defined(HCIR_GEMM_NO_MID_SMALL) && !defined(HCIR_GEMM_MFMA32)
-  // Small M: a launch whose 256 x 256 tiles fill less than 0.7 of ONE round of the 256 CUs (64 images: proj / fc2 give
-  // 150 tiles) runs on the 128 x 192 kernel at two workgroups per CU instead - 2.7 x the tiles, every CU busy; its
-  // results are bit-identical (same k order).  12 % slower per flop on full rounds, which is why only these take it.
-  if constexpr (EPI != EPI_BIAS_F16_DUAL_GELU) {
+    // Small M: a launch whose 256 x 256 tiles fill less than 0.7 of ONE round of the 256 CUs (64 images: proj / fc2
+    // give 150 tiles) runs on the 128 x 192 kernel at two workgroups per CU instead - 2.7 x the tiles, every CU busy;
+    // its results are bit-identical (same k order).  12 % slower per flop on full rounds, which is why only these take it.
     if (tn * tm * 10 < 256 * 7 && g.n % GMid::TN == 0 && (g.n / GMid::TN) * hcir_cdiv(g.m, GMid::TM) <= 512) {
       launch_gemm_mid<EPI>(g, st);
       return;
     }
   }
-#endif
-  // MFMA shape: a BUILD flag (make CXXFLAGS+=-DHCIR_GEMM_MFMA32 builds the 32x32x16 variant for A/B runs through
-  // HCIR_LIB_PATH); the library reads no environment variables
   launch_big_tiles<EPI>(g, tn, tm, st);
 }
 
@@ -1934,23 +1393,16 @@ int hcir_gemm_f16_gelu_dual(const void* a, int64_t lda, const void* w, int64_t l
   if (!a || !w || !out_pre || !out_act || m <= 0 || n <= 0 || k <= 0) return HCIR_ERR_INVALID;
   if (lda < k || ldw < k || (lda & 7) || (ldw & 7) || ldo < n || (ldo & 7)) return HCIR_ERR_INVALID;
   if (!gemm_takes_big(m, n, k)) return HCIR_ERR_UNSUPPORTED;
-#if defined(HCIR_GEMM_MFMA32) || defined(HCIR_GEMM_MID)
-  return HCIR_ERR_UNSUPPORTED;
-#else
   GemmArgs g{static_cast<const _Float16*>(a), static_cast<const _Float16*>(w), bias, nullptr, out_pre, m,
              lda, ldw, ldo, n, k, nullptr, nullptr, nullptr, out_pre, out_act};
   launch_gemm_big<EPI_BIAS_F16_DUAL_GELU>(g, static_cast<hipStream_t>(stream));
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
-#endif
 }
 
 #ifdef HCIR_DIAG_GSTAMPS
 int hcir_debug_gemm_stamps(unsigned long long* host_dst) {
   return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_gemm_stamps), sizeof(unsigned long long) * 256 * 8);
-}
-int hcir_debug_gemm_wstamps(unsigned long long* host_dst) {
-  return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_gemm_wstamps), sizeof(unsigned long long) * 256 * 24);
 }
 #endif
 

@@ -48,12 +48,7 @@ constexpr uint32_t kStop = 64;
 __device__ __forceinline__ uint32_t pack_lit(uint32_t step, uint32_t byte) { return step | (S_LIT << 7) | (byte << 9); }
 // Two literals behind one another as ONE entry (bit 17: a second byte follows in bits 18-25; step = both codes): the
 // walk is the serial part of the decoder, and 65-81 % of a hair crop's symbols are literals of 4.6-5.1 bits - a pair
-// per step saves 22-31 % of the steps (root-10 lookups: both codes <= 10 bits).  -DHCIR_PNG_NO_PAIRS: A/B switch.
-#ifdef HCIR_PNG_NO_PAIRS
-constexpr bool kPairLits = false;
-#else
-constexpr bool kPairLits = true;
-#endif
+// per step saves 22-31 % of the steps (root-10 lookups: both codes <= 10 bits).
 __device__ __forceinline__ uint32_t pack_lit2(uint32_t step, uint32_t b1, uint32_t b2) {
   return step | (S_LIT << 7) | (b1 << 9) | (1u << 17) | (b2 << 18);
 }
@@ -430,7 +425,7 @@ __device__ __forceinline__ void lookup_span(const Smem3* sm, const uint32_t* lo,
     d32[r] = (uint32_t)(w1 >> eb);  // >= 44 valid bits were left: a distance takes at most 28
     e2[r] = sm->dist_tab[d32[r] & ((1 << kDistRoot) - 1)];
     // behind a literal (eb = 0: d32 = the bits behind its code): the literal / length entry of the NEXT symbol
-    if constexpr (kPairLits) e1b[r] = sm->lit_tab[d32[r] & ((1 << kLitRoot) - 1)];
+    e1b[r] = sm->lit_tab[d32[r] & ((1 << kLitRoot) - 1)];
   }
 #pragma unroll
   for (int r = 0; r < kSpan; ++r) {
@@ -440,21 +435,16 @@ __device__ __forceinline__ void lookup_span(const Smem3* sm, const uint32_t* lo,
     // a long or invalid code: the walk stops there and it is decoded serially
     uint32_t res = kStop | (S_SLOW << 7);
     if (k1 == K_LIT) res = pack_lit(n1, e1[r] >> 16);
-    if constexpr (kPairLits) {
-      if (k1 == K_LIT && ((e1b[r] >> 4) & 7) == K_LIT) res = pack_lit2(n1 + (e1b[r] & 15), e1[r] >> 16, e1b[r] >> 16);
-    }
+    if (k1 == K_LIT && ((e1b[r] >> 4) & 7) == K_LIT) res = pack_lit2(n1 + (e1b[r] & 15), e1[r] >> 16, e1b[r] >> 16);
     if (k1 == K_EOB) res = kStop | (S_EOB << 7) | (n1 << 9);
     if (k1 == K_LEN && k2 == K_DIST) res = pack_match(n1 + eb + dn + deb, len[r], dist);
     out[r] = res;
   }
 }
 
-#ifndef HCIR_PNG_SLOW_INLINE
-#define HCIR_PNG_SLOW_INLINE __noinline__
-#endif
 // the same for ONE position, serially, with the long codes searched (wave-uniform).  The packed symbol; for the
 // end of the block kStop | S_EOB | its code length << 9; ~0: no valid symbol starts here.
-__device__ HCIR_PNG_SLOW_INLINE uint32_t lookup_slow(uint32_t lo, uint32_t hi, Smem3* sm, int lane) {
+__device__ __noinline__ uint32_t lookup_slow(uint32_t lo, uint32_t hi, Smem3* sm, int lane) {
   lo = U(lo);
   hi = U(hi);
   uint32_t e1 = U(sm->lit_tab[lo & ((1 << kLitRoot) - 1)]);
@@ -482,7 +472,10 @@ __device__ HCIR_PNG_SLOW_INLINE uint32_t lookup_slow(uint32_t lo, uint32_t hi, S
 // Written out: six scalar instructions per symbol and one conditional branch.  Measured on gfx950
 // (tools/ubench/walk_latency.hip): v_readlane -> SALU -> v_readlane round trip 29 cycles, a dependent SALU
 // instruction 4, a conditional branch 16 NOT taken and 20 taken - the branch count is what this loop is built around.
-#ifndef HCIR_PNG_WALK_BRANCHFREE   // default: a conditional branch behind every step (16 cycles even when not taken)
+// (A branch-free step - entry, mark and advance selected away once the chain has left the window, four steps back to
+// back, one branch behind them: nine scalar instructions per symbol - was measured and rejected: walk 69 -> 79 and
+// 83 -> 105 cycles per symbol, the 880-image launch 45.0 -> 52.6 ms; the selects lengthen the dependent chain by more
+// than the branch costs.)
 #define HCIR_WALK_STEP(C, M, X)          \
   "v_readlane_b32 %[e], %[" C "], %[p]\n\t" \
   "s_bitset1_b64 %[" M "], %[p]\n\t"        \
@@ -491,26 +484,6 @@ __device__ HCIR_PNG_SLOW_INLINE uint32_t lookup_slow(uint32_t lo, uint32_t hi, S
   "s_cmp_gt_u32 %[p], 63\n\t"               \
   "s_cbranch_scc1 " X "_%=\n\t"
 #define HCIR_WALK_STEPS(C, M, X) HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X)
-#else
-// EXPERIMENT (build flag), measured and rejected: a branch-free step - once the chain has left the window (p >= 64) a
-// step changes nothing (entry, mark and advance are selected away), four steps back to back, ONE branch behind them:
-// nine scalar instructions per symbol.  Walk 69 -> 79 and 83 -> 105 cycles per symbol, the 880-image launch 45.0 ->
-// 52.6 ms (same box, interleaved): the selects lengthen the dependent chain by more than the branch costs.
-#define HCIR_WALK_STEP(C, M, X)              \
-  "v_readlane_b32 %[e2], %[" C "], %[p]\n\t" \
-  "s_and_b32 %[t], %[e2], 127\n\t"           \
-  "s_lshl_b64 %[b], 1, %[p]\n\t"             \
-  "s_cmp_lt_u32 %[p], 64\n\t"                \
-  "s_cselect_b32 %[e], %[e2], %[e]\n\t"      \
-  "s_cselect_b32 %[t], %[t], 0\n\t"          \
-  "s_cselect_b64 %[b], %[b], 0\n\t"          \
-  "s_or_b64 %[" M "], %[" M "], %[b]\n\t"    \
-  "s_add_u32 %[p], %[p], %[t]\n\t"
-#define HCIR_WALK_STEPS(C, M, X)                                                                     \
-  HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X) HCIR_WALK_STEP(C, M, X) \
-  "s_cmp_gt_u32 %[p], 63\n\t"                                                                     \
-  "s_cbranch_scc1 " X "_%=\n\t"
-#endif
 #define HCIR_WALK_WINDOW(N, C, M, NEXT)                                                                    \
   ".Lw" N "_%=:\n\t" HCIR_WALK_STEPS(C, M, ".Lx" N) "s_branch .Lw" N "_%=\n"                             \
   ".Lx" N "_%=:\n\t"                                                                                       \
@@ -522,7 +495,7 @@ __device__ HCIR_PNG_SLOW_INLINE uint32_t lookup_slow(uint32_t lo, uint32_t hi, S
   "s_branch .Lend_%=\n"
 __device__ __forceinline__ void walk4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t& w, uint32_t& p,
                                       uint64_t& m0, uint64_t& m1, uint64_t& m2, uint64_t& m3, uint32_t& e) {
-  uint32_t t, e2;
+  uint32_t t, e2;  // (e2, b: unused by the steps; as operands they keep the kernel's SGPR allocation as it was measured)
   uint64_t b;
   asm volatile(
       "s_mov_b64 %[m0], 0\n\ts_mov_b64 %[m1], 0\n\ts_mov_b64 %[m2], 0\n\ts_mov_b64 %[m3], 0\n\t"
@@ -623,7 +596,7 @@ __device__ __noinline__ void resolve_ordered(Smem3* sm, uint32_t sym, uint32_t m
 __device__ __forceinline__ uint32_t resolve(Smem3* sm, uint32_t sym, uint32_t nsym, uint32_t wp, int lane, bool* bad) {
   constexpr uint32_t M = kRing - 1;
   const bool live = (uint32_t)lane < nsym, is_match = live && ((sym >> 7) & 1);
-  const bool lit2 = kPairLits && live && !is_match && ((sym >> 17) & 1);   // (a literal's bits 17.. are its own)
+  const bool lit2 = live && !is_match && ((sym >> 17) & 1);   // (a literal's bits 17.. are its own)
   const uint32_t mylen = !live ? 0u : (is_match ? ((sym >> 9) & 255u) + 3u : (lit2 ? 2u : 1u));
   const uint32_t mydist = (sym >> 17) + 1u;
   const float myrd = 1.0f / (float)mydist, lanef = (float)lane;
@@ -637,7 +610,7 @@ __device__ __forceinline__ uint32_t resolve(Smem3* sm, uint32_t sym, uint32_t ns
     return tot;
   }
   if ((lits >> lane) & 1) sm->ring[mypos & M] = (uint8_t)(sym >> 9);  // every literal at once
-  if constexpr (kPairLits) {   // second bytes; a lane without one writes its dump byte instead of toggling EXEC
+  {   // second bytes; a lane without one writes its dump byte instead of toggling EXEC
     const uint32_t off2 = lit2 ? ((mypos + 1) & M) : (uint32_t)(__builtin_offsetof(Smem, dump) + lane);
     const __attribute__((address_space(3))) uint8_t* base = sm->ring;
     const_cast<__attribute__((address_space(3))) uint8_t*>(base)[off2] = (uint8_t)(sym >> 18);
@@ -697,14 +670,14 @@ __device__ __forceinline__ uint32_t lds_load(const __attribute__((address_space(
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   return U(v);
 }
-__device__ __forceinline__ void lds_store(__attribute__((address_space(3))) uint32_t* p, uint32_t v, int lane) {
+__device__ __forceinline__ void lds_put(__attribute__((address_space(3))) uint32_t* p, uint32_t v, int lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   if (lane == 0) *reinterpret_cast<volatile __attribute__((address_space(3))) uint32_t*>(p) = v;
 }
 constexpr uint32_t kPollLimit = 1u << 22;  // polls of ~64 cycles: a wave that waits longer than this gives up (corrupt)
 
-template <bool LW>  // LW: a third wavefront does the lookups (lookup_wave); else this one does its own
+// the decoding wavefront; a third wavefront does its lookups (lookup_wave)
 __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const uint8_t* stream, uint32_t stream_bytes,
                                            int lane, uint64_t* diag) {
   const uint32_t total_bits = stream_bytes * 8u;
@@ -741,8 +714,8 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
   };
   uint32_t lk_seq = 0;  // passes requested so far
   auto request_lookup = [&](uint32_t at) {
-    lds_store(&sm->lk_wbase, at, lane);
-    lds_store(&sm->lk_req, ++lk_seq, lane);
+    lds_put(&sm->lk_wbase, at, lane);
+    lds_put(&sm->lk_req, ++lk_seq, lane);
   };
   auto wait_lookup = [&]() -> bool {  // until the last requested pass is in ent_buf
     for (uint32_t polls = 0; lds_load(&sm->lk_ready) != lk_seq; ++polls) {
@@ -790,7 +763,7 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
         if (room_for(64) < 64) break;
         if ((uint32_t)lane < n) sm->symq[(tail + lane) & (kQueue - 1)] = pack_lit(0, stream[src + lane]);
         tail += n;
-        lds_store(&sm->q_tail, tail, lane);
+        lds_put(&sm->q_tail, tail, lane);
         src += n;
         len -= n;
       }
@@ -801,10 +774,8 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
     // starts in a 64-bit mask per window.  Marked entries are appended to the symbol queue by their lanes.
     uint32_t wbase = bp, pos = 0;  // pass origin; next symbol's start relative to it
     bool eob = false;
-    if constexpr (LW) {
-      if (!wait_lookup()) break;   // a request of the previous block may still be in the works (its tables are gone)
-      request_lookup(wbase);
-    }
+    if (!wait_lookup()) break;   // a request of the previous block may still be in the works (its tables are gone)
+    request_lookup(wbase);
     while (!eob && !err && !stop) {
       if (wbase + pos > total_bits) {  // ran past the end of the stream
         err = 1;
@@ -815,14 +786,10 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
       uint32_t ent[kSpan];
       STAMP(0);
       COUNT(2, 1);
-      if constexpr (LW) {
-        if (!wait_lookup()) break;
+      if (!wait_lookup()) break;
 #pragma unroll
-        for (int r = 0; r < kSpan; ++r) ent[r] = sm->ent_buf[r][lane];
-        request_lookup(wbase + 64 * kSpan);
-      } else {
-        span_windows(in, wbase, lane, sm, ent);
-      }
+      for (int r = 0; r < kSpan; ++r) ent[r] = sm->ent_buf[r][lane];
+      request_lookup(wbase + 64 * kSpan);
       STAMP(2);
       // ---- walk segments of the pass: one, plus one behind every serially decoded symbol
       for (bool more = true; more;) {
@@ -882,7 +849,7 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
           }
           STAMP(7);
         }
-        lds_store(&sm->q_tail, tail, lane);
+        lds_put(&sm->q_tail, tail, lane);
         COUNT(0, n0 + n1 + n2 + n3);
         if (stopped && ((e >> 7) & 3) == S_EOB) {
           eob = true;
@@ -896,9 +863,9 @@ __device__ __forceinline__ int decode_wave(const PngBatch& a, Smem3* sm, const u
     }
     if (bp > total_bits) err = 1;
   }
-  lds_store(&sm->q_tail, tail, lane);
-  lds_store(&sm->q_eos, 1u, lane);
-  lds_store(&sm->lk_quit, 1u, lane);
+  lds_put(&sm->q_tail, tail, lane);
+  lds_put(&sm->q_eos, 1u, lane);
+  lds_put(&sm->lk_quit, 1u, lane);
 #ifdef HCIR_PNG_STAMPS
   STAMP(0);
   if (lane == 0 && diag) {
@@ -936,7 +903,7 @@ __device__ __forceinline__ void lookup_wave(Smem3* sm, const uint8_t* stream, ui
 #pragma unroll
     for (int r = 0; r < kSpan; ++r) sm->ent_buf[r][lane] = ent[r];
     seen = req;
-    lds_store(&sm->lk_ready, req, lane);
+    lds_put(&sm->lk_ready, req, lane);
   }
 }
 
@@ -966,7 +933,7 @@ __device__ __forceinline__ int copy_wave(const PngBatch& a, Smem3* sm, uint8_t* 
     bool bad;
     wp += resolve(sm, sym, nsym, wp, lane, &bad);
     head += nsym;
-    lds_store(&sm->q_head, head, lane);
+    lds_put(&sm->q_head, head, lane);
     STAMP(4);
     WAVE_SYNC();
     flush_units(sm, raw, flushed, wp, need, lane);
@@ -974,7 +941,7 @@ __device__ __forceinline__ int copy_wave(const PngBatch& a, Smem3* sm, uint8_t* 
     if (bad) err = 1;
     if (bad || wp >= need) break;
   }
-  lds_store(&sm->q_stop, 1u, lane);  // whatever the reason: the decoder need not go on
+  lds_put(&sm->q_stop, 1u, lane);  // whatever the reason: the decoder need not go on
   if (!err && wp < need) err = 1;    // the stream ends before the last scanline the window needs (or the decoder failed)
   if (!err && flushed < need) {      // the last, partial unit (the buffer has 1 KB of slack behind `need`)
     WAVE_SYNC();
@@ -993,8 +960,7 @@ __device__ __forceinline__ int copy_wave(const PngBatch& a, Smem3* sm, uint8_t* 
   return err;
 }
 
-template <bool LW>
-__global__ __launch_bounds__(LW ? 192 : 128) void png_inflate_kernel(PngBatch a) {
+__global__ __launch_bounds__(192) void png_inflate_kernel(PngBatch a) {
   __shared__ __attribute__((aligned(16))) Smem smem;
   Smem3* sm = (Smem3*)&smem;
 
@@ -1025,7 +991,7 @@ __global__ __launch_bounds__(LW ? 192 : 128) void png_inflate_kernel(PngBatch a)
 #endif
   int err = 0;
   if (wave == 0)
-    err = decode_wave<LW>(a, sm, a.blob + hp->stage_offset, hp->stream_bytes, lane, diag);
+    err = decode_wave(a, sm, a.blob + hp->stage_offset, hp->stream_bytes, lane, diag);
   else if (wave == 1)
     err = copy_wave(a, sm, a.raw + (uint64_t)img * a.raw_stride, need, lane, diag);
   else
@@ -1275,19 +1241,12 @@ extern "C" int hcir_png_decode_window_u8(const void* blob_dev, const hcir_png_he
   a.raw_stride = p.raw_stride;
   a.status = status_dev ? status_dev : reinterpret_cast<int32_t*>(ws + (size_t)b * p.raw_stride);
   a.diag = reinterpret_cast<uint64_t*>(ws + (((size_t)b * p.raw_stride + (size_t)b * 4 + 255) & ~(size_t)255));
-  // A third wavefront per image does the lookups (png_inflate_kernel<true>): it shortens every image's serial chain.
+  // A third wavefront per image does the lookups: it shortens every image's serial chain.
   // Before the literal pairs a full chip (four images per CU) had no issue slots to spare for it (46.6 against 44.4 ms
   // per 880 files) and launches of more than 600 images ran two wavefronts per image; with pairs the lookup is the
   // largest share of a decoding wavefront's time and the third wavefront wins everywhere (same box, tools/ab_png.py:
   // 256 files 26.0 against 34.8 ms, 880 files 32.4 against 39.3 ms, 1760 files 63.1 against 77.5 ms).
-  // -DHCIR_PNG_LW_MAX=<images>: A/B switch (0: never).
-#ifndef HCIR_PNG_LW_MAX
-#define HCIR_PNG_LW_MAX 0x7fffffff
-#endif
-  if (b <= HCIR_PNG_LW_MAX)
-    hipLaunchKernelGGL(png_inflate_kernel<true>, dim3((unsigned)b), dim3(192), 0, st, a);
-  else
-    hipLaunchKernelGGL(png_inflate_kernel<false>, dim3((unsigned)b), dim3(128), 0, st, a);
+  hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)b), dim3(192), 0, st, a);
   HCIR_LAUNCH_CHECK();
   const size_t lds = (size_t)64 * kRawPitch + ((size_t)p.max_x1 + 64) * 4;  // + the 64 dump words behind the row
   if (p.any[1]) hipLaunchKernelGGL(png_unfilter_kernel<1>, dim3((unsigned)b), dim3(64), lds, st, a);

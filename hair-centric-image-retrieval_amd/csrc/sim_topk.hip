@@ -27,9 +27,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#ifndef HCIR_SCAN_AUX
-#define HCIR_SCAN_AUX 2  // cache policy of the once-read gallery stream: 2 = nt (non-temporal), +5 % GB/s
-#endif
+constexpr int kScanAux = 2;  // cache policy of the once-read gallery stream: 2 = nt (non-temporal), +5 % GB/s
 
 #ifdef HCIR_DIAG_STAMPS
 // diagnostic build only (tools/build_variant.sh stamps "-DHCIR_DIAG_STAMPS"): wall-clock stamps (100 MHz) of the
@@ -285,33 +283,15 @@ __global__ __launch_bounds__(256, ((KP == 16 && QT == 1 && WQ == 2 && WGG == 2 &
     const char* gb = reinterpret_cast<const char*>(g) + (r0 * a.d) * (int64_t)sizeof(T) + issue_kc * 128;
     const char* qb = reinterpret_cast<const char*>(q) + (q_row0 * a.d) * (int64_t)sizeof(T) + issue_kc * 128;
     char* dst = lds + slot * Cfg::STAGE_BYTES + (tid & ~63) * 16;
-#ifndef HCIR_SIM_BUILTIN_DMA
 #pragma unroll
     for (int i = 0; i < NPG; ++i) {
-      if (a.shared_stream || HCIR_SCAN_AUX == 0)
+      if (a.shared_stream || kScanAux == 0)
         lds_dma16_v(gb + goff[i], lds_addr(dst) + Cfg::NT * i * 16);
       else
         lds_dma16_v_nt(gb + goff[i], lds_addr(dst) + Cfg::NT * i * 16);
     }
 #pragma unroll
     for (int i = 0; i < NPQ; ++i) lds_dma16_v(qb + qoff[i], lds_addr(dst) + Cfg::NT * (NPG + i) * 16);
-#else
-#pragma unroll
-    for (int i = 0; i < NPG; ++i) {
-      if (a.shared_stream)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb + goff[i]),
-                                         (__attribute__((address_space(3))) void*)(dst + Cfg::NT * i * 16), 16, 0, 0);
-      else
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb + goff[i]),
-                                         (__attribute__((address_space(3))) void*)(dst + Cfg::NT * i * 16), 16, 0,
-                                         HCIR_SCAN_AUX);
-    }
-#pragma unroll
-    for (int i = 0; i < NPQ; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qb + qoff[i]),
-                                       (__attribute__((address_space(3))) void*)(dst + Cfg::NT * (NPG + i) * 16), 16,
-                                       0, 0);
-#endif
     if (++issue_kc == nkc) {
       issue_kc = 0;
       ++issue_tile;
@@ -629,17 +609,10 @@ __global__ __launch_bounds__(512, 2) void sim_scan_big_kernel(BigScanArgs a) {
     }
   };
   auto issue_piece = [&](int slot, int i) {  // i is a constant after unrolling
-#ifndef HCIR_SIM_BUILTIN_DMA   // the transfer outside the compiler's view (common.h lds_dma16): big scan +3.8 %, streaming
-                               // scans +0.7..1.4 % against the builtin (kept behind this flag for A/B runs)
+    // the transfer outside the compiler's view (common.h lds_dma16): big scan +3.8 %, streaming scans +0.7..1.4 %
+    // against __builtin_amdgcn_global_load_lds
     lds_dma16((i < 4 ? gbase : qbase) + issue_kc * 128, i < 4 ? goff[i & 3] : qoff[i & 3],
               lds_addr(lds) + slot * STAGE + ((tid & ~63) + 512 * i) * 16);
-#else
-    const char* sp = (i < 4 ? gbase + goff[i & 3] : qbase + qoff[i & 3]) + issue_kc * 128;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sp,
-                                     (__attribute__((address_space(3))) void*)(lds + slot * STAGE +
-                                                                                ((tid & ~63) + 512 * i) * 16),
-                                     16, 0, 0);
-#endif
   };
   auto issue_advance = [&]() {
     if (++issue_kc == nkc) {
@@ -1464,14 +1437,8 @@ constexpr int kMaxGridX = 512;  // 2 workgroups per CU; also <= 576 lists per me
 // THREE workgroups per CU for the streaming launches (768 workgroups; the floorless launches get the batch-insertion
 // kernel of the one-query-tile geometry, two per CU) instead of two <two query tiles> workgroups with 40 KB stages.
 // Same-box A/B, 1 M x 768 fp16, 64 queries (tools/ab_sim.py): 318 -> 307 us (the prefix launch 52 -> 38 us; the main
-// scan unchanged at 5.7 TB/s).  -DHCIR_SCAN_Q64_TWO_TILES builds the earlier geometry.
-#ifndef HCIR_SCAN_Q64_TWO_TILES
-constexpr bool kQ64ThreePerCU = true;
+// scan unchanged at 5.7 TB/s).
 constexpr int kMaxGridQ64 = 768;
-#else
-constexpr bool kQ64ThreePerCU = false;
-constexpr int kMaxGridQ64 = kMaxGridX;
-#endif
 constexpr int kMaxParts = kMaxGridQ64 > kMaxGridX ? kMaxGridQ64 : kMaxGridX;
 
 // Workgroups along the gallery for `qblocks` query blocks.  Every query block scans every gallery tile; the
@@ -1497,7 +1464,7 @@ Plan make_plan(int64_t nq, int64_t ng, int k) {
     p.qb = nq <= 32 ? 32 : (nq <= 64 ? 64 : 128);
   }
   p.gm = p.qb == 128 ? 128 : 256;
-  if (kQ64ThreePerCU && p.kp == 16 && p.qb == 64) p.gm = 128;   // <QT 1, WQ 2, WGG 2>: 128-row tiles, 3 workgroups per CU
+  if (p.kp == 16 && p.qb == 64) p.gm = 128;   // <QT 1, WQ 2, WGG 2>: 128-row tiles, 3 workgroups per CU
   const int64_t tiles = hcir_cdiv(ng, p.gm);
   p.grid_main = (int)(tiles < kMaxGridX ? tiles : kMaxGridX);
   // prefix: ~1/16 of the gallery, at least 64 rows per list-k, in whole tiles
@@ -1614,10 +1581,7 @@ void launch_scan(const Plan& p, const ScanArgs& a, int grid_x, hipStream_t st) {
   } else if (p.qb == 32) {
     launch_scan_cfg<T, 16, 1, 1, 4>(a, grid_x, grid_y, st);
   } else if (p.qb == 64) {
-    if (kQ64ThreePerCU)
-      launch_scan_cfg<T, 16, 1, 2, 2>(a, grid_x, grid_y, st);
-    else
-      launch_scan_cfg<T, 16, 2, 1, 4>(a, grid_x, grid_y, st);
+    launch_scan_cfg<T, 16, 1, 2, 2>(a, grid_x, grid_y, st);
   } else {
     launch_scan_cfg<T, 16, 2, 2, 2>(a, grid_x, grid_y, st);
   }
@@ -1648,16 +1612,6 @@ void launch_cand_dtype(int dtype, int qb, const ScanArgs& a, int grid_x, hipStre
     launch_cand<_Float16>(qb, a, grid_x, st);
   else
     launch_cand<__bf16>(qb, a, grid_x, st);
-}
-
-// -DHCIR_SCAN_NO_BIG (build flag) keeps the list-keeping scan for every query count (A/B libraries through
-// HCIR_LIB_PATH); the library reads no environment variables
-inline bool big_scan_enabled() {
-#ifdef HCIR_SCAN_NO_BIG
-  return false;
-#else
-  return true;
-#endif
 }
 
 void launch_scan_dtype(int dtype, const Plan& p, const ScanArgs& a, int grid_x, hipStream_t st) {
@@ -1772,7 +1726,7 @@ int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t 
       c.row_begin = 0;
       c.row_end = S;
       // (the 16-entry list kernel of 33..64 queries works on 128-row tiles)
-      const int gm_a = (kQ64ThreePerCU && pc.qb == 64) ? 128 : pc.gm;
+      const int gm_a = pc.qb == 64 ? 128 : pc.gm;
       const int grid_a = scan_grid_x(hcir_cdiv(S, gm_a), qbl);
       launch_scan_dtype(dtype, pc, c, grid_a, st);
       HCIR_LAUNCH_CHECK();
@@ -1851,7 +1805,7 @@ int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t 
   // buffers require.  With r = rows behind the prefix / prefix rows, the number of rows that beat the
   // prefix's k-th score is negative-binomial: mean k r, variance k r (1 + r) ~ (r sqrt k)^2; r is chosen so that
   // mean + 5 sigma fits the buffer (overflow ~1e-6 per query for a gallery in random order; it is handled).
-  const bool big = big_scan_enabled() && p.npass == 1 && p.prefix < ng && dtype != HCIR_F32 && nq > 128 && k <= 16 &&
+  const bool big = p.npass == 1 && p.prefix < ng && dtype != HCIR_F32 && nq > 128 && k <= 16 &&
                    d % 64 == 0 && !q_inv_norm && !g_inv_norm && ng - p.prefix >= 4096;
   if (big) {
     // (measured flat in r = 8..26 at 220 queries: a shorter prefix is paid back by a longer candidate merge;
@@ -1953,7 +1907,7 @@ int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t 
       a.gate = overflow;  // the launches below: fallback only
     }
     const int64_t tiles_b = hcir_cdiv(ng - pp.prefix, p.gm);
-    const bool q64g3 = kQ64ThreePerCU && p.kp == 16 && p.qb == 64;
+    const bool q64g3 = p.kp == 16 && p.qb == 64;
     const int grid_b = scan_grid_x(tiles_b, qblocks, q64g3 ? kMaxGridQ64 : kMaxGridX);
     launch_scan_dtype(dtype, p, a, grid_b, st);
     HCIR_LAUNCH_CHECK();

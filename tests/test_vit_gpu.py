@@ -183,8 +183,8 @@ def test_gemm_many_tiles_per_workgroup(L, m, n, k, ln, epi):
     """Several 256 x 256 tiles per workgroup (23-32 at the benchmark's batch), ragged last row of tiles, plain and
     LayerNorm-folded fp16 epilogues.  (1) fp32 reference; (2) a row range of the same problem small enough for the
     128 x 192 kernel (same k order, same epilogue arithmetic) must give the SAME BITS; (3) run-to-run bit-identity.
-    Also the gate of the overlapped-boundary experiment (-DHCIR_GEMM_OVERLAP: tile t finished inside the first k-step
-    of tile t+1, gemm_f16_ov_kernel) - it has to pass this test unchanged."""
+    Also the gate for any change of the tile boundary (such as finishing tile t inside the first k-step of tile t+1):
+    it has to pass this test unchanged."""
     g = torch.Generator(device="cuda").manual_seed(m + n + k)
     a = (torch.randn(m, k, device="cuda", generator=g) * 0.5 + torch.randn(m, 1, device="cuda", generator=g)).half()
     w = (torch.randn(n, k, device="cuda", generator=g) * k ** -0.5).half()

@@ -1,5 +1,5 @@
-"""Summarise `rocprofv3 --pmc <SQ counters>` passes over the training step (tools/bench_train.py) into a per-kernel
-table: matrix-pipe busy, LDS busy, bank conflicts, wait fractions.
+"""Summarise `rocprofv3 --pmc <SQ counters>` passes over one workload (tools/bench_train.py, bench.py --no-extras, ...)
+into a per-kernel table: matrix-pipe busy, LDS busy, bank conflicts, wait fractions.
 
 usage: python3 tools/pmc_sq.py <out.json> <pass_dir> [<pass_dir> ...]   |   <out.json> <earlier_summary.json>
 Each pass directory holds one rocprofv3 run (counter_collection.csv [+ kernel_trace.csv]).  SQ_* cycle counters are
@@ -9,10 +9,10 @@ import collections, csv, glob, json, os, re, sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hair-centric-image-retrieval_amd"))
 
-KERNELS = [("gemm_f16_big_kernel<0", r"gemm_f16_big_kernel<0,"), ("gemm_f16_big_kernel<1", r"gemm_f16_big_kernel<1,"),
-           ("gemm_f16_big_kernel<10", r"gemm_f16_big_kernel<10,"),
-           ("gemm_f16_big_kernel<6", r"gemm_f16_big_kernel<6,"), ("gemm_f16_tn_kernel", r"gemm_f16_tn_kernel"),
-           ("attn_bwd2_kernel", r"attn_bwd2_kernel"), ("attn_bwd_kernel", r"attn_bwd_kernel<"),
+# gemm_f16_big_kernel<EPI>; traces recorded before the MFMA-shape parameter went name it gemm_f16_big_kernel<EPI, true>
+KERNELS = [*((f"gemm_f16_big_kernel<{e}", rf"gemm_f16_big_kernel<{e}[,>]") for e in (0, 1, 6, 7, 8, 9, 10)),
+           ("gemm_f16_tn_kernel", r"gemm_f16_tn_kernel"),
+           ("attn_bwd2_kernel", r"attn_bwd2_kernel"), ("attn_bwd_kernel", r"attn_bwd_kernel[<(]"),
            ("attn_fwd_kernel", r"attn_fwd_kernel"), ("layernorm_bwd_kernel", r"layernorm_bwd_kernel"),
            ("gelu_bwd_colsum_kernel", r"gelu_bwd_colsum_kernel")]
 
@@ -80,9 +80,10 @@ def main():
         if g("SQ_LDS_IDX_ACTIVE") and g("SQ_LDS_BANK_CONFLICT") is not None:
             row["bank_conflict_frac_of_lds_cycles"] = round(g("SQ_LDS_BANK_CONFLICT") / g("SQ_LDS_IDX_ACTIVE"), 4)
         table[k] = row
-    doc = {"note": "rocprofv3 --pmc passes (<= 4 SQ counters each, --kernel-trace only) over tools/bench_train.py; per "
-                   "kernel the average over the larger half of its launches; fractions are ratios of counters of ONE pass",
-           "kernels": table}
+    doc = {"note": "rocprofv3 --pmc passes (<= 4 SQ counters each, --kernel-trace only) over the workload the passes "
+                   "were recorded on (see 'passes'); per kernel the average over the larger half of its launches; "
+                   "fractions are ratios of counters of ONE pass",
+           "passes": prior.get("passes") if prior else dirs, "kernels": table}
     try:
         from hcir._lib import build_id
         doc["src_hash"] = prior["src_hash"] if prior else build_id()
