@@ -94,6 +94,13 @@ SIGNATURES = {
     "hcir_confusion_matrix": (c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "hcir_retrieval_metrics": (c_int, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                        c_vp]),
+    "hcir_softmax_xent_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "hcir_softmax_xent_fwd_bwd": (c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_sz, c_vp]),
+    "hcir_linear_argmax": (c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "hcir_class_moments_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "hcir_class_sums_f64": (c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_class_scatter_f64": (c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "hcir_positive_transform": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "hcir_bn1d_fwd": (c_int, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_f32, c_f32, c_int, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_i64, c_vp, c_i64, c_vp]),

@@ -1,5 +1,5 @@
-"""hcir.classification_engine — Classifier.knn_eval on the MI355X hot path
-(HP/src/classification_engine.py:18-98).
+"""hcir.classification_engine — Classifier.knn_eval, linear_probe_eval and compute_intra_inter_variance on the
+MI355X hot path (HP/src/classification_engine.py:18-127, 206-281).
 
 Differences from the reference, all behind the same interface:
   * embeddings stay on the device (no per-batch .cpu(), :51,63); F.normalize is hcir_l2_normalize;
@@ -10,8 +10,12 @@ Differences from the reference, all behind the same interface:
     KNeighborsClassifier.predict) of ALL k of the sweep is one hcir_knn_vote launch over that list, and
     accuracy / confusion-matrix counts come from hcir_confusion_matrix: labels and predictions stay in HBM;
     only the per-k report (text) is assembled on the host.
-linear_probe_eval / save_umap / compute_intra_inter_variance are sklearn/umap analytics outside
-the hot path and raise NotImplementedError.
+  * linear_probe_eval (:101-127) fits hcir.linear_probe.LogisticRegression on the embeddings where they lie: the
+    softmax-regression loss and gradient of every L-BFGS evaluation is one hcir_softmax_xent_fwd_bwd pass over the
+    [N, D] features, predict is hcir_linear_argmax; the reference copies the features to the host for sklearn;
+  * compute_intra_inter_variance (:206-281) takes the class counts, means and scatter from two fp64 device passes
+    (hcir_class_sums_f64, hcir_class_scatter_f64) instead of a numpy loop over the classes.
+save_umap is umap-learn analytics outside the hot path and raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -136,11 +140,59 @@ class Classifier:
             print(f"Appended results for k={k}")
         print(f"\nAll results saved in: {file_path}")
 
-    def linear_probe_eval(self, *a, **k):
-        raise NotImplementedError("linear probe is sklearn LogisticRegression analytics, outside the hot path")
+    def linear_probe_eval(self):
+        print(f"Evaluating with Linear Probe on {self.device}")
+        self.extracting_features()
+        file_path = os.path.join(self.save_path, "linear_probe_results.txt")
+        from . import metrics
+        from .linear_probe import LogisticRegression
+        dev = self.training_features.device
+        clf = LogisticRegression(max_iter=5000, solver="lbfgs", multi_class="multinomial")
+        clf.fit(self.training_features, self.training_labels.to(dev))
+        pred = clf.predict(self.testing_features)
+        # accuracy_score from the device counts: every label seen on either side gets a compact index
+        yt = self.testing_labels.to(dev)
+        classes = torch.unique(torch.cat([yt, pred]))
+        cm = metrics.confusion_matrix(torch.searchsorted(classes, yt).contiguous(),
+                                      torch.searchsorted(classes, pred).contiguous(), int(classes.numel()))
+        acc = float(cm.diagonal().sum().item()) / max(int(yt.numel()), 1)
+        self.linear_probe_predictions = pred.cpu().numpy()
+        report, cm = _report(self.testing_labels.numpy(), self.linear_probe_predictions)
+        with open(file_path, "w") as f:
+            f.write("Linear Probe Evaluation Results\n")
+            f.write("=" * 50 + "\n\n")
+            f.write(f"Accuracy: {acc:.4f}\n\n")
+            f.write("Classification Report:\n")
+            f.write(report + "\n\n")
+            f.write("Confusion Matrix:\n")
+            f.write(np.array2string(cm) + "\n\n")
+            f.write("=" * 50 + "\n\n")
+        print(f"Linear probe results saved in: {file_path}")
 
     def save_umap(self, *a, **k):
         raise NotImplementedError("UMAP visualisation is outside the hot path")
 
-    def compute_intra_inter_variance(self, *a, **k):
-        raise NotImplementedError("intra/inter-class variance analytics are outside the hot path")
+    def compute_intra_inter_variance(self, split="test"):
+        print(f"Computing intra/inter-class variance on {split} set")
+        if split not in ("train", "test", "both"):
+            raise ValueError("split must be 'train' or 'test'")
+        self.extracting_features()
+        from .linear_probe import class_variance
+        if split == "train":
+            features, labels = self.training_features, self.training_labels
+        elif split == "test":
+            features, labels = self.testing_features, self.testing_labels
+        else:
+            features = torch.cat([self.training_features, self.testing_features], dim=0)
+            labels = torch.cat([self.training_labels, self.testing_labels], dim=0)
+        intra, inter, ratio = class_variance(features.contiguous(), labels.to(features.device).to(torch.int64))
+        results = {"intra_class_variance": intra, "inter_class_variance": inter, "variance_ratio": ratio}
+        save_file = os.path.join(self.save_path, f"variance_analysis_{split}.txt")
+        with open(save_file, "w") as f:
+            f.write("Embedding Geometry Analysis\n")
+            f.write("=" * 50 + "\n")
+            for k, v in results.items():
+                f.write(f"{k}: {v:.6f}\n")
+        print(f"Variance analysis saved to: {save_file}")
+        print(results)
+        return results

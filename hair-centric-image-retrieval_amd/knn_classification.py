@@ -5,7 +5,9 @@ MI355X hot path.  Same flags (HP/knn_classification.py:47-67) and the same outpu
 
 Modes on the hot path: SHAM (resnet18 / resnet50 / vit_b_16), simclr, mae.  The other --mode
 values name SSL baselines that are out of scope: accepted by argparse,
-rejected with a clear error.  --eval_type knn is built; the other eval types are host analytics.
+rejected with a clear error.  --eval_type knn, linear_prob (`linear_probe_results.txt`: the L-BFGS fit of
+hcir.linear_probe on the device) and inter_intra_distance (`variance_analysis_both.txt`) are built;
+visualization needs umap-learn and raises NotImplementedError.
 """
 import argparse
 import os

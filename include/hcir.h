@@ -308,6 +308,42 @@ int hcir_knn_vote(const int64_t* nbr_idx, int64_t nq, int32_t kmax, int64_t idx_
 int hcir_confusion_matrix(const int64_t* y_true, const int64_t* y_pred, int64_t n, int32_t nclass, int32_t* cm,
                           int32_t* bad, void* stream);
 
+/* Linear probe: LogisticRegression(max_iter=5000, solver="lbfgs", multi_class="multinomial").fit
+ * (HP/src/classification_engine.py:107-110).  One evaluation of the objective the solver minimises, without its
+ * penalty term (the caller adds 0.5 * ||w||^2 and + w):
+ *   z = x w^T + b,   *loss = sum_i ( logsumexp_c z_ic - z_i,labels[i] )   (fp64),
+ *   gw [c][d] = (P - Y)^T x,   gb [c] = colsum(P - Y),   P = softmax(z) (never written to memory).
+ * x [n][ldx] fp32 (16-byte aligned, ldx % 4 == 0), labels [n] in [0, c), w [c][d], b [c]; d % 8 == 0,
+ * 2 <= c <= 1024 (larger: HCIR_ERR_UNSUPPORTED).  A class without rows is legal.  *bad (device int, zeroed by the
+ * caller) is set when a label is out of range; such a row is left out.  Operands stay fp32
+ * (v_mfma_f32_32x32x2_f32); per-workgroup partials are added in a fixed order, so two calls with the same inputs
+ * return the same bits.  workspace: hcir_softmax_xent_workspace_bytes (HOST; 0 for a shape the kernel rejects). */
+size_t hcir_softmax_xent_workspace_bytes(int64_t n, int32_t d, int32_t c);
+int hcir_softmax_xent_fwd_bwd(const float* x, int64_t n, int32_t d, int64_t ldx, const int64_t* labels,
+                              const float* w, const float* b, int32_t c, double* loss, float* gw, float* gb,
+                              int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* LogisticRegression.predict / decision_function (HP/src/classification_engine.py:111): pred[i] = arg-max over c of
+ * z_ic = <x_i, w_c> + b_c, the FIRST maximum on exact ties (np.argmax); logits [n][c] fp32 is optional (NULL).
+ * Same shape limits as hcir_softmax_xent_fwd_bwd. */
+int hcir_linear_argmax(const float* x, int64_t n, int32_t d, int64_t ldx, const float* w, const float* b, int32_t c,
+                       int64_t* pred, float* logits, void* stream);
+
+/* Intra/inter-class variance (HP/src/classification_engine.py:241-262), two passes with fp64 accumulators.
+ * Pass 1, hcir_class_sums_f64: counts [c] = rows of each class, sums [c][d] = their column sums; the class means
+ * (:251) and the global mean (:244) follow from them.  Pass 2, hcir_class_scatter_f64: scatter [c] =
+ * sum over the rows of class c of ||x_i - means[c]||^2 (:254) with means [c][d] read in fp64.  (The one-pass form
+ * sum ||x||^2 / n - ||m||^2 cancels on unit-norm rows.)  Every sum runs in a fixed order.  labels [n] in [0, c);
+ * *bad (device int, zeroed by the caller) is set otherwise and the row is left out.  One workspace size serves both
+ * passes: hcir_class_moments_workspace_bytes (HOST). */
+size_t hcir_class_moments_workspace_bytes(int64_t n, int32_t d, int32_t c);
+int hcir_class_sums_f64(const float* x, int64_t n, int32_t d, int64_t ldx, const int64_t* labels, int32_t c,
+                        int64_t* counts, double* sums, int32_t* bad, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int hcir_class_scatter_f64(const float* x, int64_t n, int32_t d, int64_t ldx, const int64_t* labels, int32_t c,
+                           const double* means, double* scatter, int32_t* bad, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Recall@K and AP@K of a retrieved list against per-query ground-truth ids
  * (experiments/DualViewHair/scripts/quantitative_eval.py:194-209):
  *   hit[s][q] = any ground-truth id among the first ks[s] retrieved ids
