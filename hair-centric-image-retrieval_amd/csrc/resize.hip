@@ -24,10 +24,26 @@ inline double bicubic_filter(double x) {  // Resample.c, a = -0.5
   return 0.0;
 }
 
-inline int ksize_of(int32_t in_size, int32_t out_size) {
+inline double bilinear_filter(double x) {  // Resample.c
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return 1.0 - x;
+  return 0.0;
+}
+
+struct Filter {  // Resample.c struct filter
+  double (*filter)(double);
+  double support;
+};
+
+inline const Filter* filter_of(int32_t id) {
+  static const Filter bilinear{bilinear_filter, 1.0}, bicubic{bicubic_filter, 2.0};
+  return id == HCIR_FILTER_BILINEAR ? &bilinear : (id == HCIR_FILTER_BICUBIC ? &bicubic : nullptr);
+}
+
+inline int ksize_of(const Filter& f, int32_t in_size, int32_t out_size) {
   double filterscale = (double)in_size / out_size;
   if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 2.0 * filterscale;
+  const double support = f.support * filterscale;
   return (int)ceil(support) * 2 + 1;
 }
 
@@ -139,23 +155,16 @@ int64_t max_rows(const hcir_resize_job* jobs, int64_t b) {
   return m;
 }
 
-}  // namespace
-
-extern "C" int32_t hcir_resize_bicubic_ksize(int32_t in_size, int32_t out_size) {
-  if (in_size <= 0 || out_size <= 0) return 0;
-  return ksize_of(in_size, out_size);
-}
-
 // Pillow's precompute_coeffs (box = the whole axis) followed by normalize_coeffs_8bpc.  The statements follow
 // Resample.c one for one: the rounding of every double operation is what makes the tables equal.
-extern "C" int hcir_resize_bicubic_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
+int coeffs_of(const Filter& f, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
   if (in_size <= 0 || out_size <= 0 || !bounds || !kk) return HCIR_ERR_INVALID;
   const int inSize = in_size, outSize = out_size;
   const double in0 = 0.0, in1 = (double)(float)in_size;  // the box travels as float through Image.resize
   double support, scale, filterscale;
   filterscale = scale = (double)(in1 - in0) / outSize;
   if (filterscale < 1.0) filterscale = 1.0;
-  support = 2.0 * filterscale;
+  support = f.support * filterscale;
   const int ksize = (int)ceil(support) * 2 + 1;
   std::vector<double> kbuf((size_t)ksize);
   for (int xx = 0; xx < outSize; xx++) {
@@ -170,7 +179,7 @@ extern "C" int hcir_resize_bicubic_coeffs(int32_t in_size, int32_t out_size, int
     double* k = kbuf.data();
     int x;
     for (x = 0; x < xmax; x++) {
-      const double w = bicubic_filter((x + xmin - center + 0.5) * ss);
+      const double w = f.filter((x + xmin - center + 0.5) * ss);
       k[x] = w;
       ww += w;
     }
@@ -184,6 +193,27 @@ extern "C" int hcir_resize_bicubic_coeffs(int32_t in_size, int32_t out_size, int
       ko[x] = k[x] < 0 ? (int32_t)(-0.5 + k[x] * (1 << kPrecisionBits)) : (int32_t)(0.5 + k[x] * (1 << kPrecisionBits));
   }
   return HCIR_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t hcir_resize_ksize(int32_t filter, int32_t in_size, int32_t out_size) {
+  const Filter* f = filter_of(filter);
+  if (!f || in_size <= 0 || out_size <= 0) return 0;
+  return ksize_of(*f, in_size, out_size);
+}
+
+extern "C" int hcir_resize_coeffs(int32_t filter, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
+  const Filter* f = filter_of(filter);
+  return f ? coeffs_of(*f, in_size, out_size, bounds, kk) : HCIR_ERR_UNSUPPORTED;
+}
+
+extern "C" int32_t hcir_resize_bicubic_ksize(int32_t in_size, int32_t out_size) {
+  return hcir_resize_ksize(HCIR_FILTER_BICUBIC, in_size, out_size);
+}
+
+extern "C" int hcir_resize_bicubic_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk) {
+  return hcir_resize_coeffs(HCIR_FILTER_BICUBIC, in_size, out_size, bounds, kk);
 }
 
 extern "C" size_t hcir_resize_crop_workspace_bytes(const hcir_resize_job* jobs_host, int64_t b, int32_t win_h, int32_t win_w) {

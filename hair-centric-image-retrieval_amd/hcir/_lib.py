@@ -120,6 +120,10 @@ SIGNATURES = {
     "hcir_resize_bicubic_coeffs": (c_int, [c_i32, c_i32, c_vp, c_vp]),
     "hcir_resize_crop_workspace_bytes": (c_sz, [c_vp, c_i64, c_i32, c_i32]),
     "hcir_resize_crop_bicubic_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_resize_ksize": (c_i32, [c_i32, c_i32, c_i32]),
+    "hcir_resize_coeffs": (c_int, [c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "hcir_view_blur_weights": (c_int, [c_f32, c_vp, c_vp, c_vp]),
+    "hcir_simclr_view_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -13,6 +13,10 @@ with `hcir_png_decode_window_u8` (the reference's `*_hair.png` crops, `HP/data/d
 `hcir_jpeg_decode_window_u8` (its `*_full_face` JPEG lists) -> `hcir_knn_transform_u8`.  Files outside both device
 subsets (progressive JPEG, 16-bit or interlaced PNG ...) are decoded by the worker with PIL, as the reference does,
 and ride along as RGB8 windows.
+
+`collate_train_views` is the training side of the same contract: the items of an `EncodedDataset` become the two
+SimCLR views the pretrain step consumes (`{"anchor", "pos1"}`, HP/utils/dataloader.py:36-38), with the whole-image
+decode, the crops and the augmentations on the device (`hcir.views`).
 """
 from __future__ import annotations
 
@@ -60,11 +64,13 @@ class CustomDataset(Dataset):
 
 
 class EncodedDataset(Dataset):
-    """Same CSV contract as CustomDataset; an item is (file bytes as a uint8 tensor, label)."""
+    """Same CSV contract as CustomDataset; an item is (file bytes as a uint8 tensor, label), with return_names
+    (file bytes, label, file name) so that a collate function can name a corrupt file."""
 
-    def __init__(self, annotations_file, img_dir):
+    def __init__(self, annotations_file, img_dir, return_names: bool = False):
         self.records = _read_annotations(annotations_file)
         self.root = Path(img_dir)
+        self.return_names = bool(return_names)
 
     def __len__(self) -> int:
         return len(self.records)
@@ -73,7 +79,8 @@ class EncodedDataset(Dataset):
         import numpy as np
         import torch
         name, label = self.records[index]
-        return torch.from_numpy(np.fromfile(self.root / name, dtype=np.uint8)), label
+        data = torch.from_numpy(np.fromfile(self.root / name, dtype=np.uint8))
+        return (data, label, name) if self.return_names else (data, label)
 
 
 class EncodedBatch:
@@ -136,3 +143,106 @@ def collate_encoded(items, size: int = 224, verify_crc: bool = True):
         if len(staged.rejected) < len(sub):
             parts.append((kind, staged, sel))
     return EncodedBatch(parts, host, size, len(files)), torch.as_tensor([int(it[1]) for it in items])
+
+
+class TrainViewBatch:
+    """What collate_train_views hands to the trainer: per (codec, height, width) group one staging blob with the batch
+    positions it fills, the host-decoded images of the files neither device decoder takes, and the labels."""
+
+    def __init__(self, groups, host_images, names, labels):
+        self.groups, self.host_images, self.names, self.labels = groups, host_images, names, labels
+        self.n = len(names)
+
+    def images(self, device):
+        """-> (list of n RGB8 [h, w, 3] tensors on `device`, check): every staged file decoded whole on the device
+        (one H2D copy per blob).  check() reads the decoders' status back (one copy for the batch) and raises
+        HcirError naming the corrupt files; call it after enqueuing the work that follows."""
+        import torch
+        from . import jpeg, png
+        from ._lib import HcirError
+        images = [None] * self.n
+        statuses, where = [], []
+        for kind, (h, w), staged, idx, keep in self.groups:
+            mod = png if kind == "png" else jpeg
+            whole, st = mod.decode_windows(staged.to(device), (h, w), _skip_rejected_check=True, return_status=True)
+            for k in keep:   # a rejected file's position in the blob is left alone by the device: PIL decoded it
+                images[idx[k]] = whole[k]
+            statuses.append(st if len(keep) == len(idx) else st[keep])
+            where += [idx[k] for k in keep]
+        for i, img in self.host_images.items():
+            images[i] = img.to(device, non_blocking=True)
+        if not statuses:
+            return images, lambda: None
+        st = torch.cat(statuses) if len(statuses) > 1 else statuses[0]
+        st_host = torch.empty(st.shape, dtype=st.dtype, pin_memory=True)
+        st_host.copy_(st, non_blocking=True)
+        read = torch.cuda.Event()
+        read.record(torch.cuda.current_stream(device))
+
+        def check():
+            read.synchronize()
+            bad = [self.names[where[j]] for j in torch.nonzero(st_host).flatten().tolist()]
+            if bad:
+                raise HcirError(f"corrupt image data in files {bad}")
+
+        return images, check
+
+    def views(self, device, generator=None, boxes=None, params=None, defer_check: bool = False, **transform_kwargs):
+        """-> {"anchor", "pos1"} fp32 [n, 3, 224, 224] on `device` (hcir.views.simclr_views over the decoded images).
+        A corrupt stream raises HcirError with the file names: it never yields a black image.  defer_check: return
+        (views, check) without waiting for the device; the caller runs check() before it trusts the batch (a producer
+        on a side stream calls it after it has enqueued the step that runs beside)."""
+        from . import views
+        images, check = self.images(device)
+        out = views.simclr_views(images, generator, boxes, params, **transform_kwargs)
+        if defer_check:
+            return out, check
+        check()
+        return out
+
+
+def collate_train_views(items, verify_crc: bool = True, chunk: int = 256, threads: int = 1, pin: bool = False):
+    """DataLoader collate_fn for EncodedDataset -> TrainViewBatch.  PNG files (the reference's *_hair.png crops) and
+    baseline JPEGs are staged for their device decoders, per (codec, size) group and at most `chunk` files per blob
+    (the decoders' workspace is about 3 bytes per pixel and file); anything else is decoded here with PIL, file by
+    file, as the reference does.  threads / pin: for a caller that collates in the main process (a worker is one
+    process: its own core, and its blobs are pinned by the DataLoader)."""
+    import io
+
+    import numpy as np
+    import torch
+    from . import jpeg, png
+    from ._lib import HcirError
+    from .hair_encoder import _sniff
+    files = [jpeg._as_u8(it[0]) for it in items]
+    names = [str(it[2]) if len(it) > 2 else f"<batch position {i}>" for i, it in enumerate(items)]
+    by_group = {}
+    for i, a in enumerate(files):
+        by_group.setdefault(_sniff(a), []).append(i)
+    groups, host = [], {}
+
+    def host_image(i):
+        try:
+            with Image.open(io.BytesIO(files[i].tobytes())) as im:
+                return torch.from_numpy(np.asarray(im.convert("RGB")).copy())
+        except Exception as e:  # PIL's error for a file it cannot decode, with the file's name
+            raise HcirError(f"cannot decode {names[i]}: {e}") from None
+
+    for (kind, h, w), idx in by_group.items():
+        if kind == "host":
+            for i in idx:
+                host[i] = host_image(i)
+            continue
+        mod = png if kind == "png" else jpeg
+        for s in range(0, len(idx), max(int(chunk), 1)):
+            sel = idx[s:s + max(int(chunk), 1)]
+            sub = [files[i] for i in sel]
+            staged = mod.stage_batch(sub, pin=pin, threads=threads, verify_crc=verify_crc) if kind == "png" else \
+                mod.stage_batch(sub, pin=pin, threads=threads)
+            rejected = set(staged.rejected)   # outside the device subset, or no valid file at all: PIL decides
+            for j in rejected:
+                host[sel[j]] = host_image(sel[j])
+            keep = [j for j in range(len(sel)) if j not in rejected]
+            if keep:
+                groups.append((kind, (h, w), staged, sel, keep))
+    return TrainViewBatch(groups, host, names, torch.as_tensor([int(it[1]) for it in items]))

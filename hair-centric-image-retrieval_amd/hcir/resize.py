@@ -27,21 +27,32 @@ class ResizeJob(ctypes.Structure):
 
 
 JOB_BYTES = ctypes.sizeof(ResizeJob)
-_axis_cache: Dict[Tuple[int, int], Tuple[int, np.ndarray]] = {}
+FILTERS = {"bilinear": 2, "bicubic": 3}   # HCIR_FILTER_*: Pillow's Image.Resampling numbers
+_axis_cache: Dict[Tuple[int, int, str], Tuple[int, np.ndarray]] = {}
 
 
-def axis_table(in_size: int, out_size: int) -> Tuple[int, np.ndarray]:
+def axis_table(in_size: int, out_size: int, filter: str = "bicubic") -> Tuple[int, np.ndarray]:
     """(ksize, [bounds (2 * out) | kk (out * ksize)] int32) of one axis, Pillow's tables (host, cached)."""
-    key = (int(in_size), int(out_size))
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {sorted(FILTERS)}, not {filter!r}")
+    key = (int(in_size), int(out_size), filter)
     hit = _axis_cache.get(key)
     if hit is None:
         L = _lib.lib()
-        ks = L.hcir_resize_bicubic_ksize(*key)
+        i, o = key[:2]
+        if filter == "bicubic":
+            ks = L.hcir_resize_bicubic_ksize(i, o)
+        else:
+            ks = L.hcir_resize_ksize(FILTERS[filter], i, o)
         if ks <= 0:
             raise HcirError(f"bad resize {key}")
-        tab = np.zeros(2 * key[1] + key[1] * ks, np.int32)
-        check(L.hcir_resize_bicubic_coeffs(key[0], key[1], tab.ctypes.data, tab[2 * key[1]:].ctypes.data),
-              "hcir_resize_bicubic_coeffs")
+        tab = np.zeros(2 * o + o * ks, np.int32)
+        if filter == "bicubic":
+            check(L.hcir_resize_bicubic_coeffs(i, o, tab.ctypes.data, tab[2 * o:].ctypes.data),
+                  "hcir_resize_bicubic_coeffs")
+        else:
+            check(L.hcir_resize_coeffs(FILTERS[filter], i, o, tab.ctypes.data, tab[2 * o:].ctypes.data),
+                  "hcir_resize_coeffs")
         hit = _axis_cache[key] = (ks, tab)
     return hit
 
@@ -67,22 +78,25 @@ def center_origin(oh: int, ow: int, win_h: int, win_w: int) -> Tuple[int, int]:
 _ws = {}
 
 
-def resize_center_crop(images: Union[torch.Tensor, Sequence[torch.Tensor]], size: int = 224,
-                       out_sizes: Sequence[Tuple[int, int]] = None) -> torch.Tensor:
-    """Resize(size, bicubic) -> CenterCrop(size) of RGB8 device images: one [b, h, w, 3] tensor or a list of
-    [h, w, 3] tensors of any sizes -> uint8 [b, size, size, 3].  out_sizes: (oh, ow) per image instead of the
-    shorter-side rule.  Asynchronous on the current stream."""
+def _check_images(images, what: str) -> List[torch.Tensor]:
     imgs: List[torch.Tensor] = list(images) if not isinstance(images, torch.Tensor) else list(images.unbind(0))
     if not imgs:
-        raise HcirError("resize_center_crop needs at least one image")
+        raise HcirError(f"{what} needs at least one image")
     dev = imgs[0].device
     for t in imgs:
         if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 or t.size(2) != 3 or t.stride(2) != 1 or \
                 t.stride(1) != 3 or t.device != dev:
-            raise HcirError("resize_center_crop takes RGB8 [h, w, 3] tensors (pixel-contiguous) on one HIP device "
+            raise HcirError(f"{what} takes RGB8 [h, w, 3] tensors (pixel-contiguous) on one HIP device "
                             "(no CPU fallback)")
+    return imgs
+
+
+def _run_jobs(imgs: List[torch.Tensor], specs, size: int, filter: str) -> torch.Tensor:
+    """One hcir_resize_crop_bicubic_u8 call.  specs: per output window (image index, top, left, h, w of the source
+    box, (oh, ow) it is resized to, (top, left) of the window inside the resized image)."""
     L = _lib.lib()
-    b = len(imgs)
+    dev = imgs[0].device
+    b = len(specs)
     base = min(t.data_ptr() for t in imgs)
     tables: List[np.ndarray] = []
     offs: Dict[Tuple[int, int], int] = {}
@@ -93,7 +107,7 @@ def resize_center_crop(images: Union[torch.Tensor, Sequence[torch.Tensor]], size
         if i == o:
             return -1, 0
         key = (i, o)
-        ks, tab = axis_table(i, o)
+        ks, tab = axis_table(i, o, filter)
         if key not in offs:
             offs[key] = total
             tables.append(tab)
@@ -101,13 +115,12 @@ def resize_center_crop(images: Union[torch.Tensor, Sequence[torch.Tensor]], size
         return offs[key], ks
 
     jobs = (ResizeJob * b)()
-    for n, t in enumerate(imgs):
-        h, w = int(t.size(0)), int(t.size(1))
-        oh, ow = out_sizes[n] if out_sizes is not None else resize_output_size(h, w, size)
-        top, left = center_origin(oh, ow, size, size)
+    for n, (i, top, left, h, w, (oh, ow), (ctop, cleft)) in enumerate(specs):
+        t = imgs[i]
         ch, kh = table_offset(w, ow)
         cv, kv = table_offset(h, oh)
-        jobs[n] = ResizeJob(t.data_ptr() - base, t.stride(0), h, w, oh, ow, top, left, ch, cv, kh, kv)
+        jobs[n] = ResizeJob(t.data_ptr() - base + top * t.stride(0) + left * 3, t.stride(0), h, w, oh, ow, ctop,
+                            cleft, ch, cv, kh, kv)
     host = torch.empty(b * JOB_BYTES + 4 * max(total, 1), dtype=torch.uint8, pin_memory=True)
     ctypes.memmove(host.data_ptr(), ctypes.addressof(jobs), b * JOB_BYTES)
     if total:
@@ -126,3 +139,38 @@ def resize_center_crop(images: Union[torch.Tensor, Sequence[torch.Tensor]], size
           "hcir_resize_crop_bicubic_u8")
     out._hcir_keepalive = (blob, host, imgs)  # the kernels read these after this call returns
     return out
+
+
+def resize_center_crop(images: Union[torch.Tensor, Sequence[torch.Tensor]], size: int = 224,
+                       out_sizes: Sequence[Tuple[int, int]] = None) -> torch.Tensor:
+    """Resize(size, bicubic) -> CenterCrop(size) of RGB8 device images: one [b, h, w, 3] tensor or a list of
+    [h, w, 3] tensors of any sizes -> uint8 [b, size, size, 3].  out_sizes: (oh, ow) per image instead of the
+    shorter-side rule.  Asynchronous on the current stream."""
+    imgs = _check_images(images, "resize_center_crop")
+    specs = []
+    for n, t in enumerate(imgs):
+        h, w = int(t.size(0)), int(t.size(1))
+        oh, ow = out_sizes[n] if out_sizes is not None else resize_output_size(h, w, size)
+        specs.append((n, 0, 0, h, w, (oh, ow), center_origin(oh, ow, size, size)))
+    return _run_jobs(imgs, specs, size, "bicubic")
+
+
+def resize_boxes(images: Union[torch.Tensor, Sequence[torch.Tensor]], boxes, size: int = 224,
+                 filter: str = "bilinear", image_index: Sequence[int] = None) -> torch.Tensor:
+    """`img.crop(box).resize((size, size), filter)` of RGB8 device images, Pillow's bytes: boxes [n, 4] of
+    (top, left, height, width), box k taken from image image_index[k] (default: k) -> uint8 [n, size, size, 3].
+    The device resampler runs each box as a job whose source is the box.  Asynchronous on the current stream."""
+    imgs = _check_images(images, "resize_boxes")
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    index = list(range(len(boxes))) if image_index is None else [int(i) for i in image_index]
+    if len(index) != len(boxes) or not len(boxes):
+        raise ValueError("resize_boxes needs one image index per box and at least one box")
+    specs = []
+    for i, (top, left, h, w) in zip(index, boxes.tolist()):
+        if not 0 <= i < len(imgs):
+            raise ValueError(f"image index {i} outside the {len(imgs)} images")
+        ih, iw = int(imgs[i].size(0)), int(imgs[i].size(1))
+        if h <= 0 or w <= 0 or top < 0 or left < 0 or top + h > ih or left + w > iw:
+            raise ValueError(f"box (top {top}, left {left}, {h} x {w}) leaves its {ih} x {iw} image")
+        specs.append((i, top, left, h, w, (size, size), (0, 0)))
+    return _run_jobs(imgs, specs, size, filter)

@@ -658,6 +658,57 @@ int hcir_resize_crop_bicubic_u8(const uint8_t* src, const int32_t* coef, const h
                                 const hcir_resize_job* jobs_host, int64_t b, int32_t win_h, int32_t win_w,
                                 uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* HOST.  The same tables for a named Pillow filter (Image.Resampling numbering).  HCIR_FILTER_BICUBIC returns exactly
+ * what hcir_resize_bicubic_ksize / _coeffs return; HCIR_FILTER_BILINEAR is the triangle filter (support 1.0) of
+ * Image.resize(size, BILINEAR).  Any other filter: 0 / HCIR_ERR_UNSUPPORTED.  The device resampler above takes its
+ * tables, tap counts, source offset and pitch per job, so it runs either filter, and a crop box followed by a resize
+ * (img.crop(box).resize(size)) is a job whose source is the box. */
+#define HCIR_FILTER_BILINEAR 2
+#define HCIR_FILTER_BICUBIC 3
+int32_t hcir_resize_ksize(int32_t filter, int32_t in_size, int32_t out_size);
+int hcir_resize_coeffs(int32_t filter, int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk);
+
+/* ------------------------------------------------------------------ *
+ * SimCLR training views on the device: the input of the pretrain step (batch["anchor"], batch["pos1"]).
+ *   transform = SimCLRTransform(input_size=224)                        HP/mainpretrain.py:130
+ *   images = self.transform(image); {"anchor": images[0], "pos1": images[1]}   HP/utils/dataloader.py:36-38
+ * lightly's SimCLRTransform is, on a PIL image: RandomResizedCrop(224, scale=(0.08, 1)) (bilinear) ->
+ * RandomHorizontalFlip -> RandomApply(ColorJitter(0.8, 0.8, 0.8, 0.2), p=0.8) -> RandomGrayscale(0.2) ->
+ * GaussianBlur(sigmas=(0.1, 2), prob=0.5) -> ToTensor -> Normalize(ImageNet); every op is executed by Pillow
+ * (third-party; Pillow 12.2 libImaging Blend.c, Convert.c, BoxBlur.c, Resample.c).
+ * The crop + resize is a job of hcir_resize_crop_bicubic_u8 with bilinear tables; everything after it is
+ * hcir_simclr_view_f32: one workgroup per view, the 224 x 224 RGB8 image resident in LDS (3 planes of 224 rows with
+ * a 228-byte pitch = 153 216 of the CU's 163 840 bytes) from the load to the fp32 store.  Bytes equal Pillow's after
+ * every op, and the fp32 output equals ToTensor + Normalize of them bit for bit.  All random draws are the caller's.
+ * ------------------------------------------------------------------ */
+#define HCIR_VIEW_SIZE 224
+#define HCIR_VIEW_BRIGHTNESS 0 /* entries of hcir_view_params.order */
+#define HCIR_VIEW_CONTRAST 1
+#define HCIR_VIEW_SATURATION 2
+#define HCIR_VIEW_HUE 3
+
+typedef struct hcir_view_params { /* one view */
+  int32_t flip;                   /* 0 / 1: horizontal flip                                                     */
+  int32_t jitter;                 /* 0 / 1: apply the four colour ops below                                     */
+  int32_t order[4];               /* a permutation of HCIR_VIEW_BRIGHTNESS .. HCIR_VIEW_HUE: the order they run */
+  float brightness, contrast, saturation; /* enhancement factors, finite and >= 0                               */
+  float hue;                      /* in [-0.5, 0.5]                                                             */
+  int32_t gray;                   /* 0 / 1: every channel <- L                                                  */
+  int32_t blur;                   /* 0 / 1: Gaussian blur by three box passes per axis with ...                 */
+  int32_t blur_r;                 /* ... whole pixels each side (0 or 1: sigma <= 2.3),                         */
+  uint32_t blur_ww, blur_fw;      /* ... and these 24-bit weights (hcir_view_blur_weights)                      */
+  float sigma;                    /* the sigma they derive from (kept for the caller; not read by the kernel)   */
+} hcir_view_params;
+
+/* HOST.  Pillow's box-blur weights for ImageFilter.GaussianBlur(radius = sigma).  sigma must be finite and > 0;
+ * HCIR_ERR_UNSUPPORTED when it needs more than one whole pixel each side (sigma > 2.3). */
+int hcir_view_blur_weights(float sigma, int32_t* r, uint32_t* ww, uint32_t* fw);
+/* crops: DEVICE uint8 [n][224][224][3]; params_dev: DEVICE, params_host: the same records on the host (checked here:
+ * HCIR_ERR_INVALID for a flag that is not 0 / 1, an order that is no permutation, a factor out of range, blur weights
+ * that do not sum to at most 2^24).  mean3 / std3: HOST.  out: DEVICE fp32 [n][3][224][224]. */
+int hcir_simclr_view_f32(const uint8_t* crops, const hcir_view_params* params_dev, const hcir_view_params* params_host,
+                         int64_t n, const float* mean3, const float* std3, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
