@@ -24,8 +24,10 @@
 //            the floor are appended to per-query candidate buffers; a device flag gates the
 //            list-keeping scan as fallback if a buffer overflows.
 #include "sim_core.h"
+#include "sim_plan.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 constexpr int kScanAux = 2;  // cache policy of the once-read gallery stream: 2 = nt (non-temporal), +5 % GB/s
 
@@ -160,7 +162,7 @@ struct ScanArgs {
 // batch gains (64-query call 333 -> 340 us); running a 64-query prefix as two 32-query blocks of this kernel was a
 // wash (prefix 52 -> 49 us).  The streaming launches behind a floor keep the lean kernel.
 // (KP = 16, one query tile x two wave columns, two row groups: 24 KB stages -> THREE workgroups per CU; the 64-query
-// geometry of the streaming launches, see make_plan)
+// geometry of the streaming launches, see kSimGeom in sim_plan.h)
 template <typename T, int KP, int QT, int WQ, int WGG, bool GLDS, bool CAND = false, bool BATCH = false>
 __global__ __launch_bounds__(256, ((KP == 16 && QT == 1 && WQ == 2 && WGG == 2 && GLDS && !BATCH)
                                        ? 3
@@ -1423,74 +1425,9 @@ __global__ void pass_copy_kernel(const float* __restrict__ pv, const int* __rest
 }
 
 // ----- host-side planning ---------------------------------------------------
-struct Plan {
-  int kp;          // list capacity per pass (16 or 64)
-  int qb;          // queries per workgroup (32, 64, 128)
-  int gm;          // gallery rows per workgroup tile
-  int64_t prefix;  // rows of the prefix scan (== ng: single scan)
-  int grid_main;   // workgroups (x) of the widest scan
-  int npass;       // passes for k > 64
-};
-
-constexpr int kMaxGridX = 512;  // 2 workgroups per CU; also <= 576 lists per merge pass
-// 33..64 queries with k <= 16 run as <one query tile x two wave columns> workgroups on 128-row tiles: 24 KB stages,
-// THREE workgroups per CU for the streaming launches (768 workgroups; the floorless launches get the batch-insertion
-// kernel of the one-query-tile geometry, two per CU) instead of two <two query tiles> workgroups with 40 KB stages.
-// Same-box A/B, 1 M x 768 fp16, 64 queries (tools/ab_sim.py): 318 -> 307 us (the prefix launch 52 -> 38 us; the main
-// scan unchanged at 5.7 TB/s).
-constexpr int kMaxGridQ64 = 768;
-constexpr int kMaxParts = kMaxGridQ64 > kMaxGridX ? kMaxGridQ64 : kMaxGridX;
-
-// Workgroups along the gallery for `qblocks` query blocks.  Every query block scans every gallery tile; the
-// grid is sized so that ALL (tile run, query block) workgroups are resident at once (512 slots) and the blocks
-// of one tile run sit on the same XCD (linear id = x + grid_x * y, grid_x a multiple of 8): they stream the
-// same tiles in step and all but the first read them from that XCD's L2.  (With 512 workgroups per query
-// block the blocks ran one after the other and the gallery came from HBM once per block.)
-inline int scan_grid_x(int64_t tiles, int64_t qblocks, int max_wg = kMaxGridX) {
-  int64_t cap = max_wg / (qblocks < 1 ? 1 : qblocks);
-  cap = cap < 8 ? 8 : (cap & ~int64_t(7));
-  return (int)(tiles < cap ? tiles : cap);
-}
-
-// Prefix launches of 16-entry lists with 33..kPrefixQb32MaxQ queries run as 32-query blocks (the batch-insertion
-// kernel; the prefix is latency- and insertion-bound, not bandwidth-bound, and the blocks of a tile share its L2 lines).
-Plan make_plan(int64_t nq, int64_t ng, int k) {
-  Plan p;
-  p.kp = k <= 16 ? 16 : (k <= 32 ? 32 : 64);
-  p.npass = (k + 63) / 64;
-  if (p.kp == 64) {
-    p.qb = 32;
-  } else {
-    p.qb = nq <= 32 ? 32 : (nq <= 64 ? 64 : 128);
-  }
-  p.gm = p.qb == 128 ? 128 : 256;
-  if (p.kp == 16 && p.qb == 64) p.gm = 128;   // <QT 1, WQ 2, WGG 2>: 128-row tiles, 3 workgroups per CU
-  const int64_t tiles = hcir_cdiv(ng, p.gm);
-  p.grid_main = (int)(tiles < kMaxGridX ? tiles : kMaxGridX);
-  // prefix: ~1/16 of the gallery, at least 64 rows per list-k, in whole tiles
-  p.prefix = ng;
-  if (p.npass == 1 && ng >= 32768) {
-    int64_t s = ng / 16;
-    // 64-entry lists: a workgroup's fixed cost (filling the lists from its first tile, then the in-workgroup
-    // merge: ~85 us) dwarfs its streaming time, so the prefix is ONE round of at most 64 workgroups x 1 tile;
-    // 16 K rows still put the floor within ~k ln(N/16K) insertions per query of the final k-th score
-    const int64_t lo = 8192, hi = p.kp == 64 ? 16384 : 131072;
-    s = s < lo ? lo : (s > hi ? hi : s);
-    s = hcir_cdiv(s, p.gm) * p.gm;
-    if (s < ng) p.prefix = s;
-  }
-  return p;
-}
-
-// candidates per query the big-tile scan can hold: one-element lists of the final merge (16 per lane), next
-// to the prefix list
-constexpr int kCandLPL = 16;
-constexpr int kCandCap = 64 * kCandLPL - 64;  // 960
-// candidate-append scans of <= 128 queries with 16 < k <= 64: the floor is the minimum of ceil(k/16) group floors
-// (weaker than one k-th score), so more rows clear it
-constexpr int kSelLPLBig = 48;
-constexpr int kCandCapBig = 64 * kSelLPLBig - 64;  // 3008
-constexpr int kMaxFloorGroups = 4;
+// Which flow a call takes, with which kernel geometry, prefix, grids and workspace layout, is decided once by
+// sim_topk_plan (sim_plan.h: plain C++, pinned on the CPU by tests/test_sim_plan_host.py).  The code below fills
+// argument structs from that plan and launches: one function per flow, no state passed between them.
 
 // the merge of up to `nlists` (+ the extra) sorted 32-bit-index lists: four waves per query for kout <= 16 with one
 // group, the one-wave kernel otherwise
@@ -1515,48 +1452,10 @@ inline void launch_merge32(const MergeArgs<int>& m, hipStream_t st) {
     hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3(merge_grid), dim3(256), 0, st, m);
 }
 
-
-struct Workspace {
-  float* part_val;
-  int* part_idx;
-  float* pre_val;  // [nq][kp] prefix / previous-pass result
-  int* pre_idx;
-  float* floor_val;  // [nq]
-  float* ceil_val;   // [nq]
-  int* ceil_idx;     // [nq]
-  float* cand_val;   // [kCandCap][nq]  big-tile scan: candidates behind the prefix floor
-  int* cand_idx;     // [kCandCap][nq]
-  int* cand_cnt;     // [nq] + 1 overflow flag behind it
-  size_t bytes;
-};
-
-Workspace carve(void* base, int64_t nq, int k, const Plan& p) {
-  Workspace w;
-  char* c = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    char* r = c ? c + off : nullptr;
-    off += (n + 255) & ~size_t(255);
-    return r;
-  };
-  const size_t part = (size_t)kMaxParts * nq * p.kp;
-  w.part_val = reinterpret_cast<float*>(take(part * 4));
-  w.part_idx = reinterpret_cast<int*>(take(part * 4));
-  w.pre_val = reinterpret_cast<float*>(take((size_t)nq * p.kp * 4));
-  w.pre_idx = reinterpret_cast<int*>(take((size_t)nq * p.kp * 4));
-  w.floor_val = reinterpret_cast<float*>(take((size_t)nq * 4 * kMaxFloorGroups));
-  w.ceil_val = reinterpret_cast<float*>(take((size_t)nq * 4));
-  w.ceil_idx = reinterpret_cast<int*>(take((size_t)nq * 4));
-  const size_t ccap = (k > 16 && k <= 64 && nq <= 128) ? kCandCapBig : kCandCap;
-  w.cand_val = reinterpret_cast<float*>(take(ccap * nq * 4));
-  w.cand_idx = reinterpret_cast<int*>(take(ccap * nq * 4));
-  w.cand_cnt = reinterpret_cast<int*>(take(((size_t)nq + 1) * 4));
-  w.bytes = off;
-  return w;
-}
-
 template <typename T, int KP, int QT, int WQ, int WGG>
-void launch_scan_cfg(const ScanArgs& a, int grid_x, int grid_y, hipStream_t st) {
+void launch_scan_cfg(const ScanArgs& a, int grid_x, hipStream_t st) {
+  static_assert(sim_geom(KP, 32 * QT * WQ).gm == 64 * WGG, "sim_plan.h kSimGeom");
+  const int grid_y = (int)hcir_cdiv(a.nq, 32 * QT * WQ);
   if (QT == 1 && a.d % SimElem<T>::kPerStage == 0 && !a.floor_val)
     hipLaunchKernelGGL((sim_topk_scan<T, KP, QT, WQ, WGG, true, false, (QT == 1)>), dim3(grid_x, grid_y), dim3(256), 0,
                        st, a);
@@ -1567,29 +1466,30 @@ void launch_scan_cfg(const ScanArgs& a, int grid_x, int grid_y, hipStream_t st) 
 }
 
 template <typename T>
-void launch_scan(const Plan& p, const ScanArgs& a, int grid_x, hipStream_t st) {
-  const int grid_y = (int)hcir_cdiv(a.nq, p.qb);
-  if (p.kp == 64) {
-    launch_scan_cfg<T, 64, 1, 1, 4>(a, grid_x, grid_y, st);
-  } else if (p.kp == 32) {
-    if (p.qb == 32)
-      launch_scan_cfg<T, 32, 1, 1, 4>(a, grid_x, grid_y, st);
-    else if (p.qb == 64)
-      launch_scan_cfg<T, 32, 2, 1, 4>(a, grid_x, grid_y, st);
+void launch_scan(int kp, int qb, const ScanArgs& a, int grid_x, hipStream_t st) {
+  if (kp == 64) {
+    launch_scan_cfg<T, 64, 1, 1, 4>(a, grid_x, st);
+  } else if (kp == 32) {
+    if (qb == 32)
+      launch_scan_cfg<T, 32, 1, 1, 4>(a, grid_x, st);
+    else if (qb == 64)
+      launch_scan_cfg<T, 32, 2, 1, 4>(a, grid_x, st);
     else
-      launch_scan_cfg<T, 32, 2, 2, 2>(a, grid_x, grid_y, st);
-  } else if (p.qb == 32) {
-    launch_scan_cfg<T, 16, 1, 1, 4>(a, grid_x, grid_y, st);
-  } else if (p.qb == 64) {
-    launch_scan_cfg<T, 16, 1, 2, 2>(a, grid_x, grid_y, st);
+      launch_scan_cfg<T, 32, 2, 2, 2>(a, grid_x, st);
+  } else if (qb == 32) {
+    launch_scan_cfg<T, 16, 1, 1, 4>(a, grid_x, st);
+  } else if (qb == 64) {
+    launch_scan_cfg<T, 16, 1, 2, 2>(a, grid_x, st);
   } else {
-    launch_scan_cfg<T, 16, 2, 2, 2>(a, grid_x, grid_y, st);
+    launch_scan_cfg<T, 16, 2, 2, 2>(a, grid_x, st);
   }
 }
 
 // candidate-append scan (no lists): geometry by query count only
 template <typename T, int QT, int WQ, int WGG>
-void launch_cand_cfg(const ScanArgs& a, int grid_x, int grid_y, hipStream_t st) {
+void launch_cand_cfg(const ScanArgs& a, int grid_x, hipStream_t st) {
+  static_assert(sim_geom(16, 32 * QT * WQ).gm == 64 * WGG, "sim_plan.h kSimGeom");
+  const int grid_y = (int)hcir_cdiv(a.nq, 32 * QT * WQ);
   if (a.d % SimElem<T>::kPerStage == 0)
     hipLaunchKernelGGL((sim_topk_scan<T, 16, QT, WQ, WGG, true, true>), dim3(grid_x, grid_y), dim3(256), 0, st, a);
   else
@@ -1597,30 +1497,257 @@ void launch_cand_cfg(const ScanArgs& a, int grid_x, int grid_y, hipStream_t st) 
 }
 template <typename T>
 void launch_cand(int qb, const ScanArgs& a, int grid_x, hipStream_t st) {
-  const int grid_y = (int)hcir_cdiv(a.nq, qb);
   if (qb == 32)
-    launch_cand_cfg<T, 1, 1, 4>(a, grid_x, grid_y, st);
+    launch_cand_cfg<T, 1, 1, 4>(a, grid_x, st);
   else if (qb == 64)
-    launch_cand_cfg<T, 1, 2, 2>(a, grid_x, grid_y, st);   // 128-row tiles, three workgroups per CU (C5 at 64 queries: 719 -> 706 us)
+    launch_cand_cfg<T, 1, 2, 2>(a, grid_x, st);
   else
-    launch_cand_cfg<T, 2, 2, 2>(a, grid_x, grid_y, st);
-}
-void launch_cand_dtype(int dtype, int qb, const ScanArgs& a, int grid_x, hipStream_t st) {
-  if (dtype == HCIR_F32)
-    launch_cand<float>(qb, a, grid_x, st);
-  else if (dtype == HCIR_F16)
-    launch_cand<_Float16>(qb, a, grid_x, st);
-  else
-    launch_cand<__bf16>(qb, a, grid_x, st);
+    launch_cand_cfg<T, 2, 2, 2>(a, grid_x, st);
 }
 
-void launch_scan_dtype(int dtype, const Plan& p, const ScanArgs& a, int grid_x, hipStream_t st) {
+// f(T{}) with the element type of `dtype` (validated by the caller)
+template <typename F>
+void with_dtype(int dtype, F&& f) {
   if (dtype == HCIR_F32)
-    launch_scan<float>(p, a, grid_x, st);
+    f(float{});
   else if (dtype == HCIR_F16)
-    launch_scan<_Float16>(p, a, grid_x, st);
+    f(_Float16{});
   else
-    launch_scan<__bf16>(p, a, grid_x, st);
+    f(__bf16{});
+}
+
+struct Call {  // the caller's arguments
+  const void *q, *g;
+  const float *qn, *gn;
+  int64_t nq, ng, idx_base;
+  int d, k, dtype;
+  float* out_val;
+  int64_t* out_idx;
+  hipStream_t st;
+};
+
+// list-keeping scan of rows [row_begin, row_end) by workgroups of `qb` queries
+ScanArgs list_scan_args(const Call& c, const SimWorkspace& w, int qb, int k, int64_t row_begin, int64_t row_end) {
+  ScanArgs a{};
+  a.q = c.q;
+  a.g = c.g;
+  a.qn = c.qn;
+  a.gn = c.gn;
+  a.part_val = w.part_val;
+  a.part_idx = w.part_idx;
+  a.nq = c.nq;
+  a.d = c.d;
+  a.k = k;
+  a.row_begin = row_begin;
+  a.row_end = row_end;
+  a.shared_stream = c.nq > qb ? 1 : 0;
+  return a;
+}
+// (candidate scan first: the kernels sit in the code object in order of instantiation, which tools/cmp_device_asm.py
+// and a plain diff of the device assembly rely on)
+void launch_cand_scan(const Call& c, int qb, const ScanArgs& a, int grid_x) {
+  with_dtype(c.dtype, [&](auto t) { launch_cand<decltype(t)>(qb, a, grid_x, c.st); });
+}
+void launch_list_scan(const Call& c, int kp, int qb, const ScanArgs& a, int grid_x) {
+  with_dtype(c.dtype, [&](auto t) { launch_scan<decltype(t)>(kp, qb, a, grid_x, c.st); });
+}
+
+// partial lists -> the list of the `kout` best in the workspace (prefix / previous pass), rank kout - 1 to kth_val
+MergeArgs<int> merge_to_workspace(const Call& c, const SimWorkspace& w, int nlists, int kin, int kout, float* kth_val) {
+  MergeArgs<int> m{};
+  m.vals = w.part_val;
+  m.idx = w.part_idx;
+  m.nq = c.nq;
+  m.nlists = nlists;
+  m.kin = kin;
+  m.kout = kout;
+  m.out_val = w.pre_val;
+  m.out_idx32 = w.pre_idx;
+  m.kth_val = kth_val;
+  return m;
+}
+// partial lists (+ the prefix list) -> the caller's output
+MergeArgs<int> merge_to_output(const Call& c, const SimWorkspace& w, int nlists, int kin, bool with_prefix,
+                               const int* gate, int gate_want) {
+  MergeArgs<int> m{};
+  m.vals = w.part_val;
+  m.idx = w.part_idx;
+  m.nq = c.nq;
+  m.nlists = nlists;
+  m.kin = kin;
+  m.kout = c.k;
+  if (with_prefix) {
+    m.extra_val = w.pre_val;
+    m.extra_idx = w.pre_idx;
+    m.kin_extra = c.k;
+  }
+  m.out_val = c.out_val;
+  m.out_idx = c.out_idx;
+  m.idx_base = c.idx_base;
+  m.gate = gate;
+  m.gate_want = gate_want;
+  return m;
+}
+
+// One list scan over every row + one merge.  With `gate`: the fallback of the group-floor candidate flow.
+int run_single_scan(const SimTopkPlan& p, const SimWorkspace& w, const Call& c, const int* gate) {
+  ScanArgs a = list_scan_args(c, w, p.qb, c.k, 0, c.ng);
+  a.gate = gate;
+  launch_list_scan(c, p.kp, p.qb, a, p.grid_a);
+  HCIR_LAUNCH_CHECK();
+  launch_merge32(merge_to_output(c, w, p.grid_a, p.kp, false, gate, 1), c.st);
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
+// phase A of the list flow: rows [0, S) -> the prefix top-k list and its k-th score, the floor of what follows
+int run_list_prefix(const SimTopkPlan& p, const SimWorkspace& w, const Call& c, int* zero_cnt) {
+  launch_list_scan(c, p.kp, p.qb, list_scan_args(c, w, p.qb, c.k, 0, p.S), p.grid_a);
+  HCIR_LAUNCH_CHECK();
+  MergeArgs<int> m = merge_to_workspace(c, w, p.grid_a, p.kp, c.k, w.floor_val);
+  m.gate_want = 1;  // (no gate: ignored)
+  m.zero_cnt = zero_cnt;
+  launch_merge32(m, c.st);
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
+// The list flow: phase A unless the caller's flow has run it; phase B: rows [S, ng) with the prefix k-th score as
+// floor, merged with the prefix list.  With `gate`, phase B is the fallback of a flow whose candidate buffer overflowed.
+int run_list_two_phase(const SimTopkPlan& p, const SimWorkspace& w, const Call& c, const int* gate, bool phase_a_done) {
+  if (!phase_a_done) {
+    const int rc = run_list_prefix(p, w, c, nullptr);
+    if (rc != HCIR_OK) return rc;
+  }
+  ScanArgs a = list_scan_args(c, w, p.qb, c.k, p.S, c.ng);
+  a.floor_val = w.floor_val;
+  a.gate = gate;
+  launch_list_scan(c, p.kp, p.qb, a, p.grid_b);
+  HCIR_LAUNCH_CHECK();
+  launch_merge32(merge_to_output(c, w, p.grid_b, p.kp, true, gate, gate ? 1 : 0), c.st);
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
+// <= 128 queries, k <= 64, big gallery (docs/LAB_NOTEBOOK.md "sim_topk: candidate flow").
+//   A  rows [0, S): the 16-entry list kernel (its fixed cost is 53 us; the 64-entry one costs 131 us), workgroup
+//      x in group x % G, G = 1 (k <= 16) or ceil(k / 16); one merge launch gives every group's floor - the
+//      k-th (G = 1) or 16th best score of the group - and, for G = 1, the prefix top-k list;
+//   B  a scan WITHOUT lists appends every row at / above the floor (min over the groups: >= k rows sit at or
+//      above it) to the query's candidate buffer: G = 1 over rows [S, N) with `> floor` (a tie loses to the k
+//      prefix rows with smaller indices), G > 1 over ALL rows with `>= floor` (the group lists do not hold the
+//      prefix's top-k);
+//   C  select: top-k of the candidates (+ the prefix list), one wave per query;
+//   then the list flow as fallback, gated by the overflow flag (sim_plan_candidate).
+int run_candidate_flow(const SimTopkPlan& p, const SimWorkspace& w, const Call& c) {
+  const int merge_grid = (int)hcir_cdiv(c.nq, 4);
+  ScanArgs s = list_scan_args(c, w, p.cand_qb, p.G == 1 ? c.k : 16, 0, p.S);
+  launch_list_scan(c, 16, p.cand_qb, s, p.cand_grid_a);
+  HCIR_LAUNCH_CHECK();
+  MergeArgs<int> m = merge_to_workspace(c, w, p.cand_grid_a, 16, s.k, w.floor_val);
+  m.zero_cnt = w.cand_cnt;
+  m.ngroups = p.G;
+  if (p.G == 1)
+    launch_merge32(m, c.st);   // four waves per query (the selection merge below: 21.6 us at 32 queries)
+  else
+    hipLaunchKernelGGL(topk_merge_sel_kernel<kMergeLPL>, dim3(merge_grid, p.G), dim3(256), 0, c.st, m);
+  HCIR_LAUNCH_CHECK();
+  s.row_begin = p.G == 1 ? p.S : 0;
+  s.row_end = c.ng;
+  s.floor_val = w.floor_val;
+  s.floor_groups = p.G;
+  s.floor_inclusive = p.G > 1 ? 1 : 0;
+  s.cand_val = w.cand_val;
+  s.cand_idx = w.cand_idx;
+  s.cand_cnt = w.cand_cnt;
+  s.overflow = w.overflow;
+  s.cap = p.cand_cap;
+  s.cand_query_major = 1;
+  launch_cand_scan(c, p.cand_qb, s, p.cand_grid_b);
+  HCIR_LAUNCH_CHECK();
+  SelectArgs sa{};
+  sa.cand_val = w.cand_val;
+  sa.cand_idx = w.cand_idx;
+  sa.cand_cnt = w.cand_cnt;
+  sa.cap = p.cand_cap;
+  if (p.G == 1) {
+    sa.pre_val = w.pre_val;
+    sa.pre_idx = w.pre_idx;
+    sa.kpre = c.k;
+  }
+  sa.out_val = c.out_val;
+  sa.out_idx = c.out_idx;
+  sa.nq = c.nq;
+  sa.idx_base = c.idx_base;
+  sa.k = c.k;
+  sa.gate = w.overflow;
+  sa.gate_want = 0;
+  if (p.select == SIM_SELECT_WAVE_SMALL)
+    hipLaunchKernelGGL(topk_select_kernel<kSelLPLSmall>, dim3(merge_grid), dim3(256), 0, c.st, sa);
+  else if (p.select == SIM_SELECT_WAVE)
+    hipLaunchKernelGGL(topk_select_kernel<kCandLPL>, dim3(merge_grid), dim3(256), 0, c.st, sa);
+  else
+    hipLaunchKernelGGL(topk_select4_kernel<(kCandCapBig + 255) / 256 + 1>, dim3((unsigned)c.nq), dim3(256), 0, c.st, sa);
+  HCIR_LAUNCH_CHECK();
+  return p.fallback_phases == 2 ? run_list_two_phase(p, w, c, w.overflow, p.phase_a_done)
+                                : run_single_scan(p, w, c, w.overflow);
+}
+
+// > 128 queries (MFMA-bound): list prefix, then the 256 x 256 tile scan collects the rare rows above the floor and one
+// merge ranks them with the prefix list; the list-keeping phase B only runs (device-side gate) if a buffer overflowed.
+int run_big_tile_flow(const SimTopkPlan& p, const SimWorkspace& w, const Call& c) {
+  const int rc = run_list_prefix(p, w, c, w.cand_cnt);  // (the big scan's counters and overflow flag start at zero)
+  if (rc != HCIR_OK) return rc;
+  BigScanArgs b{};
+  b.q = c.q;
+  b.g = c.g;
+  b.floor_val = w.floor_val;
+  b.cand_val = w.cand_val;
+  b.cand_idx = w.cand_idx;
+  b.cand_cnt = w.cand_cnt;
+  b.overflow = w.overflow;
+  b.nq = c.nq;
+  b.row_begin = p.S;
+  b.row_end = c.ng;
+  b.d = c.d;
+  b.cap = p.cand_cap;
+  with_dtype(c.dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (!std::is_same<T, float>::value)   // (fp32 never gets this flow)
+      hipLaunchKernelGGL(sim_scan_big_kernel<T>, dim3((unsigned)p.big_grid_x, (unsigned)p.big_grid_y), dim3(512), 0,
+                         c.st, b);
+  });
+  HCIR_LAUNCH_CHECK();
+  MergeArgs<int> m = merge_to_output(c, w, p.cand_cap, 1, true, w.overflow, 0);
+  m.vals = w.cand_val;
+  m.idx = w.cand_idx;
+  m.nlists_q = w.cand_cnt;
+  launch_merge32(m, c.st);
+  HCIR_LAUNCH_CHECK();
+  return run_list_two_phase(p, w, c, w.overflow, p.phase_a_done);
+}
+
+// k > 64: successive passes of <= 64 ranks below a moving ceiling.
+int run_multipass(const SimTopkPlan& p, const SimWorkspace& w, const Call& c) {
+  int done = 0;
+  for (int pass = 0; pass < p.npass; ++pass) {
+    const int kk = (c.k - done) < 64 ? (c.k - done) : 64;
+    ScanArgs a = list_scan_args(c, w, p.qb, kk, 0, c.ng);
+    a.ceil_val = pass ? w.ceil_val : nullptr;
+    a.ceil_idx = pass ? w.ceil_idx : nullptr;
+    launch_list_scan(c, p.kp, p.qb, a, p.grid_a);
+    HCIR_LAUNCH_CHECK();
+    MergeArgs<int> m = merge_to_workspace(c, w, p.grid_a, p.kp, kk, w.ceil_val);
+    m.kth_idx = w.ceil_idx;
+    hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3((int)hcir_cdiv(c.nq, 4)), dim3(256), 0, c.st, m);
+    HCIR_LAUNCH_CHECK();
+    // scatter this pass's [nq][kk] block into out[:, done:done+kk]
+    hipLaunchKernelGGL(pass_copy_kernel, dim3((unsigned)hcir_cdiv(c.nq * kk, 256)), dim3(256), 0, c.st,
+                       w.pre_val, w.pre_idx, c.nq, kk, c.k, done, c.idx_base, c.out_val, c.out_idx);
+    HCIR_LAUNCH_CHECK();
+    done += kk;
+  }
+  return HCIR_OK;
 }
 
 }  // namespace
@@ -1634,11 +1761,8 @@ int hcir_debug_stamps(unsigned long long* host_dst) {
 #endif
 
 size_t hcir_sim_topk_workspace_bytes(int64_t nq, int64_t ng, int32_t d, int32_t k, int dtype) {
-  (void)d;
-  (void)dtype;
   if (nq <= 0 || ng <= 0 || k <= 0) return 0;
-  const Plan p = make_plan(nq, ng, k);
-  return carve(nullptr, nq, k, p).bytes;
+  return sim_topk_plan(nq, ng, d, k, dtype, false, false).ws_bytes;  // (the layout does not depend on the norms)
 }
 
 int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t d, int32_t k,
@@ -1650,324 +1774,18 @@ int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t 
   if (nq <= 0 || ng <= 0 || d <= 0 || (d & 7) || k <= 0 || k > HCIR_TOPK_MAX) return HCIR_ERR_INVALID;
   if (k > ng || ng >= (int64_t(1) << 31)) return HCIR_ERR_INVALID;
   if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
-  const Plan p = make_plan(nq, ng, k);
-  Workspace w = carve(workspace, nq, k, p);
-  if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int merge_grid = (int)hcir_cdiv(nq, 4);
-
-  const int64_t qblocks = hcir_cdiv(nq, p.qb);
-  ScanArgs a{};
-  a.q = q;
-  a.g = g;
-  a.qn = q_inv_norm;
-  a.gn = g_inv_norm;
-  a.part_val = w.part_val;
-  a.part_idx = w.part_idx;
-  a.nq = nq;
-  a.d = d;
-  a.shared_stream = qblocks > 1 ? 1 : 0;
-
-  // ---- <= 128 queries, k <= 64, big gallery: candidate-append flow (DESIGN.md "sim_topk: candidate flow").
-  //   A  rows [0, S): the 16-entry list kernel (its fixed cost is 53 us; the 64-entry one costs 131 us), workgroup
-  //      x in group x % G, G = 1 (k <= 16) or ceil(k / 16); one merge launch gives every group's floor - the
-  //      k-th (G = 1) or 16th best score of the group - and, for G = 1, the prefix top-k list;
-  //   B  a scan WITHOUT lists appends every row at / above the floor (min over the groups: >= k rows sit at or
-  //      above it) to the query's candidate buffer: G = 1 over rows [S, N) with `> floor` (a tie loses to the k
-  //      prefix rows with smaller indices), G > 1 over ALL rows with `>= floor` (the group lists do not hold the
-  //      prefix's top-k);
-  //   C  select: top-k of the candidates (+ the prefix list), one wave per query.
-  // A gallery whose later rows systematically beat the prefix overflows a buffer: the device flag then gates the
-  // list-keeping flow below (all of it for G > 1, its second phase for G = 1), whose launches are empty otherwise.
-  const int* fallback_gate = nullptr;
-  bool prefix_done = false;
-  int64_t cand_prefix = 0;
-  // Same-box A/B against the list-keeping flow (tools/ab_sim.py, 1 M x 768 fp16, k = 16): 1 query 313 -> 302 us,
-  // 32 queries 327 -> 318 us, but 64 queries 333 -> 352 us and 128 queries 443 -> 453 us (two query tiles per wave:
-  // the list kernel's main scan is as fast there, and the flow adds two gated launches): k <= 16 takes the
-  // candidate flow up to 32 queries only.  k > 16 (1.25 M x 1024, top-50): 1001 -> 639 us at 32 queries,
-  // 1662 -> 742 us at 64: always.
-  if (p.npass == 1 && p.prefix < ng && nq <= 128 && (k > 16 || nq <= 32)) {
-    const int G = k <= 16 ? 1 : (k + 15) / 16;
-    int cap = k <= 16 ? kCandCap : kCandCapBig;
-    Plan pc = p;
-    pc.kp = 16;
-    pc.qb = nq <= 32 ? 32 : (nq <= 64 ? 64 : 128);
-    pc.gm = pc.qb == 128 ? 128 : 256;
-    int64_t S = p.prefix;
-    if (G == 1) {
-      // Without lists behind the floor a longer prefix costs little (one round of <= 512 one-tile workgroups
-      // takes the same ~55 us as half a round) and pays twice: fewer rows for the main scan and r = 7 instead of
-      // 15, i.e. <= 38 * 7 candidates per query, a 7-slot select instead of a 15-slot one.
-      // (measured, 1 M x 768 fp16: 32 queries 0.314 -> 0.306 ms; at 64 queries the 2-tile-deep list prefix costs
-      // what the shorter main scan and select save, 0.330 -> 0.335 ms: N/16 kept there)
-      S = pc.qb == 32 ? ng / 8 : ng / 16;
-      S = S < 8192 ? 8192 : (S > 131072 ? 131072 : S);
-      S = hcir_cdiv(S, pc.gm) * pc.gm;
-      if (S < ng && 38 * ((ng - S) / S + 1) <= 64 * 7) cap = 64 * 7;  // small select (one buffer size for scan AND select)
-    }
-    if (G > 1) {
-      // Rows at or above the floor, r + 1 = N / S.  The tail probability at a group's 16th best of n rows is
-      // ~ Gamma(16) / n (mean 16, sd 4), the floor is the weakest of the G groups: the count is ~ X G (r + 1) with
-      // X the largest of G Gamma(16) draws.  P(X > 38) ~ 1e-5 per draw: sized for 38 G (r + 1) <= cap (an
-      // earlier 16 G + 5 sigma sizing overflowed a few percent of the QUERIES, and one overflow reruns the call).
-      const float per = 38.0f * G;
-      int64_t rp1 = (int64_t)((float)cap / per);
-      rp1 = rp1 < 2 ? 2 : rp1;
-      S = hcir_cdiv(ng, rp1);
-      S = S < 8192 ? 8192 : S;
-      S = hcir_cdiv(S, pc.gm) * pc.gm;
-    }
-    if (S < ng && hcir_cdiv(S, pc.gm) >= 4 * G) {
-      const int64_t qbl = hcir_cdiv(nq, pc.qb);
-      ScanArgs c = a;
-      c.shared_stream = qbl > 1 ? 1 : 0;
-      c.k = G == 1 ? k : 16;
-      c.row_begin = 0;
-      c.row_end = S;
-      // (the 16-entry list kernel of 33..64 queries works on 128-row tiles)
-      const int gm_a = pc.qb == 64 ? 128 : pc.gm;
-      const int grid_a = scan_grid_x(hcir_cdiv(S, gm_a), qbl);
-      launch_scan_dtype(dtype, pc, c, grid_a, st);
-      HCIR_LAUNCH_CHECK();
-      MergeArgs<int> m{};
-      m.vals = w.part_val;
-      m.idx = w.part_idx;
-      m.nq = nq;
-      m.nlists = grid_a;
-      m.kin = 16;
-      m.kout = c.k;
-      m.out_val = w.pre_val;
-      m.out_idx32 = w.pre_idx;
-      m.kth_val = w.floor_val;
-      m.zero_cnt = w.cand_cnt;
-      m.ngroups = G;
-      if (G == 1)
-        launch_merge32(m, st);   // four waves per query (the selection merge below: 21.6 us at 32 queries)
-      else
-        hipLaunchKernelGGL(topk_merge_sel_kernel<kMergeLPL>, dim3(merge_grid, G), dim3(256), 0, st, m);
-      HCIR_LAUNCH_CHECK();
-      int* overflow = w.cand_cnt + nq;
-      c.row_begin = G == 1 ? S : 0;
-      c.row_end = ng;
-      c.floor_val = w.floor_val;
-      c.floor_groups = G;
-      c.floor_inclusive = G > 1 ? 1 : 0;
-      c.cand_val = w.cand_val;
-      c.cand_idx = w.cand_idx;
-      c.cand_cnt = w.cand_cnt;
-      c.overflow = overflow;
-      c.cap = cap;
-      c.cand_query_major = 1;
-      const bool cg3 = pc.qb == 64;   // launch_cand's 64-query geometry: 128-row tiles, up to 768 workgroups
-      const int grid_b = scan_grid_x(hcir_cdiv(c.row_end - c.row_begin, cg3 ? 128 : pc.gm), qbl, cg3 ? 768 : kMaxGridX);
-      launch_cand_dtype(dtype, pc.qb, c, grid_b, st);
-      HCIR_LAUNCH_CHECK();
-      SelectArgs sa{};
-      sa.cand_val = w.cand_val;
-      sa.cand_idx = w.cand_idx;
-      sa.cand_cnt = w.cand_cnt;
-      sa.cap = cap;
-      if (G == 1) {
-        sa.pre_val = w.pre_val;
-        sa.pre_idx = w.pre_idx;
-        sa.kpre = k;
-      }
-      sa.out_val = out_val;
-      sa.out_idx = out_idx;
-      sa.nq = nq;
-      sa.idx_base = idx_base;
-      sa.k = k;
-      sa.gate = overflow;
-      sa.gate_want = 0;
-      // expected candidates <= 38 (N - S) / S per query (k <= 16): a small select when the prefix is long
-      if (cap == 64 * 7)
-        hipLaunchKernelGGL(topk_select_kernel<8>, dim3(merge_grid), dim3(256), 0, st, sa);
-      else if (k <= 16)
-        hipLaunchKernelGGL(topk_select_kernel<kCandLPL>, dim3(merge_grid), dim3(256), 0, st, sa);
-      else   // 3008 candidates: four waves per query, 12 + 1 slots per lane
-        hipLaunchKernelGGL(topk_select4_kernel<(kCandCapBig + 255) / 256 + 1>, dim3((unsigned)nq), dim3(256), 0, st, sa);
-      HCIR_LAUNCH_CHECK();
-      fallback_gate = overflow;
-      prefix_done = G == 1;   // the list flow's phase A is exactly what ran above (same kernel, rows [0, S))
-      if (G == 1) cand_prefix = S;
-    }
+  const SimTopkPlan p = sim_topk_plan(nq, ng, d, k, dtype, q_inv_norm != nullptr, g_inv_norm != nullptr);
+  if (!workspace || workspace_bytes < p.ws_bytes) return HCIR_ERR_WORKSPACE;
+  const SimWorkspace w = sim_workspace(workspace, nq, p);
+  const Call c{q, g, q_inv_norm, g_inv_norm, nq, ng, idx_base, d, k, dtype, out_val, out_idx,
+               static_cast<hipStream_t>(stream)};
+  switch (p.flow) {
+    case SIM_FLOW_SINGLE_SCAN: return run_single_scan(p, w, c, nullptr);
+    case SIM_FLOW_LIST_TWO_PHASE: return run_list_two_phase(p, w, c, nullptr, false);
+    case SIM_FLOW_CANDIDATE: return run_candidate_flow(p, w, c);
+    case SIM_FLOW_BIG_TILE: return run_big_tile_flow(p, w, c);
+    default: return run_multipass(p, w, c);
   }
-
-  Plan pp = p;  // (the prefix may shrink below)
-  if (cand_prefix) pp.prefix = cand_prefix;
-  // Group-floor candidate flow (k > 16): its fallback (a candidate buffer overflowed, ~1e-5 per call) is the ONE-phase
-  // list scan over all rows + one merge - two gated launches that exit at once in the common case, where the
-  // two-phase flow cost four (~4.5 us each even when empty: 3 % of a 64-query C5 call).
-  if (fallback_gate && !prefix_done) pp.prefix = ng;
-  // Many queries (MFMA-bound): the 256 x 256 tile scan collects the rare rows above the prefix floor.  The
-  // prefix itself runs on the list-keeping kernel at half that rate, so it is only as long as the candidate
-  // buffers require.  With r = rows behind the prefix / prefix rows, the number of rows that beat the
-  // prefix's k-th score is negative-binomial: mean k r, variance k r (1 + r) ~ (r sqrt k)^2; r is chosen so that
-  // mean + 5 sigma fits the buffer (overflow ~1e-6 per query for a gallery in random order; it is handled).
-  const bool big = p.npass == 1 && p.prefix < ng && dtype != HCIR_F32 && nq > 128 && k <= 16 &&
-                   d % 64 == 0 && !q_inv_norm && !g_inv_norm && ng - p.prefix >= 4096;
-  if (big) {
-    // (measured flat in r = 8..26 at 220 queries: a shorter prefix is paid back by a longer candidate merge;
-    // r is capped at 15 - the 1/16 prefix of the list-keeping path - which leaves 11 sigma of headroom)
-    int64_t rr = (int64_t)((float)kCandCap / ((float)k + 5.0f * sqrtf((float)k)));
-    rr = rr > 15 ? 15 : rr;
-    int64_t s = hcir_cdiv(ng, (rr < 1 ? 1 : rr) + 1);
-    s = s < 8192 ? 8192 : s;
-    s = hcir_cdiv(s, p.gm) * p.gm;
-    if (s < pp.prefix) pp.prefix = s;
-  }
-  if (p.npass == 1) {
-    a.k = k;
-    const bool two_phase = pp.prefix < ng;
-    // phase A: rows [0, prefix)
-    a.row_begin = 0;
-    a.row_end = pp.prefix;
-    const int64_t tiles_a = hcir_cdiv(pp.prefix, p.gm);
-    const int grid_a = scan_grid_x(tiles_a, qblocks);
-    a.gate = fallback_gate;
-    if (!prefix_done) {
-      launch_scan_dtype(dtype, p, a, grid_a, st);
-      HCIR_LAUNCH_CHECK();
-    }
-    MergeArgs<int> m{};
-    m.gate = fallback_gate;
-    m.gate_want = 1;
-    m.vals = w.part_val;
-    m.idx = w.part_idx;
-    m.nq = nq;
-    m.nlists = grid_a;
-    m.kin = p.kp;
-    m.kout = k;
-    if (!two_phase) {
-      m.out_val = out_val;
-      m.out_idx = out_idx;
-      m.idx_base = idx_base;
-      launch_merge32(m, st);
-      HCIR_LAUNCH_CHECK();
-      return HCIR_OK;
-    }
-    m.out_val = w.pre_val;
-    m.out_idx32 = w.pre_idx;
-    m.kth_val = w.floor_val;
-    if (big) m.zero_cnt = w.cand_cnt;  // the big scan's counters and overflow flag start at zero
-    if (!prefix_done) {
-      launch_merge32(m, st);
-      HCIR_LAUNCH_CHECK();
-    }
-    // phase B: rows [prefix, ng) with the prefix k-th score as floor
-    a.row_begin = pp.prefix;
-    a.row_end = ng;
-    a.floor_val = w.floor_val;
-    // Many queries (MFMA-bound): the 256 x 256 tile scan collects the rare rows above the floor; the
-    // list-keeping scan below then only runs (device-side gate) if a candidate buffer overflowed.
-    int* overflow = w.cand_cnt + nq;
-    if (big) {
-      BigScanArgs b{};
-      b.q = q;
-      b.g = g;
-      b.floor_val = w.floor_val;
-      b.cand_val = w.cand_val;
-      b.cand_idx = w.cand_idx;
-      b.cand_cnt = w.cand_cnt;
-      b.overflow = overflow;
-      b.nq = nq;
-      b.row_begin = pp.prefix;
-      b.row_end = ng;
-      b.d = d;
-      b.cap = kCandCap;
-      const int64_t qb256 = hcir_cdiv(nq, 256);
-      const int64_t tiles256 = hcir_cdiv(ng - pp.prefix, 256);
-      int64_t gx = 256 / qb256;  // one 128 KB workgroup per CU, every query block of a tile run resident
-      gx = gx < 8 ? 8 : (gx & ~int64_t(7));
-      gx = tiles256 < gx ? tiles256 : gx;
-      if (dtype == HCIR_F16)
-        hipLaunchKernelGGL(sim_scan_big_kernel<_Float16>, dim3((unsigned)gx, (unsigned)qb256), dim3(512), 0, st, b);
-      else
-        hipLaunchKernelGGL(sim_scan_big_kernel<__bf16>, dim3((unsigned)gx, (unsigned)qb256), dim3(512), 0, st, b);
-      HCIR_LAUNCH_CHECK();
-      MergeArgs<int> mc{};
-      mc.vals = w.cand_val;
-      mc.idx = w.cand_idx;
-      mc.nq = nq;
-      mc.nlists = kCandCap;
-      mc.nlists_q = w.cand_cnt;
-      mc.kin = 1;
-      mc.kout = k;
-      mc.extra_val = w.pre_val;
-      mc.extra_idx = w.pre_idx;
-      mc.kin_extra = k;
-      mc.out_val = out_val;
-      mc.out_idx = out_idx;
-      mc.idx_base = idx_base;
-      mc.gate = overflow;
-      mc.gate_want = 0;
-      launch_merge32(mc, st);
-      HCIR_LAUNCH_CHECK();
-      a.gate = overflow;  // the launches below: fallback only
-    }
-    const int64_t tiles_b = hcir_cdiv(ng - pp.prefix, p.gm);
-    const bool q64g3 = p.kp == 16 && p.qb == 64;
-    const int grid_b = scan_grid_x(tiles_b, qblocks, q64g3 ? kMaxGridQ64 : kMaxGridX);
-    launch_scan_dtype(dtype, p, a, grid_b, st);
-    HCIR_LAUNCH_CHECK();
-    MergeArgs<int> m2{};
-    m2.vals = w.part_val;
-    m2.idx = w.part_idx;
-    m2.nq = nq;
-    m2.nlists = grid_b;
-    m2.kin = p.kp;
-    m2.kout = k;
-    m2.extra_val = w.pre_val;
-    m2.extra_idx = w.pre_idx;
-    m2.kin_extra = k;
-    m2.out_val = out_val;
-    m2.out_idx = out_idx;
-    m2.idx_base = idx_base;
-    if (big) {
-      m2.gate = overflow;
-      m2.gate_want = 1;
-    } else if (fallback_gate) {
-      m2.gate = fallback_gate;
-      m2.gate_want = 1;
-    }
-    launch_merge32(m2, st);
-    HCIR_LAUNCH_CHECK();
-    return HCIR_OK;
-  }
-
-  // k > 64: successive passes of <= 64 ranks below a moving ceiling.
-  a.row_begin = 0;
-  a.row_end = ng;
-  const int grid_x = scan_grid_x(hcir_cdiv(ng, p.gm), qblocks);
-  int done = 0;
-  for (int pass = 0; pass < p.npass; ++pass) {
-    const int kk = (k - done) < 64 ? (k - done) : 64;
-    a.k = kk;
-    a.ceil_val = pass ? w.ceil_val : nullptr;
-    a.ceil_idx = pass ? w.ceil_idx : nullptr;
-    launch_scan_dtype(dtype, p, a, grid_x, st);
-    HCIR_LAUNCH_CHECK();
-    MergeArgs<int> m{};
-    m.vals = w.part_val;
-    m.idx = w.part_idx;
-    m.nq = nq;
-    m.nlists = grid_x;
-    m.kin = p.kp;
-    m.kout = kk;
-    m.out_val = w.pre_val;
-    m.out_idx32 = w.pre_idx;
-    m.kth_val = w.ceil_val;
-    m.kth_idx = w.ceil_idx;
-    hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3(merge_grid), dim3(256), 0, st, m);
-    HCIR_LAUNCH_CHECK();
-    // scatter this pass's [nq][kk] block into out[:, done:done+kk]
-    hipLaunchKernelGGL(pass_copy_kernel, dim3((unsigned)hcir_cdiv(nq * kk, 256)), dim3(256), 0, st,
-                       w.pre_val, w.pre_idx, nq, kk, k, done, idx_base, out_val, out_idx);
-    HCIR_LAUNCH_CHECK();
-    done += kk;
-  }
-  return HCIR_OK;
 }
 
 int hcir_topk_merge(const float* vals, const int64_t* idx, int32_t nlists, int64_t nq, int32_t k_in,
