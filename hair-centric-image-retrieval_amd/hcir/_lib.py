@@ -124,6 +124,11 @@ SIGNATURES = {
     "hcir_resize_coeffs": (c_int, [c_i32, c_i32, c_i32, c_vp, c_vp]),
     "hcir_view_blur_weights": (c_int, [c_f32, c_vp, c_vp, c_vp]),
     "hcir_simclr_view_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_conv2d_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                c_vp, c_int, c_vp, c_vp]),
+    "hcir_conv2d_tile_n": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "hcir_resnet_stem": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_avgpool_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_int, c_f32, c_vp, c_vp]),
 }
 
 

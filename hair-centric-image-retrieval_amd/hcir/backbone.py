@@ -17,6 +17,7 @@ from torch import nn
 
 from . import _tv_resnet, models_vit
 from .main_backbone import SimCLRProjectionHead, ViTWrapper
+from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 
 
@@ -39,6 +40,14 @@ class SimCLR(nn.Module):
         else:
             raise ValueError(f"Unsupported model: {model}")
         self.projection_head = SimCLRProjectionHead(proj_input_dim, proj_input_dim, output_dim)
+        # opt-in HIP trunk for the ResNets (eval mode, HIP device, no_grad), as in SHAM2
+        self.hip_trunk = False
+        self._trunk_cache = ResNetEngineCache()
+
+    def _hip_trunk(self, x):
+        if "vit" in self.model or not hip_trunk_active(self.hip_trunk, self.backbone, x):
+            return None
+        return self._trunk_cache.get(self.backbone, x.device).forward(x)
 
     def forward(self, x):
         if "vit" in self.model:
@@ -46,11 +55,18 @@ class SimCLR(nn.Module):
             # (HP/src/backbone.py:675-681).  Defined as SHAM2 does: project CLS.
             _, cls16 = self.backbone.forward_cls(x, want_f16=True)
             return self.projection_head.forward_hip(cls16)
+        f = self._hip_trunk(x)
+        if f is not None:
+            head = self.projection_head
+            return head(f) if head.training else head.forward_hip(f.half())
         return self.projection_head(self.backbone(x).flatten(start_dim=1))
 
     def extract_features(self, x):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
+        f = self._hip_trunk(x)
+        if f is not None:
+            return f
         return self.backbone(x).flatten(start_dim=1)
 
 

@@ -24,6 +24,7 @@ from torch import nn
 from . import _lib
 from ._lib import HcirError, check
 from . import _tv_resnet, _tv_vit
+from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 from .vit_train import VitTrainer, vit_cls_with_grad
 
@@ -199,6 +200,25 @@ class SHAM2(nn.Module):
         deactivate_requires_grad(self.backbone_momentum)
         deactivate_requires_grad(self.projection_head_momentum)
 
+        # opt-in: ResNet trunks in eval mode, on a HIP device, under no_grad run on hcir.resnet_engine (the HIP
+        # convolution kernels) instead of torch / MIOpen; off, or with any condition unmet, the torch path is untouched
+        self.hip_trunk = False
+        self._trunk_caches = {}
+
+    def _hip_trunk(self, which: str, x):
+        """fp32 [B, C] features of `backbone` / `backbone_momentum` from the HIP engine, or None when the switch
+        does not apply to this call."""
+        trunk = getattr(self, which)
+        if "vit" in self.model or not hip_trunk_active(self.hip_trunk, trunk, x):
+            return None
+        cache = self._trunk_caches.setdefault(which, ResNetEngineCache())
+        return cache.get(trunk, x.device).forward(x)
+
+    @staticmethod
+    def _project(head, f):
+        # eval-mode head on the two affine-epilogue GEMMs (forward_hip); a head in train mode keeps its torch modules
+        return head(f) if head.training else head.forward_hip(f.half())
+
     def _vit_project(self, backbone, head, x):
         if head.training:
             # train mode (HP/src/pretrain_engine.py:603 model.train()): the backbone forward is differentiable on the
@@ -211,6 +231,9 @@ class SHAM2(nn.Module):
     def forward(self, x):
         if "vit" in self.model:
             return self._vit_project(self.backbone, self.projection_head, x)
+        f = self._hip_trunk("backbone", x)
+        if f is not None:
+            return self._project(self.projection_head, f)
         x = self.backbone(x).flatten(start_dim=1)
         return self.projection_head(x)
 
@@ -231,16 +254,25 @@ class SHAM2(nn.Module):
     def forward_momentum(self, x):
         if "vit" in self.model:
             return self._vit_project(self.backbone_momentum, self.projection_head_momentum, x)
+        f = self._hip_trunk("backbone_momentum", x)
+        if f is not None:
+            return self._project(self.projection_head_momentum, f)
         x = self.backbone_momentum(x).flatten(start_dim=1)
         return self.projection_head_momentum(x)
 
     def extract_features(self, x):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
+        f = self._hip_trunk("backbone", x)
+        if f is not None:
+            return f
         return self.backbone(x).flatten(start_dim=1)
 
     @torch.no_grad()
     def extract_features_ema(self, x):
         if "vit" in self.model:
             return self.backbone_momentum.forward_cls(x)
+        f = self._hip_trunk("backbone_momentum", x)
+        if f is not None:
+            return f
         return self.backbone_momentum(x).flatten(start_dim=1)

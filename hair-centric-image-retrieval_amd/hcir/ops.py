@@ -158,3 +158,83 @@ def topk_merge(vals: torch.Tensor, idx: torch.Tensor, k_out: int) -> Tuple[torch
     check(_lib.lib().hcir_topk_merge(vals.data_ptr(), idx.data_ptr(), nl, nq, kin, k_out,
                                      ov.data_ptr(), oi.data_ptr(), _stream(vals)), "hcir_topk_merge")
     return ov, oi
+
+
+# ------------------------------------------------------------------ ResNet trunk (csrc/conv.hip)
+def conv_out_size(n: int, r: int, stride: int, pad: int) -> int:
+    return (n + 2 * pad - r) // stride + 1
+
+
+def stem_out_size(n: int) -> int:
+    """Side of the pooled stem map: conv 7 / 2 / pad 3, then maxpool 3 / 2 / pad 1."""
+    return ((n - 1) // 2 + 1 - 1) // 2 + 1
+
+
+def conv2d_f16(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, stride: int, pad: int,
+               resid: Optional[torch.Tensor] = None, relu: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu?(conv(x, w) * scale + bias (+ resid)): x fp16 [B,H,W,Cin], w fp16 [Cout,R,S,Cin], scale / bias fp32 [Cout],
+    resid fp16 of the output's shape -> fp16 [B,Ho,Wo,Cout] (written into `out` when given)."""
+    for t, n in ((x, "x"), (w, "w"), (scale, "scale"), (bias, "bias")):
+        _dev(t, n)
+    if x.dtype != torch.float16 or w.dtype != torch.float16 or x.dim() != 4 or w.dim() != 4:
+        raise HcirError("conv2d_f16 expects fp16 NHWC activations and fp16 [Cout,R,S,Cin] weights")
+    if scale.dtype != torch.float32 or bias.dtype != torch.float32:
+        raise HcirError("conv2d_f16 expects fp32 scale and bias")
+    b, h, wd, cin = x.shape
+    cout, r, s, cin_w = w.shape
+    if cin_w != cin or scale.numel() != cout or bias.numel() != cout:
+        raise HcirError(f"shape mismatch: x {tuple(x.shape)} w {tuple(w.shape)} scale {tuple(scale.shape)}")
+    shape = (b, conv_out_size(h, r, stride, pad), conv_out_size(wd, s, stride, pad), cout)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=x.device)
+    for t, n in ((out, "out"), (resid, "resid")):
+        if t is not None:
+            _dev(t, n)
+            if t.dtype != torch.float16 or tuple(t.shape) != shape:
+                raise HcirError(f"`{n}` must be fp16 {shape}, got {t.dtype} {tuple(t.shape)}")
+    check(_lib.lib().hcir_conv2d_f16(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, r, s, stride, pad,
+                                     scale.data_ptr(), bias.data_ptr(), _ptr(resid), int(relu), out.data_ptr(),
+                                     _stream(x)), "hcir_conv2d_f16")
+    return out
+
+
+def resnet_stem(img: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """maxpool(relu(bn(conv7x7/2(img)))): img fp32 NCHW [B,3,H,W], w_packed from resnet_engine.pack_stem_weight ->
+    fp16 NHWC [B,Hp,Wp,64]."""
+    for t, n in ((img, "img"), (w_packed, "w_packed"), (scale, "scale"), (bias, "bias")):
+        _dev(t, n)
+    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 3:
+        raise HcirError(f"resnet_stem expects an fp32 [B,3,H,W] image, got {img.dtype} {tuple(img.shape)}")
+    if w_packed.dtype != torch.float16 or w_packed.numel() != 10 * 2 * 64 * 8:
+        raise HcirError("resnet_stem expects the packed fp16 stem weight (pack_stem_weight)")
+    if scale.dtype != torch.float32 or bias.dtype != torch.float32 or scale.numel() != 64 or bias.numel() != 64:
+        raise HcirError("resnet_stem expects fp32 scale and bias of 64 channels")
+    b, _, h, wd = img.shape
+    shape = (b, stem_out_size(h), stem_out_size(wd), 64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=img.device)
+    _dev(out, "out")
+    if out.dtype != torch.float16 or tuple(out.shape) != shape:
+        raise HcirError(f"`out` must be fp16 {shape}")
+    check(_lib.lib().hcir_resnet_stem(img.data_ptr(), b, h, wd, w_packed.data_ptr(), scale.data_ptr(),
+                                      bias.data_ptr(), out.data_ptr(), _stream(img)), "hcir_resnet_stem")
+    return out
+
+
+def avgpool_nhwc(x: torch.Tensor, l2_normalize: bool = False, eps: float = 1e-12,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mean over H, W of fp16 [B,H,W,C] -> fp32 [B,C]; optionally F.normalize of each row."""
+    _dev(x, "x")
+    if x.dtype != torch.float16 or x.dim() != 4:
+        raise HcirError("avgpool_nhwc expects fp16 [B,H,W,C]")
+    b, h, wd, c = x.shape
+    if out is None:
+        out = torch.empty((b, c), dtype=torch.float32, device=x.device)
+    _dev(out, "out")
+    if out.dtype != torch.float32 or tuple(out.shape) != (b, c):
+        raise HcirError(f"`out` must be fp32 {(b, c)}")
+    check(_lib.lib().hcir_avgpool_nhwc_f16(x.data_ptr(), b, h, wd, c, int(l2_normalize), eps, out.data_ptr(),
+                                           _stream(x)), "hcir_avgpool_nhwc_f16")
+    return out

@@ -42,6 +42,8 @@ def parse_args(argv=None):
     parser.add_argument('--num_workers', type=int, default=4)
     parser.add_argument('--eval_type', default=None, type=str,
                         choices=["knn", "linear_prob", "visualization", "inter_intra_distance"])
+    # not a reference flag: which code runs a ResNet trunk in eval mode - torch / MIOpen, or hcir.resnet_engine
+    parser.add_argument('--resnet_engine', type=str, default='torch', choices=['torch', 'hip'])
     return parser.parse_args(argv)
 
 
@@ -92,6 +94,8 @@ def build_model(args):
                          "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae")
     if args.checkpoint_path:
         print("Model weights loaded!")
+    if getattr(args, "resnet_engine", "torch") == "hip" and hasattr(model, "hip_trunk"):
+        model.hip_trunk = True
     return model
 
 

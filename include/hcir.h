@@ -709,6 +709,49 @@ int hcir_view_blur_weights(float sigma, int32_t* r, uint32_t* ww, uint32_t* fw);
 int hcir_simclr_view_f32(const uint8_t* crops, const hcir_view_params* params_dev, const hcir_view_params* params_host,
                          int64_t n, const float* mean3, const float* std3, float* out, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * ResNet-18 / ResNet-50 trunk, eval mode (running statistics), inference only.
+ * Replaces the nn.Sequential(children()[:-1]) trunk behind SHAM2.extract_features / extract_features_ema
+ * (HP/src/main_backbone.py:572-578,624-629) and SimCLR.extract_features (HP/src/backbone.py:660-661):
+ * torchvision Conv2d / BatchNorm2d / ReLU / MaxPool2d / AdaptiveAvgPool2d.
+ * Activations are NHWC fp16; accumulation and every epilogue are fp32; each stored value is rounded to fp16 once.
+ * ------------------------------------------------------------------ */
+
+/* Implicit-GEMM convolution (no im2col buffer) fused with the folded BatchNorm, the block's residual add and ReLU:
+ *   out[b][ho][wo][n] = fp16( relu?( acc * scale[n] + bias[n] (+ resid[b][ho][wo][n]) ) ),
+ *   acc = sum_{r,s,c} x[b][ho*stride + r - pad][wo*stride + s - pad][c] * w[n][r][s][c]   (padding taps are zeros).
+ * x fp16 [B][H][W][Cin]; w fp16 [Cout][R][S][Cin]; scale, bias fp32 [Cout] (scale = gamma / sqrt(var + eps) stays
+ * out of the fp16 weights: a small running_var would overflow them); resid fp16 of out's shape or NULL, added in
+ * fp32; out fp16 [B][Ho][Wo][Cout], Ho = (H + 2 pad - R) / stride + 1.
+ * Kernels exist for (R, S, pad) in {(1,1,0), (3,3,1)}, stride in {1, 2}, Cin % 64 == 0, Cout % 64 == 0, any
+ * B, H, W >= 1; anything else is HCIR_ERR_UNSUPPORTED (decided from the shape alone, before any pointer is looked at
+ * or the device is touched). */
+int hcir_conv2d_f16(const void* x, int64_t b, int32_t h, int32_t w, int32_t cin, const void* wgt, int32_t cout,
+                    int32_t r, int32_t s, int32_t stride, int32_t pad, const float* scale, const float* bias,
+                    const void* resid, int relu, void* out, void* stream);
+/* HOST.  Width of the output-channel tile hcir_conv2d_f16 runs this shape with: 128 when Cout % 128 == 0 and the
+ * launch still has at least 512 workgroups of 128 pixels x 128 channels, else 64 (two instantiations of one kernel; a
+ * test uses this to know which one a case exercised).  Negative: the status hcir_conv2d_f16 returns for the shape. */
+int32_t hcir_conv2d_tile_n(int64_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t r, int32_t s,
+                           int32_t stride, int32_t pad);
+
+/* The stem: Conv2d(3, 64, 7, stride 2, pad 3) + folded BatchNorm + ReLU + MaxPool2d(3, stride 2, pad 1) in one
+ * kernel; the Hc x Wc x 64 pre-pool map never goes to memory.  img fp32 NCHW [B][3][H][W], H, W >= 7 (smaller:
+ * HCIR_ERR_UNSUPPORTED); out fp16 NHWC [B][Hp][Wp][64] with Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1.
+ * The image is rounded to fp16 for the MFMA (as the weights are); conv * scale + bias and ReLU are fp32, the max is
+ * taken over the fp32 values of the window's positions INSIDE the conv map (padding is excluded, not zero) and
+ * rounded once.  w_packed fp16 [10][2][64][8]: element j of lane l of MFMA step kk, n tile nt is
+ * W[nt * 32 + (l & 31)][k = 16 kk + 8 (l >> 5) + j] with k = (c * 7 + ky) * 7 + kx, zero for k >= 147
+ * (hcir.resnet_engine.pack_stem_weight). */
+int hcir_resnet_stem(const float* img, int64_t b, int32_t h, int32_t w, const void* w_packed, const float* scale,
+                     const float* bias, void* out, void* stream);
+
+/* AdaptiveAvgPool2d((1, 1)) + flatten: out[b][c] = mean over H*W of x fp16 [B][H][W][C], fp32 out [B][C].
+ * fp32 compensated summation in index order, no atomics: the result does not depend on the launch.  l2_normalize != 0:
+ * each row is divided by max(||row||_2, eps) (F.normalize, HP/src/classification_engine.py:50, eps 1e-12). */
+int hcir_avgpool_nhwc_f16(const void* x, int64_t b, int32_t h, int32_t w, int32_t c, int l2_normalize, float eps,
+                          float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
