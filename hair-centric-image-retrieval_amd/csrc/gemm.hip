@@ -5,13 +5,18 @@
 // HP/src/main_backbone.py:554) and Conv2d(3,768,16,16) patch embedding
 // (HP/src/main_backbone.py:543; HP/src/models_vit.py:42,48).
 //
-// Two kernels (launch_gemm picks):
+// Three kernels (launch_gemm / launch_gemm_big pick):
 //   * gemm_f16_big_kernel — M >= 1024, N % 256 == 0, K % 64 == 0 (every encoder GEMM of the benchmark):
 //     persistent 256(n) x 256(m) x 64(k) tiles, 8 waves of 128 x 64 (MFMA 16x16x32), two 64 KB LDS slots filled
 //     by LDS-DMA, LDS-transposed full-line epilogues incl. the LayerNorm fold (hcir_gemm_f16_fused);
+//   * gemm_f16_mid_kernel — the same shapes when the 256 x 256 tiles fill the 256 CUs badly (small M, the rows
+//     behind the last whole round of tiles): persistent 128(n) x 192(m) x 64(k) tiles, 4 waves of 64 x 96, two
+//     workgroups per CU; bit-identical results;
 //   * gemm_f16_kernel — everything else (small M, ragged N / K): the sim_core.h tile engine with W rows on the
 //     MFMA row index and activation rows on the column index (a lane owns ONE activation row and receives the
 //     output features in groups of 4 registers), workgroup tile 128 x 128 x 64, 4 waves of 2x2 MFMA 32x32x16.
+// The two persistent kernels differ in geometry (G256 / GMid) and in their MFMA loops only: they share ONE stage
+// issuer (GemmStages<G>) and ONE LDS-transposing epilogue (gemm_epilogue_lds).
 #include "sim_core.h"
 #include "act.h"
 #include <stdlib.h>
@@ -158,9 +163,16 @@ __device__ __forceinline__ float sum8_dpp(float v) {
   return v;
 }
 
-template <int EPI, bool FULL>
-__device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, const WaveAcc& acc, char* region,
-                                                          int64_t m0w, int nbase, int lane) {
+
+// LDS-transposing epilogue of both persistent kernels, for a 16x16x32 accumulator block acc[NTW n-tiles][MTH m-tiles
+// from mt0, of MTT]: (16 NTW) features x (16 MTH) rows, transposed through `region` (16 MTH rows x 128 B, private to
+// the wave) one 128-B output line per row and pass.  The 256 x 256 kernel instantiates it at <8, 4, 4> (its whole
+// 128 x 64 wave tile), the 128 x 192 kernel at <4, 6, 3> (one 48-row half of its 64 x 96 wave tile): ONE body, so
+// the two kernels round the same fp32 value once and store the same bits (test_gemm_big_and_mid_kernels_same_bits;
+// the tail split of launch_gemm_big sends rows of one matrix through both).
+template <int EPI, bool FULL, int NTW, int MTT, int MTH>
+__device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const f32x4 (&acc)[NTW][MTT], int mt0,
+                                                       char* region, int64_t m0w, int nbase, int lane) {
   constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kGelu = (EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kResidH = (EPI == HCIR_EPI_BIAS_RESID_F16 || EPI == EPI_RESID_F16_STATS);
@@ -168,7 +180,11 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   constexpr bool kF16 = (EPI == HCIR_EPI_BIAS_F16 || kGelu || kLn ||
                          EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH || kDual);
   constexpr bool kAffine = (EPI == HCIR_EPI_AFFINE_RELU_F16 || EPI == HCIR_EPI_AFFINE_F32);
-  constexpr int NPASS = kF16 ? 2 : 4;  // 64 or 32 output features (128 B) per pass
+  constexpr int FPP = kF16 ? 64 : 32;      // output features (128 B) per pass
+  constexpr int NPASS = NTW * 16 / FPP;
+  constexpr int NIT = MTH * 2;             // groups of 8 rows
+  constexpr int UB = (NIT % 4 == 0) ? 4 : 3;  // rows requested / stored back to back
+  static_assert(NIT % UB == 0 && (NTW * 16) % FPP == 0, "geometry");
   const int rrow = lane >> 3, rchunk = lane & 7;
 
   // fp16 outputs: bias / scale / activation / LayerNorm fold run on the ACCUMULATOR side, in fp32, before the one
@@ -177,12 +193,12 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   // time: five VALU instructions per output pair instead of two, and the epilogue phase of a tile is VALU / LDS-issue
   // time (in-kernel stamps: 4.6 us per qkv tile, 8.6 us per fc1 tile).
   constexpr bool kScaleA = kF16 && (EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH);
-  f32x4 biasA[kF16 ? 8 : 1], scaleA[kScaleA ? 8 : 1];
+  f32x4 biasA[kF16 ? NTW : 1], scaleA[kScaleA ? NTW : 1];
   bool has_scale = false;
   if constexpr (kF16) {
     has_scale = kScaleA && (EPI == HCIR_EPI_AFFINE_RELU_F16 || g.scale != nullptr);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
+    for (int t = 0; t < NTW; ++t) {
       const int n = nbase + 16 * t + 4 * (lane >> 4);
       biasA[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (g.bias) biasA[t] = *reinterpret_cast<const f32x4*>(g.bias + n);
@@ -201,7 +217,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
     if constexpr (kF16) break;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      const int n = nbase + pass * (kF16 ? 64 : 32) + rchunk * (kF16 ? 8 : 4) + 4 * j;
+      const int n = nbase + pass * FPP + rchunk * (kF16 ? 8 : 4) + 4 * j;
       bias[pass][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       scale[pass][j] = (f32x4){1.f, 1.f, 1.f, 1.f};
       if (g.bias) bias[pass][j] = *reinterpret_cast<const f32x4*>(g.bias + n);
@@ -211,19 +227,19 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   }
   // LayerNorm fold, out = rstd[m] (acc - mean[m] c1[n]) + bias[n], all on the accumulator side in fp32: rounding the
   // raw accumulator first loses the result under the cancellation acc - mean c1 when |mean| >> std (measured: 20x
-  // the error at mean/std = 50, 2.4x at 5; equal at 0).  mean / rstd of the 4 rows this lane owns, c1 of its features.
-  float ln_rs[4], ln_mean[4];
-  f32x4 c1a[8];
+  // the error at mean/std = 50, 2.4x at 5; equal at 0).  mean / rstd of the MTH rows this lane owns, c1 of its features.
+  float ln_rs[MTH], ln_mean[MTH];
+  f32x4 c1a[NTW];
   if constexpr (kLn) {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
+    for (int mt = 0; mt < MTH; ++mt) {
       int64_t mm = m0w + 16 * mt + (lane & 15);
       mm = mm < g.m ? mm : g.m - 1;
       ln_mean[mt] = g.ln_stats[2 * mm];
       ln_rs[mt] = g.ln_stats[2 * mm + 1];
     }
 #pragma unroll
-    for (int t = 0; t < 8; ++t) c1a[t] = *reinterpret_cast<const f32x4*>(g.ln_c1 + nbase + 16 * t + 4 * (lane >> 4));
+    for (int t = 0; t < NTW; ++t) c1a[t] = *reinterpret_cast<const f32x4*>(g.ln_c1 + nbase + 16 * t + 4 * (lane >> 4));
   }
   // (Issuing the next tile's first stage from here, behind these constant loads and with vmcnt(8), instead of from
   // inside the tile's last k-step - so that this wait does not sit out the rest of the stage's round trip - was
@@ -231,15 +247,15 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (kLn) {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(ln_rs[mt]));
+    for (int mt = 0; mt < MTH; ++mt) asm volatile("" : "+v"(ln_rs[mt]));
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(ln_mean[mt]));
+    for (int mt = 0; mt < MTH; ++mt) asm volatile("" : "+v"(ln_mean[mt]));
 #pragma unroll
-    for (int t = 0; t < 8; ++t) launder(c1a[t]);
+    for (int t = 0; t < NTW; ++t) launder(c1a[t]);
   }
   if constexpr (kF16) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
+    for (int t = 0; t < NTW; ++t) {
       launder(biasA[t]);
       if constexpr (kScaleA) launder(scaleA[t]);
     }
@@ -263,7 +279,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
     // ---- accumulators -> LDS (lane = output row m, registers = features n)
     const int r16 = lane & 15, q16 = lane >> 4;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
+    for (int mt = 0; mt < MTH; ++mt) {
       const int row = mt * 16 + r16;
       if constexpr (kF16) {
 #pragma unroll
@@ -273,7 +289,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
           float xs[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float x = acc.a[nt][mt][e];
+            float x = acc[nt][mt0 + mt][e];
             const float bb = biasA[nt][e];
             if constexpr (kLn) {
               // out = rstd[m] (acc - mean[m] c1[n]) + bias[n]: centered first (cancellation when |mean| >> std)
@@ -305,7 +321,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
         for (int q = 0; q < 2; ++q) {   // 32 features per pass = 2 n-tiles of 16
           const int nt = 2 * pass + q;
           const int chunk = 4 * q + q16;
-          *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = acc.a[nt][mt];
+          *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = acc[nt][mt0 + mt];
         }
       }
     }
@@ -313,17 +329,17 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
     if constexpr (kF16) {
       const int n = nbase + pass * 64 + rchunk * 8;
 #pragma unroll
-      for (int it0 = 0; it0 < 8; it0 += 4) {
-        // fp16 residual: the four old rows of a group are requested back to back (counted waits).  (Not reading them
+      for (int it0 = 0; it0 < NIT; it0 += UB) {
+        // fp16 residual: the old rows of a group are requested back to back (counted waits).  (Not reading them
         // at all - a timing ablation, wrong results - took proj 237 -> 201 us, fc2 709 -> 686 us at batch 880.
         // Requesting all sixteen pieces of the tile during its last k-step instead (registers freed by keeping the
         // bias in LDS; bit-identical) made proj 3.5 % and fc2 1.3 % SLOWER: the 128 KB a tile reads here go through
         // the same L2 -> CU path as its stages, and that path is what bounds the main loop -
         // profiles/r4_gemm_resid_prefetch.txt)
-        f16x8 oldh[4];
+        f16x8 oldh[UB];
         if constexpr (kResidH) {
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
+          for (int u = 0; u < UB; ++u) {
             const int64_t mm = m0w + (it0 + u) * 8 + rrow;
 #pragma unroll
             for (int e = 0; e < 8; ++e) oldh[u][e] = (_Float16)0.f;
@@ -332,7 +348,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
           }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < UB; ++u) {
           const int row = (it0 + u) * 8 + rrow;
           const f16x8 v = *reinterpret_cast<const f16x8*>(region + row * 128 + ((rchunk ^ (row & 7)) << 4));
           // the image already holds the finished fp16 values; the fp16 residual is one packed add per pair (the
@@ -378,12 +394,12 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
       const int n = nbase + pass * 32 + rchunk * 4;
       const f32x4 b = bias[pass][0], sc = scale[pass][0];
 #pragma unroll
-      for (int it0 = 0; it0 < 8; it0 += 4) {
-        // the four old-value loads of a group are issued back to back, so their waits are COUNTED
+      for (int it0 = 0; it0 < NIT; it0 += UB) {
+        // the old-value loads of a group are issued back to back, so their waits are COUNTED
         // (vmcnt(3), ...) and the stores of the previous group stay in flight
-        f32x4 oldv[4];
+        f32x4 oldv[UB];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < UB; ++u) {
           const int64_t mm = m0w + (it0 + u) * 8 + rrow;
           oldv[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
           if constexpr (EPI == HCIR_EPI_BIAS_RESID_F32) {
@@ -392,7 +408,7 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
           }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < UB; ++u) {
           const int row = (it0 + u) * 8 + rrow;
           const int64_t mm = m0w + row;
           f32x4 v = *reinterpret_cast<const f32x4*>(region + row * 128 + ((rchunk ^ (row & 7)) << 4));
@@ -413,23 +429,22 @@ __device__ __forceinline__ void gemm_epilogue256_lds_impl(const GemmArgs& g, con
   }
 }
 
-// Epilogue of the 256 x 256 kernel: every wave transposes its 128(n) x 64(m) accumulator tile
-// through a private 8 KB piece of the LDS slot that the tile's last k-step has just released,
-// 128 B of one output row at a time, so that a lane ends up with 16 contiguous bytes of ONE output
-// row and 8 lanes cover a whole 128-B line (the direct layout gives every lane 8 B of a different
-// row: 1.6-1.9 TB/s effective on the fp16 outputs).  The fp32 outputs take bias / residual on the
-// row-contiguous side.  [64 rows][128 B] image, 16-B chunks XOR-swizzled with row & 7.
-// Full tiles (all 64 rows of the wave inside M) take a branch-free path.
-template <int EPI>
-__device__ __forceinline__ void gemm_epilogue256_lds(const GemmArgs& g, const WaveAcc& acc,
-                                                     char* region, int64_t m0w, int nbase, int lane) {
+// Every wave transposes its accumulator block through a private piece of the LDS slot that the tile's last k-step
+// has just released, 128 B of one output row at a time, so that a lane ends up with 16 contiguous bytes of ONE
+// output row and 8 lanes cover a whole 128-B line (the direct layout gives every lane 8 B of a different row:
+// 1.6-1.9 TB/s effective on the fp16 outputs).  The fp32 outputs take bias / residual on the row-contiguous side.
+// [16 MTH rows][128 B] image, 16-B chunks XOR-swizzled with row & 7.
+// Full blocks (all 16 MTH rows inside M) take a branch-free path.
+template <int EPI, int NTW, int MTT, int MTH>
+__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs& g, const f32x4 (&acc)[NTW][MTT], int mt0,
+                                                  char* region, int64_t m0w, int nbase, int lane) {
   // opaque lane id: the epilogue's ~60 loop-invariant LDS / global addresses all derive from it, so hipcc
   // cannot hoist them out of the persistent tile loop into long-lived registers
   asm volatile("" : "+v"(lane));
-  if (m0w + 64 <= g.m)
-    gemm_epilogue256_lds_impl<EPI, true>(g, acc, region, m0w, nbase, lane);
+  if (m0w + 16 * MTH <= g.m)
+    gemm_epilogue_lds_impl<EPI, true, NTW, MTT, MTH>(g, acc, mt0, region, m0w, nbase, lane);
   else
-    gemm_epilogue256_lds_impl<EPI, false>(g, acc, region, m0w, nbase, lane);
+    gemm_epilogue_lds_impl<EPI, false, NTW, MTT, MTH>(g, acc, mt0, region, m0w, nbase, lane);
 }
 
 template <int EPI, bool GLDS>
@@ -486,21 +501,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(GemmArgs g, int tiles_
   gemm_epilogue<EPI>(g, acc, m0, n0, wave_n, wave_m, lane);
 }
 
-// ---------------------------------------------------------------------------
-// Big-tile GEMM: 256(n) x 256(m) per workgroup, 8 waves as 2(n) x 4(m), each wave
-// 128(n) x 64(m) = 8 x 4 MFMA 16x16x32 tiles (128 accumulator registers), persistent
-// over tiles.  Why this geometry (measured, DESIGN.md "GEMM ablation"): with 64 x 64
-// wave tiles the LDS pipe (fragment reads + DMA writes, ~170 B/clk of 256) is the limit
-// and compute alone tops out at 1.24 PF; 128 x 64 wave tiles cut LDS reads per MFMA by
-// 25 % and L2->LDS traffic per flop by 2x.  Rows stay 128 B (BK = 64): with 64-B row
-// pieces (BK = 32) the LDS-DMA path moved 2.2-2.8x fewer bytes per second.
-//
-// A stage is 512 rows x 128 B = 64 KB; two slots.  Step s: wait for stage s (vmcnt(0)),
-// barrier, then the eight DMA pieces of stage s+1 are issued between the fragment reads
-// and the MFMAs of the FIRST 32-k substep, so that they have the rest of the step (32+
-// MFMAs per wave) to land.  Stages run on across tile boundaries: the next tile's first
-// stage flies under the epilogue.  Requires K % 64 == 0.
-// ---------------------------------------------------------------------------
 #ifdef HCIR_DIAG_GSTAMPS
 // diagnostic build only (tools/diag_gemm_stamps.py): 100 MHz wall-clock stamps around the SECOND tile of every
 // workgroup of the 256 x 256 kernel
@@ -522,47 +522,79 @@ constexpr int kGemmNGroupWide = 6;  // group size when it divides tiles_n (fc1: 
                                     // then fetched by two XCD sets instead of four (PMC: fc1 reads x5.3 -> see DESIGN);
                                     // time flat against 3 (profiles/r3_diag_ab_gemm_ngroup.txt), fabric bytes -20 %
 
+// Geometry of a persistent kernel: NT threads as WAVES_N x WAVES_M waves on a TN(n) x TM(m) tile; a stage is TN W
+// rows then TM activation rows of 128 B (BK = 64), filled by NLOAD 16-B LDS-DMA pieces per thread, the first NW of
+// them W rows (NT * NW == TN * 8: no piece straddles the two operands).
 struct G256 {
   static constexpr int NT = 512;
-  static constexpr int ROWS = 512;               // 256 W rows (n) then 256 activation rows (m)
-  static constexpr int STAGE_BYTES = ROWS * 128; // 64 KB
-  static constexpr int NLOAD = ROWS * 8 / NT;    // 16-B pieces per thread per stage = 8
+  static constexpr int TN = 256, TM = 256;
+  static constexpr int WAVES_N = 2, WAVES_M = 4;   // wave tile 128(n) x 64(m)
+  static constexpr int ROWS = TN + TM;             // 256 W rows (n) then 256 activation rows (m)
+  static constexpr int STAGE_BYTES = ROWS * 128;   // 64 KB
+  static constexpr int NLOAD = ROWS * 8 / NT;      // 16-B pieces per thread per stage = 8 (4 W + 4 activation)
+  static constexpr int NW = TN * 8 / NT;           // 4
+  static constexpr bool N_GROUPED = true;          // tile order: kGemmNGroup / kGemmNGroupWide
+  static_assert(WAVES_N * WAVES_M * 64 == NT && NT * NW == TN * 8, "geometry");
 };
 
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int tiles_n, int tiles_m) {
-  __shared__ __attribute__((aligned(16))) char lds[2 * G256::STAGE_BYTES];
+struct GMid {
+  static constexpr int NT = 256;
+  static constexpr int TN = 128, TM = 192;
+  static constexpr int WAVES_N = 2, WAVES_M = 2;   // wave tile 64(n) x 96(m), two 48-row halves
+  static constexpr int ROWS = TN + TM;             // 128 W rows (n) then 192 activation rows (m)
+  static constexpr int STAGE_BYTES = ROWS * 128;   // 40 KB
+  static constexpr int NLOAD = ROWS * 8 / NT;      // 10 pieces of 16 B per thread per stage (4 W + 6 activation)
+  static constexpr int NW = TN * 8 / NT;           // 4
+  static constexpr bool N_GROUPED = false;         // tile order: n fastest
+  static_assert(WAVES_N * WAVES_M * 64 == NT && NT * NW == TN * 8, "geometry");
+};
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_n = wave >> 2, wave_m = wave & 3;
+// Stage issuer of both persistent kernels: which tiles this workgroup owns, where a tile lies, and the LDS-DMA
+// pieces of the next stage to issue (stages run on across tile boundaries).  The kernels keep their own MFMA loops
+// and decide where in them the pieces go out.
+template <class G>
+struct GemmStages {
+  // State first, configuration after it, `issue_kc` ... `soff` in this order: hipcc numbers the loop-carried values
+  // in member order, and every other order measurably reschedules the 256 x 256 kernel (tools/cmp_device_asm.py:
+  // instruction counts move by 1-2 in all of its epilogues).
+  int issue_kc = 0, issue_ti = 0;  // next stage to issue
+  const char* wbase = nullptr;
+  const char* abase = nullptr;
+  // per-thread DMA source offsets of the tile being issued (row + swizzled chunk), in bytes from the
+  // tile's W / activation origin: 32-bit VGPR offsets on wave-uniform 64-bit bases (global saddr mode)
+  uint32_t soff[G::NLOAD];
+  const GemmArgs& g;
+  char* const lds;
+  const int tiles_n, tiles_m, tid;
   const int ntiles = tiles_n * tiles_m;
   const int nkc = g.k / 64;
   const int my_tiles =
       (int)blockIdx.x < ntiles ? (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
   const int nsteps = my_tiles * nkc;
 
-  auto tile_origin = [&](int ti, int& n0, int64_t& m0) {
-    const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
-    // n-grouped order: the W panels of one group of n-tiles stay in the XCD's L2 while every m-tile streams past
-    // them (a W set wider than the 4 MB L2 - fc1: 12 panels, 4.7 MB - is otherwise re-fetched for every row of tiles)
-    const int ngrp = (tiles_n % kGemmNGroupWide == 0 && tiles_n > kGemmNGroupWide) ? kGemmNGroupWide : kGemmNGroup;
-    if (tiles_n % ngrp == 0 && tiles_n > ngrp) {
-      const int per = ngrp * tiles_m;
-      const int grp = t / per, rem = t - grp * per;
-      n0 = (grp * ngrp + rem % ngrp) * 256;
-      m0 = (int64_t)(rem / ngrp) * 256;
-      return;
-    }
-    n0 = (t % tiles_n) * 256;
-    m0 = (int64_t)(t / tiles_n) * 256;
-  };
+  __device__ __forceinline__ GemmStages(const GemmArgs& g_, char* lds_, int tiles_n_, int tiles_m_, int tid_)
+      : g(g_), lds(lds_), tiles_n(tiles_n_), tiles_m(tiles_m_), tid(tid_) {}
 
-  // per-thread DMA source offsets of the tile being issued (row + swizzled chunk), in bytes from the
-  // tile's W / activation origin: 32-bit VGPR offsets on wave-uniform 64-bit bases (global saddr mode)
-  uint32_t soff[G256::NLOAD];
-  const char* wbase = nullptr;
-  const char* abase = nullptr;
-  auto set_sources = [&](int t_i) {
+  // origin of this workgroup's ti-th tile
+  __device__ __forceinline__ void tile_origin(int ti, int& n0, int64_t& m0) const {
+    const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
+    if constexpr (G::N_GROUPED) {
+      // n-grouped order: the W panels of one group of n-tiles stay in the XCD's L2 while every m-tile streams past
+      // them (a W set wider than the 4 MB L2 - fc1: 12 panels, 4.7 MB - is otherwise re-fetched for every row of tiles)
+      const int ngrp = (tiles_n % kGemmNGroupWide == 0 && tiles_n > kGemmNGroupWide) ? kGemmNGroupWide : kGemmNGroup;
+      if (tiles_n % ngrp == 0 && tiles_n > ngrp) {
+        const int per = ngrp * tiles_m;
+        const int grp = t / per, rem = t - grp * per;
+        n0 = (grp * ngrp + rem % ngrp) * G::TN;
+        m0 = (int64_t)(rem / ngrp) * G::TM;
+        return;
+      }
+    }
+    n0 = (t % tiles_n) * G::TN;
+    m0 = (int64_t)(t / tiles_n) * G::TM;
+  }
+
+  __device__ __forceinline__ void set_sources(int t_i) {
     int n0;
     int64_t m0;
     tile_origin(t_i, n0, m0);
@@ -574,45 +606,76 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
     int otid = tid;
     asm volatile("" : "+v"(otid));
 #pragma unroll
-    for (int i = 0; i < G256::NLOAD; ++i) {
-      const int piece = otid + G256::NT * i;
+    for (int i = 0; i < G::NLOAD; ++i) {
+      const int piece = otid + G::NT * i;
       const int row = piece >> 3, chunk = (piece & 7) ^ ((row >> 1) & 7);
-      if (row < 256) {
+      if (row < G::TN) {
         const int nr = n0 + row > g.n - 1 ? g.n - 1 - n0 : row;
         soff[i] = (uint32_t)(((int64_t)nr * g.ldw + chunk * 8) * 2);
       } else {
-        int64_t mr = row - 256;
+        int64_t mr = row - G::TN;
         mr = m0 + mr > g.m - 1 ? g.m - 1 - m0 : mr;
         soff[i] = (uint32_t)((mr * g.lda + chunk * 8) * 2);
       }
     }
-  };
-  int issue_ti = 0, issue_kc = 0;  // next stage to issue
-  auto issue_piece = [&](int slot, int i) {
-    // pieces 0..3 are W rows, 4..7 activation rows (i is a constant after unrolling).  Default cache policy
+  }
+
+  __device__ __forceinline__ void issue_piece(int slot, int i) const {
+    // pieces 0..NW-1 are W rows, the rest activation rows (i is a constant after unrolling).  Default cache policy
     // on both operands: `nt` (aux 2) on the activation rows measured +-1 %, on the W rows -9..-13 %
     // (every CU of an XCD re-reads them from L2).  The transfer is issued outside the compiler's view (common.h
     // lds_dma16): +1.3 % over the layer against __builtin_amdgcn_global_load_lds (qkv +2.6 %)
-    lds_dma16((i < 4 ? wbase : abase) + issue_kc * 128, soff[i],
-              lds_addr(lds) + slot * G256::STAGE_BYTES + ((tid & ~63) + G256::NT * i) * 16);
-  };
-  auto issue_advance = [&]() {
+    lds_dma16((i < G::NW ? wbase : abase) + issue_kc * 128, soff[i],
+              lds_addr(lds) + slot * G::STAGE_BYTES + ((tid & ~63) + G::NT * i) * 16);
+  }
+
+  __device__ __forceinline__ void issue_advance() {
     if (++issue_kc == nkc) {
       issue_kc = 0;
       ++issue_ti;
       if (issue_ti < my_tiles) set_sources(issue_ti);
     }
-  };
+  }
+
+  // the whole first stage, into slot 0
+  __device__ __forceinline__ void issue_first() {
+    if (nsteps > 0) {
+      set_sources(0);
+#pragma unroll
+      for (int i = 0; i < G::NLOAD; ++i) issue_piece(0, i);
+      issue_advance();
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// Big-tile GEMM: 256(n) x 256(m) per workgroup, 8 waves as 2(n) x 4(m), each wave
+// 128(n) x 64(m) = 8 x 4 MFMA 16x16x32 tiles (128 accumulator registers), persistent
+// over tiles.  Why this geometry (measured, DESIGN.md "GEMM ablation"): with 64 x 64
+// wave tiles the LDS pipe (fragment reads + DMA writes, ~170 B/clk of 256) is the limit
+// and compute alone tops out at 1.24 PF; 128 x 64 wave tiles cut LDS reads per MFMA by
+// 25 % and L2->LDS traffic per flop by 2x.  Rows stay 128 B (BK = 64): with 64-B row
+// pieces (BK = 32) the LDS-DMA path moved 2.2-2.8x fewer bytes per second.
+//
+// A stage is 512 rows x 128 B = 64 KB; two slots.  Step s: wait for stage s (vmcnt(0)),
+// barrier, then the eight DMA pieces of stage s+1 are issued between the fragment reads
+// and the MFMAs of the FIRST 32-k substep, so that they have the rest of the step (32+
+// MFMAs per wave) to land.  Stages run on across tile boundaries: the next tile's first
+// stage flies under the epilogue.  Requires K % 64 == 0.
+// ---------------------------------------------------------------------------
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int tiles_n, int tiles_m) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * G256::STAGE_BYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_n = wave / G256::WAVES_M, wave_m = wave % G256::WAVES_M;
+  GemmStages<G256> stg(g, lds, tiles_n, tiles_m, tid);
+  const int nkc = stg.nkc, nsteps = stg.nsteps;
 
   WaveAcc acc;
   acc.zero();
 
-  if (nsteps > 0) {
-    set_sources(0);
-#pragma unroll
-    for (int i = 0; i < G256::NLOAD; ++i) issue_piece(0, i);
-    issue_advance();
-  }
+  stg.issue_first();
 
   int kc = 0, ti = 0;
   for (int step = 0; step < nsteps; ++step) {
@@ -638,7 +701,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       u32x4 bf[4];
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
-        bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(256 + wave_m * 64 + mt * 16 + r16, chunk));
+        bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(G256::TN + wave_m * 64 + mt * 16 + r16, chunk));
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         u32x4 af[4];
@@ -648,7 +711,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
               st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
         if (do_issue && ks2 == 0) {  // the eight DMA pieces of stage step+1 in the first 32-k substep
 #pragma unroll
-          for (int i = 0; i < 4; ++i) issue_piece(islot, 4 * half + i);
+          for (int i = 0; i < 4; ++i) stg.issue_piece(islot, 4 * half + i);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -659,20 +722,21 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
                 0, 0, 0);
       }
     }
-    if (do_issue) issue_advance();
+    if (do_issue) stg.issue_advance();
     HCIR_GSTAMP(ti == 2 && kc == 0, 5);
 
     if (++kc == nkc) {
       int n0;
       int64_t m0;
-      tile_origin(ti, n0, m0);
+      stg.tile_origin(ti, n0, m0);
       HCIR_GSTAMP(ti == 1, 1);
       // all waves are done reading slot step&1 (their MFMAs have consumed it) after this barrier;
-      // the slot stays free until the DMA of stage step+2 is issued behind the next step's barrier
+      // the slot stays free until the DMA of stage step+2 is issued behind the next step's barrier.
+      // Per wave a private 8 KB piece of it: 64 rows x 128 B.
       __builtin_amdgcn_s_barrier();
       HCIR_GSTAMP(ti == 1, 2);
-      gemm_epilogue256_lds<EPI>(g, acc, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
-                                m0 + wave_m * 64, n0 + wave_n * 128, lane);
+      gemm_epilogue_lds<EPI, 8, 4, 4>(g, acc.a, 0, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
+                                      m0 + wave_m * 64, n0 + wave_n * 128, lane);
       HCIR_GSTAMP(ti == 1, 3);
       acc.zero();
       kc = 0;
@@ -680,7 +744,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       // the DMA source offsets of the tile being issued are RE-DERIVED here instead of living through the epilogue:
       // the dual-output variant spilled them, and its reload made the compiler put vmcnt(0) in front of every DMA
       // group of the main loop (MFMA busy 39 % against 57 % for the other variants)
-      if (issue_ti < my_tiles) set_sources(issue_ti);
+      if (stg.issue_ti < stg.my_tiles) stg.set_sources(stg.issue_ti);
     }
   }
 }
@@ -695,302 +759,17 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
 // themselves: while one transposes and stores, the other owns the matrix pipes, and the output bursts of a CU
 // (and of the chip) spread over the tile time.  Price: 1.67 x the L2->LDS bytes per flop of the 256^2 tile and
 // 10 instead of 12 fragment reads per 24 instead of 32 MFMAs (+11 % LDS reads per MFMA).
-// Same staging (LDS-DMA, 128-B rows, XOR swizzle), same MFMA operand maps and k order as the 256^2 kernel:
-// results are bit-identical to it.  Requires K % 64 == 0, N % 128 == 0.
+// Same staging (GemmStages: LDS-DMA, 128-B rows, XOR swizzle), same MFMA operand maps and k order as the 256^2
+// kernel, the same epilogue (gemm_epilogue_lds): results are bit-identical to it.  Requires K % 64 == 0, N % 128 == 0.
 // ---------------------------------------------------------------------------
-struct GMid {
-  static constexpr int NT = 256;
-  static constexpr int TN = 128, TM = 192;
-  static constexpr int ROWS = TN + TM;             // 128 W rows (n) then 192 activation rows (m)
-  static constexpr int STAGE_BYTES = ROWS * 128;   // 40 KB
-  static constexpr int NLOAD = ROWS * 8 / NT;      // 10 pieces of 16 B per thread per stage (4 W + 6 activation)
-  static constexpr int NW = TN * 8 / NT;           // 4
-};
-
-// Epilogue of a 16x16x32 accumulator block acc[NTW n-tiles][.. MTH m-tiles from mt0]: (16 NTW) features x (16 MTH)
-// rows, transposed through `region` (16 MTH rows x 128 B, private to the wave) one 128-B output line per row and
-// pass; the arithmetic of gemm_epilogue256_lds_impl (same order of operations -> same bits).
-template <int EPI, bool FULL, int NTW, int MTT, int MTH>
-__device__ __forceinline__ void gemm_epilogue16_lds_impl(const GemmArgs& g, const f32x4 (&acc)[NTW][MTT], int mt0,
-                                                         char* region, int64_t m0h, int nbase, int lane) {
-  constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
-  constexpr bool kGelu = (EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_GELU_F16);
-  constexpr bool kResidH = (EPI == HCIR_EPI_BIAS_RESID_F16 || EPI == EPI_RESID_F16_STATS);
-  constexpr bool kF16 = (EPI == HCIR_EPI_BIAS_F16 || kGelu || kLn || EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH);
-  constexpr bool kAffine = (EPI == HCIR_EPI_AFFINE_RELU_F16 || EPI == HCIR_EPI_AFFINE_F32);
-  constexpr int FPP = kF16 ? 64 : 32;      // features per pass = one 128-B line per row
-  constexpr int NPASS = NTW * 16 / FPP;
-  constexpr int NB = kF16 ? 2 : 1;
-  constexpr int NIT = MTH * 2;             // groups of 8 rows
-  constexpr int UB = (NIT % 4 == 0) ? 4 : 3;
-  static_assert(NIT % UB == 0 && (NTW * 16) % FPP == 0, "geometry");
-  const int rrow = lane >> 3, rchunk = lane & 7;
-  const int r16 = lane & 15, q16 = lane >> 4;
-
-  f32x4 bias[NPASS][NB], scale[NPASS][NB];
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    if constexpr (kF16) break;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int n = nbase + pass * FPP + rchunk * (kF16 ? 8 : 4) + 4 * j;
-      bias[pass][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      scale[pass][j] = (f32x4){1.f, 1.f, 1.f, 1.f};
-      if (g.bias) bias[pass][j] = *reinterpret_cast<const f32x4*>(g.bias + n);
-      if (kAffine || (EPI == HCIR_EPI_BIAS_RESID_F32 && g.scale))
-        scale[pass][j] = *reinterpret_cast<const f32x4*>(g.scale + n);
-    }
-  }
-  // fp16 outputs: bias / scale / activation / LayerNorm fold run on the ACCUMULATOR side, in fp32, before the ONE
-  // rounding to fp16, exactly as in gemm_epilogue256_lds_impl (the earlier form rounded the raw accumulator first:
-  // a second rounding, one fp16 ulp away from the 256 x 256 kernel's result)
-  constexpr bool kScaleA = kF16 && (EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH);
-  f32x4 biasA[kF16 ? NTW : 1], scaleA[kScaleA ? NTW : 1];
-  if constexpr (kF16) {
-    const bool has_scale = kScaleA && (EPI == HCIR_EPI_AFFINE_RELU_F16 || g.scale != nullptr);
-#pragma unroll
-    for (int t = 0; t < NTW; ++t) {
-      const int n = nbase + 16 * t + 4 * q16;
-      biasA[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (g.bias) biasA[t] = *reinterpret_cast<const f32x4*>(g.bias + n);
-      if constexpr (kScaleA) {
-        scaleA[t] = (f32x4){1.f, 1.f, 1.f, 1.f};
-        if (has_scale) scaleA[t] = *reinterpret_cast<const f32x4*>(g.scale + n);
-      }
-    }
-  }
-  float ln_rs[MTH], ln_mean[MTH];
-  f32x4 c1a[NTW];
-  if constexpr (kLn) {
-#pragma unroll
-    for (int mt = 0; mt < MTH; ++mt) {
-      int64_t mm = m0h + 16 * mt + r16;
-      mm = mm < g.m ? mm : g.m - 1;
-      ln_mean[mt] = g.ln_stats[2 * mm];
-      ln_rs[mt] = g.ln_stats[2 * mm + 1];
-    }
-#pragma unroll
-    for (int t = 0; t < NTW; ++t) c1a[t] = *reinterpret_cast<const f32x4*>(g.ln_c1 + nbase + 16 * t + 4 * q16);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (kLn) {
-#pragma unroll
-    for (int mt = 0; mt < MTH; ++mt) {
-      asm volatile("" : "+v"(ln_rs[mt]));
-      asm volatile("" : "+v"(ln_mean[mt]));
-    }
-#pragma unroll
-    for (int t = 0; t < NTW; ++t) launder(c1a[t]);
-  }
-  if constexpr (kF16) {
-#pragma unroll
-    for (int t = 0; t < NTW; ++t) {
-      launder(biasA[t]);
-      if constexpr (kScaleA) launder(scaleA[t]);
-    }
-  }
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    if constexpr (kF16) break;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      launder(bias[pass][j]);
-      launder(scale[pass][j]);
-    }
-  }
-
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    // ---- accumulators -> LDS (lane = output row m, registers = features n)
-#pragma unroll
-    for (int mt = 0; mt < MTH; ++mt) {
-      const int row = mt * 16 + r16;
-      if constexpr (kF16) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int nt = 4 * pass + q;
-          f16x4 o;
-          float xs[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float x = acc[nt][mt0 + mt][e];
-            const float bb = biasA[nt][e];
-            if constexpr (kLn) {
-              // out = rstd[m] (acc - mean[m] c1[n]) + bias[n]: centered first (cancellation when |mean| >> std)
-              x = __builtin_fmaf(ln_rs[mt], __builtin_fmaf(-ln_mean[mt], c1a[nt][e], x), bb);
-            } else if constexpr (EPI == HCIR_EPI_AFFINE_RELU_F16) {
-              x = fmaxf(__builtin_fmaf(x, scaleA[nt][e], bb), 0.f);
-            } else if constexpr (kResidH) {
-              x = scaleA[nt][e] * (x + bb);
-            } else {
-              x += bb;
-            }
-            xs[e] = x;
-          }
-          if constexpr (kGelu) {
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-              const gelu_f32x2 y = gelu_erf2((gelu_f32x2){xs[e], xs[e + 1]});
-              xs[e] = y[0];
-              xs[e + 1] = y[1];
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)xs[e];
-          const int chunk = 2 * q + (q16 >> 1);
-          *reinterpret_cast<f16x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4) + 8 * (q16 & 1)) = o;
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int nt = 2 * pass + q;
-          const int chunk = 4 * q + q16;
-          *reinterpret_cast<f32x4*>(region + row * 128 + ((chunk ^ (row & 7)) << 4)) = acc[nt][mt0 + mt];
-        }
-      }
-    }
-    // ---- LDS -> rows: lane = (row rrow + 8 it, 16-B chunk rchunk)
-    if constexpr (kF16) {
-      const int n = nbase + pass * 64 + rchunk * 8;
-#pragma unroll
-      for (int it0 = 0; it0 < NIT; it0 += UB) {
-        f16x8 oldh[UB];
-        if constexpr (kResidH) {
-#pragma unroll
-          for (int u = 0; u < UB; ++u) {
-            const int64_t mm = m0h + (it0 + u) * 8 + rrow;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oldh[u][e] = (_Float16)0.f;
-            if (FULL || mm < g.m)
-              oldh[u] = *reinterpret_cast<const f16x8*>(static_cast<const _Float16*>(g.resid) + mm * g.ldo + n);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int row = (it0 + u) * 8 + rrow;
-          const f16x8 v = *reinterpret_cast<const f16x8*>(region + row * 128 + ((rchunk ^ (row & 7)) << 4));
-          // the image already holds the finished fp16 values; the fp16 residual is one packed add per pair (the
-          // exact sum of two fp16 numbers, rounded once)
-          f16x8 o;
-          if constexpr (kResidH)
-            o = v + oldh[u];
-          else
-            o = v;
-          const int64_t m = m0h + row;
-          if (FULL || m < g.m)
-            __builtin_nontemporal_store(o, reinterpret_cast<f16x8*>(static_cast<_Float16*>(g.out) + m * g.ldo + n));
-          if constexpr (EPI == EPI_RESID_F16_STATS) {
-            float xv[8], s1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              xv[e] = (float)o[e];
-              s1 += xv[e];
-            }
-            const float mean_s = sum8_dpp(s1) * (1.0f / 64.0f);
-            float m2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float dv = xv[e] - mean_s;
-              m2 = __builtin_fmaf(dv, dv, m2);
-            }
-            m2 = sum8_dpp(m2);
-            if (rchunk == 0 && (FULL || m < g.m)) {
-              const int64_t slice = (nbase >> 6) + pass;
-              *reinterpret_cast<f32x2*>(g.stats_part + (slice * (g.stats_ld ? g.stats_ld : g.m) + m) * 2) = (f32x2){mean_s, m2};
-            }
-          }
-        }
-      }
-    } else {
-      const int n = nbase + pass * 32 + rchunk * 4;
-      const f32x4 b = bias[pass][0], sc = scale[pass][0];
-#pragma unroll
-      for (int it0 = 0; it0 < NIT; it0 += UB) {
-        f32x4 oldv[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int64_t mm = m0h + (it0 + u) * 8 + rrow;
-          oldv[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-          if constexpr (EPI == HCIR_EPI_BIAS_RESID_F32) {
-            if (FULL || mm < g.m)
-              oldv[u] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(g.resid) + mm * g.ldo + n);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int row = (it0 + u) * 8 + rrow;
-          const int64_t mm = m0h + row;
-          f32x4 v = *reinterpret_cast<const f32x4*>(region + row * 128 + ((rchunk ^ (row & 7)) << 4));
-          if constexpr (EPI == HCIR_EPI_AFFINE_F32) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(v[e], sc[e], b[e]);
-          } else if constexpr (EPI == HCIR_EPI_BIAS_RESID_F32) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(sc[e], v[e] + b[e], oldv[u][e]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += b[e];
-          }
-          if (FULL || mm < g.m) *reinterpret_cast<f32x4*>(static_cast<float*>(g.out) + mm * g.ldo + n) = v;
-        }
-      }
-    }
-  }
-}
-
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int tiles_n, int tiles_m) {
   __shared__ __attribute__((aligned(16))) char lds[2 * GMid::STAGE_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_n = wave >> 1, wave_m = wave & 1;
-  const int ntiles = tiles_n * tiles_m;
-  const int nkc = g.k / 64;
-  const int my_tiles =
-      (int)blockIdx.x < ntiles ? (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-  const int nsteps = my_tiles * nkc;
-
-  auto tile_origin = [&](int ti, int& n0, int64_t& m0) {
-    const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
-    n0 = (t % tiles_n) * GMid::TN;
-    m0 = (int64_t)(t / tiles_n) * GMid::TM;
-  };
-
-  uint32_t soff[GMid::NLOAD];
-  const char* wbase = nullptr;
-  const char* abase = nullptr;
-  auto set_sources = [&](int t_i) {
-    int n0;
-    int64_t m0;
-    tile_origin(t_i, n0, m0);
-    wbase = reinterpret_cast<const char*>(g.w + (int64_t)n0 * g.ldw);
-    abase = reinterpret_cast<const char*>(g.a + m0 * g.lda);
-#pragma unroll
-    for (int i = 0; i < GMid::NLOAD; ++i) {
-      const int piece = tid + GMid::NT * i;
-      const int row = piece >> 3, chunk = (piece & 7) ^ ((row >> 1) & 7);
-      if (row < GMid::TN) {
-        const int nr = n0 + row > g.n - 1 ? g.n - 1 - n0 : row;
-        soff[i] = (uint32_t)(((int64_t)nr * g.ldw + chunk * 8) * 2);
-      } else {
-        int64_t mr = row - GMid::TN;
-        mr = m0 + mr > g.m - 1 ? g.m - 1 - m0 : mr;
-        soff[i] = (uint32_t)((mr * g.lda + chunk * 8) * 2);
-      }
-    }
-  };
-  int issue_ti = 0, issue_kc = 0;
-  auto issue_piece = [&](int slot, int i) {  // i constant after unrolling: pieces 0..3 W rows, 4..9 activation rows
-    lds_dma16((i < GMid::NW ? wbase : abase) + issue_kc * 128, soff[i],
-              lds_addr(lds) + slot * GMid::STAGE_BYTES + ((tid & ~63) + GMid::NT * i) * 16);
-  };
-  auto issue_advance = [&]() {
-    if (++issue_kc == nkc) {
-      issue_kc = 0;
-      ++issue_ti;
-      if (issue_ti < my_tiles) set_sources(issue_ti);
-    }
-  };
+  const int wave_n = wave / GMid::WAVES_M, wave_m = wave % GMid::WAVES_M;
+  GemmStages<GMid> stg(g, lds, tiles_n, tiles_m, tid);
+  const int nkc = stg.nkc, nsteps = stg.nsteps;
 
   f32x4 acc[4][6];
   auto zero_acc = [&]() {
@@ -1001,12 +780,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
   };
   zero_acc();
 
-  if (nsteps > 0) {
-    set_sources(0);
-#pragma unroll
-    for (int i = 0; i < GMid::NLOAD; ++i) issue_piece(0, i);
-    issue_advance();
-  }
+  stg.issue_first();
 
   const int r16 = lane & 15, kq = lane >> 4;
   int kc = 0, ti = 0;
@@ -1031,7 +805,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
       for (int hq = 0; hq < 2; ++hq) {
         if (do_issue && ks2 == 0) {  // the ten DMA pieces of stage step+1 in the first 32-k substep
 #pragma unroll
-          for (int i = 0; i < 5; ++i) issue_piece(islot, 5 * hq + i);
+          for (int i = 0; i < 5; ++i) stg.issue_piece(islot, 5 * hq + i);
         }
 #pragma unroll
         for (int q = 2 * hq; q < 2 * hq + 2; ++q)
@@ -1041,40 +815,24 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
                                                                __builtin_bit_cast(f16x8, bf[mt]), acc[q][mt], 0, 0, 0);
       }
     }
-    if (do_issue) issue_advance();
+    if (do_issue) stg.issue_advance();
 
     if (++kc == nkc) {
       int n0;
       int64_t m0;
-      tile_origin(ti, n0, m0);
+      stg.tile_origin(ti, n0, m0);
       // every wave is done reading slot step&1; it stays free until the DMA of stage step+2 goes out behind the
       // next step's barrier.  Per wave a private 6 KB piece of it: 48 rows x 128 B, two row halves per tile.
       __builtin_amdgcn_s_barrier();
       char* region = lds + (step & 1) * GMid::STAGE_BYTES + wave * 6144;
-      int lane_o = lane;
-      asm volatile("" : "+v"(lane_o));  // opaque: the epilogue's addresses are not hoisted out of the tile loop
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const int64_t m0h = m0 + wave_m * 96 + hh * 48;
-        if (m0h + 48 <= g.m)
-          gemm_epilogue16_lds_impl<EPI, true, 4, 6, 3>(g, acc, 3 * hh, region, m0h, n0 + wave_n * 64, lane_o);
-        else
-          gemm_epilogue16_lds_impl<EPI, false, 4, 6, 3>(g, acc, 3 * hh, region, m0h, n0 + wave_n * 64, lane_o);
-      }
+      for (int hh = 0; hh < 2; ++hh)
+        gemm_epilogue_lds<EPI, 4, 6, 3>(g, acc, 3 * hh, region, m0 + wave_m * 96 + hh * 48, n0 + wave_n * 64, lane);
       zero_acc();
       kc = 0;
       ++ti;
     }
   }
-}
-
-inline bool gemm_takes_mid(int64_t m, int n, int k) { return k % 64 == 0 && m >= 1024 && n % 128 == 0; }
-
-template <int EPI>
-void launch_gemm_mid(const GemmArgs& g, hipStream_t st) {
-  const int tn = g.n / GMid::TN, tm = (int)hcir_cdiv(g.m, GMid::TM);
-  const int grid = tn * tm < 512 ? tn * tm : 512;  // persistent: two workgroups per CU
-  hipLaunchKernelGGL((gemm_f16_mid_kernel<EPI>), dim3(grid), dim3(256), 0, st, g, tn, tm);
 }
 
 // ---------------------------------------------------------------------------
@@ -1260,16 +1018,41 @@ __global__ void cls_row_kernel(const float* __restrict__ cls, const float* __res
   tok[bi * t * (int64_t)d + n] = (TokT)(cls[n] + pos_mult * pos[n]);
 }
 
+// (mean, M2) of the 64-feature slices of hcir_gemm_f16_fused -> (mean, rstd) per row by Chan's parallel-variance
+// combination (equal slice sizes), slices visited in index order: deterministic, no cancellation
+__global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int parts, int64_t m, float slice_n,
+                                         float eps, float* __restrict__ stats) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= m) return;
+  float ms = 0.f;
+  for (int p = 0; p < parts; ++p) ms += part[((int64_t)p * m + row) * 2];
+  const float mean = ms / (float)parts;
+  float m2 = 0.f;
+  for (int p = 0; p < parts; ++p) {
+    const f32x2 v = *reinterpret_cast<const f32x2*>(part + ((int64_t)p * m + row) * 2);
+    const float dm = v[0] - mean;
+    m2 += v[1] + slice_n * dm * dm;
+  }
+  const float var = m2 / (slice_n * (float)parts);
+  *reinterpret_cast<f32x2*>(stats + 2 * row) = (f32x2){mean, 1.0f / sqrtf(var + eps)};
+}
+
+// Which kernel a launch takes, callee first: launch_gemm -> launch_gemm_big -> launch_big_tiles / launch_gemm_mid.
 inline bool gemm_takes_big(int64_t m, int n, int k) { return k % 64 == 0 && m >= 1024 && n % 256 == 0; }
+inline bool gemm_takes_mid(int64_t m, int n, int k) { return k % 64 == 0 && m >= 1024 && n % 128 == 0; }
 
 template <int EPI>
-void launch_gemm_mid(const GemmArgs& g, hipStream_t st);
+void launch_gemm_mid(const GemmArgs& g, hipStream_t st) {
+  const int tn = g.n / GMid::TN, tm = (int)hcir_cdiv(g.m, GMid::TM);
+  const int grid = tn * tm < 512 ? tn * tm : 512;  // persistent: two workgroups per CU
+  hipLaunchKernelGGL((gemm_f16_mid_kernel<EPI>), dim3(grid), dim3(GMid::NT), 0, st, g, tn, tm);
+}
 
 // The 256 x 256 persistent kernel over tn x tm tiles
 template <int EPI>
 void launch_big_tiles(const GemmArgs& g, int tn, int tm, hipStream_t st) {
   const int grid = tn * tm < 256 ? tn * tm : 256;  // persistent: one workgroup per CU
-  hipLaunchKernelGGL((gemm_f16_big_kernel<EPI>), dim3(grid), dim3(512), 0, st, g, tn, tm);
+  hipLaunchKernelGGL((gemm_f16_big_kernel<EPI>), dim3(grid), dim3(G256::NT), 0, st, g, tn, tm);
 }
 
 template <int EPI>
@@ -1313,25 +1096,6 @@ void launch_gemm_big(const GemmArgs& g, hipStream_t st) {
   launch_big_tiles<EPI>(g, tn, tm, st);
 }
 
-// (mean, M2) of the 64-feature slices of hcir_gemm_f16_fused -> (mean, rstd) per row by Chan's parallel-variance
-// combination (equal slice sizes), slices visited in index order: deterministic, no cancellation
-__global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int parts, int64_t m, float slice_n,
-                                         float eps, float* __restrict__ stats) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  float ms = 0.f;
-  for (int p = 0; p < parts; ++p) ms += part[((int64_t)p * m + row) * 2];
-  const float mean = ms / (float)parts;
-  float m2 = 0.f;
-  for (int p = 0; p < parts; ++p) {
-    const f32x2 v = *reinterpret_cast<const f32x2*>(part + ((int64_t)p * m + row) * 2);
-    const float dm = v[0] - mean;
-    m2 += v[1] + slice_n * dm * dm;
-  }
-  const float var = m2 / (slice_n * (float)parts);
-  *reinterpret_cast<f32x2*>(stats + 2 * row) = (f32x2){mean, 1.0f / sqrtf(var + eps)};
-}
-
 template <int EPI>
 void launch_gemm(const GemmArgs& g, hipStream_t st) {
   if (gemm_takes_big(g.m, g.n, g.k)) {
@@ -1366,7 +1130,7 @@ int hcir_gemm_f16_resid(const void* a, int64_t lda, const void* w, int64_t ldw, 
   if ((k & 7) || (n & 7) || lda < k || ldw < k || (lda & 7) || (ldw & 7) || ldo < n || (ldo & 3))
     return HCIR_ERR_INVALID;
   // row pitches other than k: only the 256x256 persistent kernel carries separate pitches
-  if ((lda != k || ldw != k) && !(k % 64 == 0 && m >= 1024 && n % 256 == 0)) return HCIR_ERR_UNSUPPORTED;
+  if ((lda != k || ldw != k) && !gemm_takes_big(m, n, k)) return HCIR_ERR_UNSUPPORTED;
   if ((epilogue == HCIR_EPI_AFFINE_RELU_F16 || epilogue == HCIR_EPI_AFFINE_F32) && !scale)
     return HCIR_ERR_INVALID;
   if (hcir_cdiv(m, 128) * hcir_cdiv(n, 128) > 0x7fffffff) return HCIR_ERR_INVALID;

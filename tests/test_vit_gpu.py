@@ -229,6 +229,83 @@ def test_gemm_many_tiles_per_workgroup(L, m, n, k, ln, epi):
         assert torch.equal(part, got[rows0:rows0 + nrows]), rows0
 
 
+@pytest.fixture(scope="module")
+def same_bits_problem():
+    """Operands of test_gemm_big_and_mid_kernels_same_bits, made once: 4 x 45 tiles of 256 x 256 (180 x 10 >= 256 x 7:
+    the 256 x 256 kernel; 180 <= 256: no tail split; ragged last row of tiles), k = 64."""
+    m, n, k = 11517, 1024, 64
+    g = torch.Generator(device="cuda").manual_seed(m + n + k)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g)
+    a = (rnd(m, k) * 0.5).half()
+    w = (rnd(n, k) * k ** -0.5).half()
+    x = a.float()
+    return dict(m=m, n=n, k=k, a=a, w=w, bias=rnd(n), scale=torch.rand(n, device="cuda", generator=g) + 0.5,
+                resid=rnd(m, n), acc=x @ w.float().t(), c1=w.float().sum(1),
+                stats=torch.stack([x.mean(1), (x.var(1, unbiased=False) + 1e-6).rsqrt()], 1).contiguous())
+
+
+@pytest.mark.parametrize("case", ["bias_f16", "gelu_f16", "resid_f32_scale", "bias_f32", "resid_f16_scale", "resid_f16",
+                                  "affine_relu_f16", "affine_f32", "ln_bias_f16", "ln_gelu_f16", "resid_f16_stats"])
+def test_gemm_big_and_mid_kernels_same_bits(L, same_bits_problem, case):
+    """The 256 x 256 and the 128 x 192 kernel share one epilogue and one k order: for EVERY epilogue, a row range of a
+    problem that is small enough for the 128 x 192 kernel (1530 rows = 8 x 8 tiles, under 0.7 of a round of 256 x 256
+    tiles; the last 48-row half ragged) gives the bits that the 256 x 256 kernel gave for those rows of the whole
+    problem - the per-row statistics slices included.  One fp32 reference comparison per epilogue (tolerances of
+    test_gemm_epilogues), so that "same bits" is not "same wrong bits"."""
+    p = same_bits_problem
+    m, n, k, a, w, bias, scale, acc = (p[x] for x in ("m", "n", "k", "a", "w", "bias", "scale", "acc"))
+    epi, fused, sc, f32 = {"bias_f16": (0, None, None, False), "gelu_f16": (1, None, None, False),
+                           "resid_f32_scale": (2, None, scale, True), "bias_f32": (3, None, None, True),
+                           "resid_f16_scale": (6, None, scale, False), "resid_f16": (6, None, None, False),
+                           "affine_relu_f16": (4, None, scale, False), "affine_f32": (5, None, scale, True),
+                           "ln_bias_f16": (0, "ln", None, False), "ln_gelu_f16": (1, "ln", None, False),
+                           "resid_f16_stats": (6, "stats", None, False)}[case]
+    dt = torch.float32 if f32 else torch.float16
+    resid = p["resid"].to(dt) if epi in (2, 6) else None
+    if fused == "ln":
+        ref = (a.float() - p["stats"][:, :1]) * p["stats"][:, 1:] @ w.float().t() + bias
+    elif epi in (4, 5):
+        ref = acc * scale + bias
+    else:
+        ref = acc + bias
+    if epi == 1:
+        ref = F.gelu(ref)
+    if epi == 4:
+        ref = F.relu(ref)
+    if resid is not None:
+        ref = resid.float() + (ref * sc if sc is not None else ref)
+    nsl = n // 64
+
+    def run(rows0, nrows):
+        out = resid[rows0:rows0 + nrows].clone() if resid is not None else \
+            torch.full((nrows, n), float("nan"), dtype=dt, device="cuda")
+        part = torch.full((nsl, nrows, 2), float("nan"), device="cuda") if fused == "stats" else None
+        ap, scp = a.data_ptr() + rows0 * k * 2, sc.data_ptr() if sc is not None else None
+        if fused:
+            st = L.hcir_gemm_f16_fused(ap, k, w.data_ptr(), k, bias.data_ptr(), scp, nrows, n, k, epi, out.data_ptr(), n,
+                                       p["stats"].data_ptr() + rows0 * 8 if fused == "ln" else None,
+                                       p["c1"].data_ptr() if fused == "ln" else None,
+                                       part.data_ptr() if part is not None else None, _st())
+        else:
+            st = L.hcir_gemm_f16(ap, k, w.data_ptr(), k, bias.data_ptr(), scp, nrows, n, k, epi, out.data_ptr(), n, _st())
+        assert st == 0
+        torch.cuda.synchronize()
+        return out, part
+
+    full, full_part = run(0, m)
+    tol = 1e-4 if f32 else 2e-3
+    err = (full.float() - ref).abs().max().item()
+    print(f"{case}: max abs error {err:.3e}, bound {tol * max(1.0, ref.abs().max().item()):.3e}")
+    assert err <= tol * max(1.0, ref.abs().max().item())
+    nrows = 1530
+    for rows0 in (0, m - nrows):
+        part_out, part_stats = run(rows0, nrows)
+        assert torch.equal(part_out, full[rows0:rows0 + nrows]), rows0
+        if fused == "stats":      # the whole problem's slices have pitch m, the row range's pitch nrows
+            assert torch.isfinite(full_part).all()
+            assert torch.equal(part_stats, full_part[:, rows0:rows0 + nrows]), rows0
+
+
 @pytest.mark.parametrize("m,d,mlp", [(1500, 256, 512), (197 * 6, 768, 3072), (197 * 64, 768, 3072)])
 def test_gemm_fused_layernorm(L, m, d, mlp):
     """hcir_gemm_f16_fused: (1) the fp16-residual epilogue also emits per-row (sum, sumsq) slices ->
