@@ -1,6 +1,6 @@
-// conv_plan.h — host-side geometry of the ResNet convolution kernels (conv.hip): which requests a kernel exists for,
-// output sizes, tile choice and launch grid.  Plain C++, no device code, so that the arithmetic can be read (and
-// restated in Python, hcir/resnet_engine.py) without the kernels.
+// conv_plan.h — host-side geometry of the ResNet convolution kernels (conv.hip, conv_bwd.hip): which requests a kernel
+// exists for, output sizes, tile choice, M splits and launch grid.  Plain C++, no device code, so that the arithmetic
+// can be read (and restated in Python, hcir/resnet_engine.py) without the kernels.
 #pragma once
 #include <stdint.h>
 
@@ -39,6 +39,49 @@ static inline int conv_plan(int64_t b, int32_t h, int32_t w, int32_t cin, int32_
   p->bn = (cout % 128 == 0 && p->grid_m * (cout / 128) >= 512) ? 128 : 64;
   p->grid_n = cout / p->bn;
   return HCIR_OK;
+}
+
+// Weight gradient (conv_bwd.hip): per tap a [Cout] x [Cin] product contracted over the M = B * ho * wo output pixels.
+struct WgradPlan {
+  int32_t ho, wo;
+  int64_t m;
+  int32_t k;               // row length of dw: R * S * Cin
+  int32_t tn, tc;          // output tile: tn output channels x tc input channels of one tap
+  int32_t taps;            // R * S
+  int32_t tiles;           // (Cout / tn) * (Cin / tc) * taps
+  int32_t splits;          // workgroups along M per tile
+  int64_t rows_per_split;  // multiple of WGRAD_BM; only the last split may hold fewer
+};
+
+constexpr int WGRAD_BM = 64;        // output pixels per main-loop step
+constexpr int WGRAD_TARGET = 512;   // workgroups wanted at least: two per CU
+
+static inline int wgrad_plan(int64_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t r, int32_t s,
+                             int32_t stride, int32_t pad, WgradPlan* p) {
+  ConvPlan f;
+  const int st = conv_plan(b, h, w, cin, cout, r, s, stride, pad, &f);   // the forward's shapes, the forward's statuses
+  if (st != HCIR_OK) return st;
+  p->ho = f.ho;
+  p->wo = f.wo;
+  p->m = f.m;
+  p->k = f.k;
+  p->tn = cout % 128 == 0 ? 128 : 64;
+  p->tc = cin % 128 == 0 ? 128 : 64;
+  p->taps = r * s;
+  const int64_t tiles = (int64_t)(cout / p->tn) * (cin / p->tc) * p->taps;
+  if (tiles > (1 << 20)) return HCIR_ERR_UNSUPPORTED;
+  p->tiles = (int32_t)tiles;
+  // layer1's 3x3 is 9 tiles: M is cut until the grid has WGRAD_TARGET workgroups, but never below one step per split
+  const int64_t steps = (p->m + WGRAD_BM - 1) / WGRAD_BM;
+  int64_t splits = (WGRAD_TARGET + tiles - 1) / tiles;
+  splits = splits > steps ? steps : splits;
+  p->rows_per_split = ((steps + splits - 1) / splits) * WGRAD_BM;
+  p->splits = (int32_t)((p->m + p->rows_per_split - 1) / p->rows_per_split);
+  return HCIR_OK;
+}
+
+static inline size_t wgrad_workspace_bytes(const WgradPlan& p, int32_t cout) {
+  return p.splits > 1 ? (size_t)p.splits * cout * p.k * sizeof(float) : 0;   // one split writes dw itself
 }
 
 // Stem: conv 7x7 / 2 / pad 3 then maxpool 3x3 / 2 / pad 1.

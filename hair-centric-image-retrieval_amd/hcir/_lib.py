@@ -129,6 +129,11 @@ SIGNATURES = {
     "hcir_conv2d_tile_n": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "hcir_resnet_stem": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hcir_avgpool_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_int, c_f32, c_vp, c_vp]),
+    "hcir_conv2d_wgrad_f16": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                      c_vp, c_sz, c_vp]),
+    "hcir_conv2d_wgrad_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "hcir_conv2d_wgrad_splits": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "hcir_spread2_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
 }
 
 

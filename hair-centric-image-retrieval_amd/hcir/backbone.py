@@ -17,6 +17,7 @@ from torch import nn
 
 from . import _tv_resnet, models_vit
 from .main_backbone import SimCLRProjectionHead, ViTWrapper
+from .conv_train import hip_train_active, train_trunk
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 
@@ -43,6 +44,13 @@ class SimCLR(nn.Module):
         # opt-in HIP trunk for the ResNets (eval mode, HIP device, no_grad), as in SHAM2
         self.hip_trunk = False
         self._trunk_cache = ResNetEngineCache()
+        # opt-in HIP body convolutions for a ResNet in train mode with autograd on, as in SHAM2
+        self.hip_train = False
+
+    def _hip_train(self, x):
+        if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
+            return None
+        return train_trunk(self.backbone, x)
 
     def _hip_trunk(self, x):
         if "vit" in self.model or not hip_trunk_active(self.hip_trunk, self.backbone, x):
@@ -59,12 +67,17 @@ class SimCLR(nn.Module):
         if f is not None:
             head = self.projection_head
             return head(f) if head.training else head.forward_hip(f.half())
+        f = self._hip_train(x)
+        if f is not None:
+            return self.projection_head(f)
         return self.projection_head(self.backbone(x).flatten(start_dim=1))
 
     def extract_features(self, x):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
         f = self._hip_trunk(x)
+        if f is None:
+            f = self._hip_train(x)
         if f is not None:
             return f
         return self.backbone(x).flatten(start_dim=1)

@@ -1,0 +1,180 @@
+"""hcir.conv_train — training the ResNet-18 / ResNet-50 body on libhcir's convolution kernels: a differentiable
+convolution over fp16 NHWC activations and the fp32 master weight, and the train-mode walk of the trunk that uses it.
+
+Serves the forward and backward of the torchvision Conv2d modules behind HP/src/main_backbone.py:576-579 in the step
+of HP/src/pretrain_engine.py:682-747, which runs under torch.autocast(fp16): fp16 conv operands with fp32
+accumulation are the reference's own arithmetic.  Opt-in through the model's `hip_train` switch.
+
+  forward   hcir_conv2d_f16 with the identity epilogue (scale 1, bias 0, no residual, no ReLU)
+  dx        hcir_conv2d_f16 again, over dy with wT[c][r'][s'][n] = w[n][R-1-r'][S-1-s'][c]:
+              stride 1           dx = conv(dy, wT, stride 1, same pad)
+              1x1 stride 2       t = conv(dy, wT) at Ho x Wo, dx = spread2(t)   (dx[2i][2j] = t[i][j], zero elsewhere)
+              3x3 stride 2       z = spread2(dy) at H x W, dx = conv(z, wT, stride 1, pad 1): 4x the useful flops on
+                                 the three stride-2 3x3 layers of a trunk (a parity-class kernel is later work)
+  dW        hcir_conv2d_wgrad_f16 (csrc/conv_bwd.hip), fp32 [Cout,R,S,Cin], permuted back to [Cout,Cin,R,S] and
+            handed to autograd, whose own accumulation sums the views of a step
+
+The stem (Conv 7x7, BatchNorm, ReLU, MaxPool: 3 % of the flops, Cin = 3 fits none of the kernels), every BatchNorm2d
+(batch statistics, running-statistic updates), ReLU, the residual adds and the average pool stay the trunk's own torch
+modules, called on channels-last fp16 tensors.  torch's batch norm takes fp16 input with fp32 parameters as it does
+under autocast (batch_norm is on neither autocast list: it runs in its input's dtype), so no autocast region is needed.
+"""
+from __future__ import annotations
+
+import weakref
+from typing import Tuple
+
+import torch
+from torch import nn
+
+from . import ops
+from ._lib import HcirError
+from .resnet_engine import layer_table, pack_conv_weight
+
+
+class _WeightCache:
+    """Per parameter: the fp16 packed weight [Cout,R,S,Cin] and its flipped transpose [Cin,R,S,Cout], refreshed when
+    the parameter's (_version, data_ptr, device) changes - an optimizer step, load_state_dict, .to() - as VitTrainer
+    does for the ViT's operand copies.  A write through `p.data` bumps none of them: call clear() after such an edit."""
+
+    def __init__(self):
+        self._ent = {}    # id(parameter) -> (weak reference, key, w16, wt16); a tensor's == is elementwise, so no
+                          # WeakKeyDictionary
+
+    def clear(self) -> None:
+        self._ent.clear()
+
+    def get(self, w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        key = (w._version, w.data_ptr(), str(w.device))
+        ent = self._ent.get(id(w))
+        if ent is None or ent[0]() is not w or ent[1] != key:
+            ents, i = self._ent, id(w)
+
+            def drop(ref):    # the parameter died: forget its copies, unless the id already belongs to a new one
+                if i in ents and ents[i][0] is ref:
+                    del ents[i]
+
+            ent = (weakref.ref(w, drop), key, pack_conv_weight(w), flip_transpose_packed(w))
+            ents[i] = ent
+        return ent[2], ent[3]
+
+
+def flip_transpose_packed(w: torch.Tensor) -> torch.Tensor:
+    """[Cout,Cin,R,S] -> fp16 [Cin,R,S,Cout] with both taps reversed: the packed weight of the data-gradient conv."""
+    return pack_conv_weight(w.detach().flip(2, 3).permute(1, 0, 2, 3))
+
+
+weights = _WeightCache()
+_identity = {}
+
+
+def _identity_epilogue(device: torch.device, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    key = (str(device), n)
+    ent = _identity.get(key)
+    if ent is None:
+        ent = (torch.ones(n, dtype=torch.float32, device=device), torch.zeros(n, dtype=torch.float32, device=device))
+        _identity[key] = ent
+    return ent
+
+
+def _conv(x: torch.Tensor, w16: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    one, zero = _identity_epilogue(x.device, w16.shape[0])
+    return ops.conv2d_f16(x, w16, one, zero, stride, pad)
+
+
+def conv2d_dgrad(dy: torch.Tensor, wt16: torch.Tensor, h: int, w: int, stride: int, pad: int) -> torch.Tensor:
+    """dx fp16 [B,h,w,Cin] of a convolution whose input was h x w: dy fp16 [B,Ho,Wo,Cout], wt16 from
+    flip_transpose_packed."""
+    r = wt16.shape[1]
+    if stride == 1:
+        return _conv(dy, wt16, 1, pad)
+    if stride != 2 or (r, pad) not in ((1, 0), (3, 1)):
+        raise HcirError(f"conv2d_dgrad: no plan for a {r}x{r} / {stride} / pad {pad} convolution")
+    if r == 1:
+        return ops.spread2_nhwc(_conv(dy, wt16, 1, 0), h, w)
+    return _conv(ops.spread2_nhwc(dy, h, w), wt16, 1, 1)
+
+
+class _Conv2dNHWC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad):
+        if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.dtype != torch.float32:
+            raise HcirError(f"conv2d_nhwc expects an fp32 [Cout,Cin,R,R] weight, got {weight.dtype} "
+                            f"{tuple(weight.shape)}")
+        x = x.contiguous()
+        w16, wt16 = weights.get(weight)
+        ctx.save_for_backward(x)
+        ctx.wt16, ctx.r, ctx.stride, ctx.pad = wt16, weight.shape[2], stride, pad
+        return _conv(x, w16, stride, pad)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = conv2d_dgrad(dy, ctx.wt16, x.shape[1], x.shape[2], ctx.stride, ctx.pad)
+        if ctx.needs_input_grad[1]:
+            dw = ops.conv2d_wgrad(x, dy, ctx.r, ctx.stride, ctx.pad).permute(0, 3, 1, 2).contiguous()
+        return dx, dw, None, None
+
+
+def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """Differentiable convolution: x fp16 NHWC [B,H,W,Cin], weight the module's fp32 [Cout,Cin,R,R] parameter ->
+    fp16 NHWC [B,Ho,Wo,Cout].  Shapes without a kernel raise HcirError."""
+    return _Conv2dNHWC.apply(x, weight, stride, pad)
+
+
+_checked = weakref.WeakKeyDictionary()
+
+
+def _check_trunk(trunk: nn.Module) -> None:
+    """resnet_engine's structure checks (stem, pooling, every body conv has a kernel), once per trunk object and
+    number of modules."""
+    n = sum(1 for _ in trunk.modules())
+    if _checked.get(trunk) != n:
+        layer_table(trunk)
+        _checked[trunk] = n
+
+
+def _cv(conv: nn.Conv2d, a: torch.Tensor) -> torch.Tensor:
+    # `a` is a logical [B,C,H,W] view of an NHWC tensor (what the BatchNorm2d modules take); so is the result
+    y = conv2d_nhwc(a.permute(0, 2, 3, 1), conv.weight, conv.stride[0], conv.padding[0])
+    return y.permute(0, 3, 1, 2)
+
+
+def _block(blk: nn.Module, a: torch.Tensor) -> torch.Tensor:
+    """torchvision BasicBlock.forward / Bottleneck.forward with the convolutions on conv2d_nhwc."""
+    identity = a
+    out = blk.relu(blk.bn1(_cv(blk.conv1, a)))
+    if hasattr(blk, "conv3"):
+        out = blk.relu(blk.bn2(_cv(blk.conv2, out)))
+        out = blk.bn3(_cv(blk.conv3, out))
+    else:
+        out = blk.bn2(_cv(blk.conv2, out))
+    if blk.downsample is not None:
+        identity = blk.downsample[1](_cv(blk.downsample[0], a))
+    out = out + identity
+    return blk.relu(out)
+
+
+def train_trunk(trunk: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """The differentiable train-mode walk of nn.Sequential(children()[:-1]): x fp32 [B,3,H,W] -> fp32 [B,C]."""
+    _check_trunk(trunk)
+    kids = list(trunk.children())
+    a = kids[3](kids[2](kids[1](kids[0](x))))
+    # the one cast and layout change: fp16, NHWC in memory (a channels-last [B,C,H,W] tensor)
+    a = a.permute(0, 2, 3, 1).contiguous().half().permute(0, 3, 1, 2)
+    for layer in kids[4:8]:
+        for blk in layer:
+            a = _block(blk, a)
+    return kids[8](a.float()).flatten(start_dim=1)
+
+
+def hip_train_active(enabled: bool, trunk: nn.Module, x: torch.Tensor) -> bool:
+    """The conditions under which a model's `hip_train` switch routes a ResNet trunk through train_trunk: switched
+    on, trunk in train mode, autograd on, and an fp32 [B >= 1, 3, H >= 7, W >= 7] tensor on a HIP device.  Any other
+    call keeps the code it had."""
+    return (bool(enabled) and trunk.training and torch.is_grad_enabled() and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] == 3
+            and x.shape[2] >= 7 and x.shape[3] >= 7)

@@ -7,7 +7,8 @@ signatures (HP/src/main_backbone.py:528-637), backed by the MI355X hot path.
   SimCLRProjectionHead(in, hid, out)   lightly.models.modules (keys layers.{0,1,3,4})
 
 ViT compute goes through hcir.vit_engine -> libhcir.so (hand-written HIP);
-ResNet trunks are PyTorch-ROCm modules.  The ViT path has no CPU
+ResNet trunks are PyTorch-ROCm modules unless `hip_trunk` (eval mode, hcir.resnet_engine) or
+`hip_train` (train mode, hcir.conv_train) is switched on.  The ViT path has no CPU
 fallback.  With autograd enabled on parameters that require grad, `forward_cls` runs the
 training forward of hcir.vit_train (activations kept, backward through hcir_gemm_f16_tn /
 hcir_attn_bwd / hcir_layernorm_bwd ...): `SHAM2.forward` in train mode is differentiable
@@ -24,6 +25,7 @@ from torch import nn
 from . import _lib
 from ._lib import HcirError, check
 from . import _tv_resnet, _tv_vit
+from .conv_train import hip_train_active, train_trunk
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 from .vit_train import VitTrainer, vit_cls_with_grad
@@ -204,6 +206,17 @@ class SHAM2(nn.Module):
         # convolution kernels) instead of torch / MIOpen; off, or with any condition unmet, the torch path is untouched
         self.hip_trunk = False
         self._trunk_caches = {}
+        # opt-in: ResNet trunks in train mode with autograd on run their body convolutions, forward and backward, on
+        # the HIP kernels (hcir.conv_train); off, or with any condition unmet, nothing changes.  The momentum twin is
+        # never trained and never takes this path.
+        self.hip_train = False
+
+    def _hip_train(self, x):
+        """fp32 [B, C] differentiable features of `backbone` from hcir.conv_train, or None when the `hip_train` switch
+        does not apply to this call."""
+        if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
+            return None
+        return train_trunk(self.backbone, x)
 
     def _hip_trunk(self, which: str, x):
         """fp32 [B, C] features of `backbone` / `backbone_momentum` from the HIP engine, or None when the switch
@@ -234,6 +247,9 @@ class SHAM2(nn.Module):
         f = self._hip_trunk("backbone", x)
         if f is not None:
             return self._project(self.projection_head, f)
+        f = self._hip_train(x)
+        if f is not None:
+            return self.projection_head(f)
         x = self.backbone(x).flatten(start_dim=1)
         return self.projection_head(x)
 
@@ -264,6 +280,8 @@ class SHAM2(nn.Module):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
         f = self._hip_trunk("backbone", x)
+        if f is None:
+            f = self._hip_train(x)
         if f is not None:
             return f
         return self.backbone(x).flatten(start_dim=1)

@@ -238,3 +238,62 @@ def avgpool_nhwc(x: torch.Tensor, l2_normalize: bool = False, eps: float = 1e-12
     check(_lib.lib().hcir_avgpool_nhwc_f16(x.data_ptr(), b, h, wd, c, int(l2_normalize), eps, out.data_ptr(),
                                            _stream(x)), "hcir_avgpool_nhwc_f16")
     return out
+
+
+# ------------------------------------------------------------------ ResNet body backward (csrc/conv_bwd.hip)
+def _wgrad_shape(x: torch.Tensor, dy: torch.Tensor, r: int, stride: int, pad: int):
+    if x.dtype != torch.float16 or dy.dtype != torch.float16 or x.dim() != 4 or dy.dim() != 4:
+        raise HcirError("conv2d_wgrad expects fp16 NHWC x [B,H,W,Cin] and dy [B,Ho,Wo,Cout]")
+    b, h, wd, cin = x.shape
+    cout = dy.shape[3]
+    want = (b, conv_out_size(h, r, stride, pad), conv_out_size(wd, r, stride, pad), cout)
+    if tuple(dy.shape) != want:
+        raise HcirError(f"shape mismatch: x {tuple(x.shape)} with a {r}x{r} / {stride} / pad {pad} conv gives dy "
+                        f"{want}, got {tuple(dy.shape)}")
+    return b, h, wd, cin, cout
+
+
+def conv2d_wgrad_splits(b: int, h: int, w: int, cin: int, cout: int, r: int, stride: int, pad: int) -> int:
+    """Number of M splits hcir_conv2d_wgrad_f16 runs the shape with; raises for a shape without a kernel."""
+    n = _lib.lib().hcir_conv2d_wgrad_splits(b, h, w, cin, cout, r, r, stride, pad)
+    if n < 0:
+        check(n, "hcir_conv2d_wgrad_splits")
+    return n
+
+
+def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, r: int, stride: int, pad: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Weight gradient of conv2d_f16's convolution: x fp16 [B,H,W,Cin], dy fp16 [B,Ho,Wo,Cout] -> fp32
+    [Cout,R,S,Cin] (the layout of resnet_engine.pack_conv_weight), deterministic."""
+    _dev(x, "x")
+    _dev(dy, "dy")
+    b, h, wd, cin, cout = _wgrad_shape(x, dy, r, stride, pad)
+    shape = (cout, r, r, cin)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _dev(out, "out")
+    if out.dtype != torch.float32 or tuple(out.shape) != shape:
+        raise HcirError(f"`out` must be fp32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    L = _lib.lib()
+    wsb = L.hcir_conv2d_wgrad_workspace_bytes(b, h, wd, cin, cout, r, r, stride, pad)
+    ws = _ws.get(x.device, wsb) if wsb else None
+    check(L.hcir_conv2d_wgrad_f16(x.data_ptr(), dy.data_ptr(), b, h, wd, cin, cout, r, r, stride, pad, out.data_ptr(),
+                                  _ptr(ws), wsb, _stream(x)), "hcir_conv2d_wgrad_f16")
+    return out
+
+
+def spread2_nhwc(src: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, 2i, 2j] = src[b, i, j], zero elsewhere: src fp16 [B,hs,ws,C] -> fp16 [B,h,w,C], every element written."""
+    _dev(src, "src")
+    if src.dtype != torch.float16 or src.dim() != 4:
+        raise HcirError("spread2_nhwc expects fp16 [B,hs,ws,C]")
+    b, hs, ws, c = src.shape
+    shape = (b, h, w, c)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=src.device)
+    _dev(out, "out")
+    if out.dtype != torch.float16 or tuple(out.shape) != shape:
+        raise HcirError(f"`out` must be fp16 {shape}, got {out.dtype} {tuple(out.shape)}")
+    check(_lib.lib().hcir_spread2_nhwc_f16(src.data_ptr(), b, hs, ws, c, h, w, out.data_ptr(), _stream(src)),
+          "hcir_spread2_nhwc_f16")
+    return out

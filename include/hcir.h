@@ -710,7 +710,8 @@ int hcir_simclr_view_f32(const uint8_t* crops, const hcir_view_params* params_de
                          int64_t n, const float* mean3, const float* std3, float* out, void* stream);
 
 /* ------------------------------------------------------------------ *
- * ResNet-18 / ResNet-50 trunk, eval mode (running statistics), inference only.
+ * ResNet-18 / ResNet-50 trunk, eval mode (running statistics): the inference engine.  hcir_conv2d_f16 with the
+ * identity epilogue is also the train-mode forward and the data gradient of the body convolutions (next section).
  * Replaces the nn.Sequential(children()[:-1]) trunk behind SHAM2.extract_features / extract_features_ema
  * (HP/src/main_backbone.py:572-578,624-629) and SimCLR.extract_features (HP/src/backbone.py:660-661):
  * torchvision Conv2d / BatchNorm2d / ReLU / MaxPool2d / AdaptiveAvgPool2d.
@@ -751,6 +752,41 @@ int hcir_resnet_stem(const float* img, int64_t b, int32_t h, int32_t w, const vo
  * each row is divided by max(||row||_2, eps) (F.normalize, HP/src/classification_engine.py:50, eps 1e-12). */
 int hcir_avgpool_nhwc_f16(const void* x, int64_t b, int32_t h, int32_t w, int32_t c, int l2_normalize, float eps,
                           float* out, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * ResNet-18 / ResNet-50 body convolutions, backward (training; hcir/conv_train.py, the model's `hip_train` switch).
+ * Serves the backward of the torchvision Conv2d modules behind HP/src/main_backbone.py:576-579, reached from
+ * scaler.scale(total_loss).backward() at HP/src/pretrain_engine.py:747 (the step runs under torch.autocast(fp16),
+ * HP/src/pretrain_engine.py:681,715: fp16 operands with fp32 accumulation are the reference's own arithmetic).
+ * The data gradient needs no kernel of its own: it is hcir_conv2d_f16 over dy with the flipped, transposed weight
+ * (stride 1), followed (1x1 stride 2) or preceded (3x3 stride 2) by hcir_spread2_nhwc_f16.
+ * ------------------------------------------------------------------ */
+
+/* Weight gradient of hcir_conv2d_f16's convolution:
+ *   dw[n][r][s][c] = sum_{b,ho,wo} dy[b][ho][wo][n] * x[b][ho*stride + r - pad][wo*stride + s - pad][c]
+ * (padding taps are zeros).  x fp16 [B][H][W][Cin]; dy fp16 [B][Ho][Wo][Cout]; dw fp32 [Cout][R][S][Cin], overwritten.
+ * fp32 accumulation; the B*Ho*Wo pixels are split over workgroups whose partial tiles go to `workspace` and are added
+ * in split order: no float atomics, two calls give the same bits.  Shapes and statuses as the forward: (R, S, pad) in
+ * {(1,1,0), (3,3,1)}, stride in {1, 2}, Cin % 64 == 0, Cout % 64 == 0, any B, H, W >= 1; anything else is
+ * HCIR_ERR_UNSUPPORTED, decided from the shape alone before a pointer is looked at.  HCIR_ERR_WORKSPACE when
+ * `workspace_bytes` is below the size the shape needs (0 when one split covers M; `workspace` may then be NULL). */
+int hcir_conv2d_wgrad_f16(const void* x, const void* dy, int64_t b, int32_t h, int32_t w, int32_t cin, int32_t cout,
+                          int32_t r, int32_t s, int32_t stride, int32_t pad, float* dw, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* HOST.  Workspace of the weight gradient for a shape: splits * Cout * R * S * Cin * 4 bytes, 0 when one split covers
+ * M or the shape has no kernel. */
+size_t hcir_conv2d_wgrad_workspace_bytes(int64_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t r,
+                                         int32_t s, int32_t stride, int32_t pad);
+/* HOST.  Number of M splits the weight gradient runs this shape with (a test uses it to know which path a case
+ * exercised).  Negative: the status the weight gradient returns for the shape. */
+int32_t hcir_conv2d_wgrad_splits(int64_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t r, int32_t s,
+                                 int32_t stride, int32_t pad);
+
+/* dst[b][2i][2j][:] = src[b][i][j][:], zero elsewhere: src fp16 [B][hs][ws][C], dst fp16 [B][h][w][C], every element
+ * of dst written (plain vector stores, no memset needed).  HCIR_ERR_INVALID unless 2 (hs - 1) <= h - 1 and
+ * 2 (ws - 1) <= w - 1; HCIR_ERR_UNSUPPORTED unless C % 8 == 0. */
+int hcir_spread2_nhwc_f16(const void* src, int64_t b, int32_t hs, int32_t ws, int32_t c, int32_t h, int32_t w,
+                          void* dst, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,151 @@
+"""ResNet-18 / ResNet-50 trunk TRAINING timings on one GPU: forward + backward of the trunk at 224 x 224 (recorded in
+DESIGN.md §3.4, not gated; bench.py is the contract).
+
+Four paths, same process, same machine, same input; median over --steps iterations after --warmup (HIP events around
+forward + backward of loss = features.sum(); gradients are dropped between iterations, no optimizer):
+  torch_fp32                 the torch trunk as SHAMTrainStep runs it today (fp32 NCHW, MIOpen)
+  torch_autocast             torch.autocast(fp16), the reference's way (HP/src/pretrain_engine.py:681)
+  torch_autocast_chlast      the same on a channels_last trunk and input: the fair vendor yardstick
+  hip_train                  the model's `hip_train` switch: hcir.conv_train (body convolutions on the HIP kernels)
+then ONE more hip_train iteration with every libhcir call bracketed by HIP events, which splits its device time into
+forward convolutions, data gradients by plan (stride 1; 1x1 stride 2; the 3x3 stride 2 that does 4x the useful
+flops - each with its spread-by-2 copy), weight gradients, and the rest (torch: stem, BatchNorm, ReLU, adds, casts,
+pool).  Events, not a profiler's kernel trace: forward and data gradient run the SAME kernel and only the call site
+tells them apart.
+One JSON line per (model, batch).
+
+  python tools/bench_resnet_train.py [--model resnet50,resnet18] [--batch 64,256] [--steps 10] [--warmup 3]
+"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "hair-centric-image-retrieval_amd"))
+
+
+def median_ms(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return statistics.median(times)
+
+
+def fwd_bwd(features, params):
+    def run():
+        for p in params:
+            p.grad = None
+        features().float().sum().backward()
+    return run
+
+
+def kernel_shares(model, x):
+    """Device time of one hip_train forward + backward by kind of libhcir work (HIP events around every forward
+    convolution, every data gradient - its spread-by-2 copy included - and every weight gradient)."""
+    from hcir import conv_train, ops
+    spans = []
+    inside = {"dgrad": False}
+
+    def bracket(label, fn, *a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(*a, **k)
+        e1.record()
+        spans.append((label, e0, e1))
+        return out
+
+    real_conv, real_wgrad, real_dgrad = ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad
+
+    def conv(*a, **k):
+        return real_conv(*a, **k) if inside["dgrad"] else bracket("forward", real_conv, *a, **k)
+
+    def dgrad(dy, wt16, h, w, stride, pad):
+        label = "dgrad_stride1" if stride == 1 else ("dgrad_1x1_stride2" if wt16.shape[1] == 1 else "dgrad_3x3_stride2")
+        inside["dgrad"] = True
+        try:
+            return bracket(label, real_dgrad, dy, wt16, h, w, stride, pad)
+        finally:
+            inside["dgrad"] = False
+
+    ops.conv2d_f16, conv_train.conv2d_dgrad = conv, dgrad
+    ops.conv2d_wgrad = lambda *a, **k: bracket("wgrad", real_wgrad, *a, **k)
+    try:
+        for p in model.backbone.parameters():
+            p.grad = None
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        model.extract_features(x).float().sum().backward()
+        t1.record()
+        torch.cuda.synchronize()
+    finally:
+        ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad = real_conv, real_wgrad, real_dgrad
+    total = t0.elapsed_time(t1)
+    by = {}
+    for label, e0, e1 in spans:
+        by[label] = by.get(label, 0.0) + e0.elapsed_time(e1)
+    by["torch_rest"] = total - sum(by.values())
+    return {"total_ms": round(total, 3), "ms": {k: round(v, 3) for k, v in sorted(by.items())},
+            "share": {k: round(v / total, 4) for k, v in sorted(by.items())}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="resnet50,resnet18")
+    ap.add_argument("--batch", default="64,256")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+
+    from hcir.main_backbone import SHAM2
+
+    dev = torch.device("cuda", 0)
+    for name in args.model.split(","):
+        torch.manual_seed(0)
+        model = SHAM2(name).train().to(dev)
+        trunk = model.backbone
+        trunk_cl = copy.deepcopy(trunk).to(memory_format=torch.channels_last)
+        for b in (int(v) for v in args.batch.split(",")):
+            x = torch.randn(b, 3, 224, 224, device=dev)
+            x_cl = x.contiguous(memory_format=torch.channels_last)
+
+            def autocast(t, inp):
+                def f():
+                    with torch.autocast("cuda", dtype=torch.float16):
+                        return t(inp).flatten(1)
+                return f
+
+            model.hip_train = False
+            ms = {"torch_fp32": median_ms(fwd_bwd(lambda: trunk(x).flatten(1), list(trunk.parameters())),
+                                          args.warmup, args.steps),
+                  "torch_autocast": median_ms(fwd_bwd(autocast(trunk, x), list(trunk.parameters())),
+                                              args.warmup, args.steps),
+                  "torch_autocast_chlast": median_ms(fwd_bwd(autocast(trunk_cl, x_cl), list(trunk_cl.parameters())),
+                                                     args.warmup, args.steps)}
+            model.hip_train = True
+            ms["hip_train"] = median_ms(fwd_bwd(lambda: model.extract_features(x), list(trunk.parameters())),
+                                        args.warmup, args.steps)
+            shares = kernel_shares(model, x)
+            out = {"model": name, "batch": b, "steps": args.steps,
+                   "ms": {k: round(v, 3) for k, v in ms.items()},
+                   "img_per_s": {k: round(b / v * 1e3, 1) for k, v in ms.items()},
+                   "fastest": min(ms, key=ms.get),
+                   "hip_train_vs": {k: round(ms["hip_train"] / v, 3) for k, v in ms.items() if k != "hip_train"},
+                   "hip_train_breakdown": shares}
+            print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

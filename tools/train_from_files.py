@@ -61,6 +61,8 @@ def main():
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-steps", type=int, default=0)
+    ap.add_argument("--hip-train", action="store_true",
+                    help="ResNet models: body convolutions forward and backward on the HIP kernels (hcir.conv_train)")
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
@@ -71,6 +73,7 @@ def main():
                                          num_workers=a.workers, collate_fn=functools.partial(collate_train_views),
                                          pin_memory=False)
     model = SHAM2(a.model).cuda()
+    model.hip_train = a.hip_train
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
     step = SHAMTrainStep(model, opt, torch.amp.GradScaler("cuda"), warm_up_epochs=a.warm_up_epochs)
 
