@@ -134,6 +134,12 @@ SIGNATURES = {
     "hcir_conv2d_wgrad_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "hcir_conv2d_wgrad_splits": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "hcir_spread2_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "hcir_bn2d_fwd_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_f32, c_vp, c_int, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_bn2d_bwd_nhwc_f16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_sz, c_vp]),
+    "hcir_bn2d_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "hcir_bn2d_chunks": (c_i32, [c_i64, c_i32]),
 }
 
 

@@ -17,7 +17,7 @@ from torch import nn
 
 from . import _tv_resnet, models_vit
 from .main_backbone import SimCLRProjectionHead, ViTWrapper
-from .conv_train import hip_train_active, train_trunk
+from .conv_train import hip_train_active, train_trunk, train_trunk_fused
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 
@@ -46,10 +46,14 @@ class SimCLR(nn.Module):
         self._trunk_cache = ResNetEngineCache()
         # opt-in HIP body convolutions for a ResNet in train mode with autograd on, as in SHAM2
         self.hip_train = False
+        # opt-in on top of hip_train: the body's BatchNorm2d, residual adds and ReLUs on HIP as well, as in SHAM2
+        self.hip_train_norm = False
 
     def _hip_train(self, x):
         if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
             return None
+        if self.hip_train_norm:
+            return train_trunk_fused(self.backbone, x)
         return train_trunk(self.backbone, x)
 
     def _hip_trunk(self, x):

@@ -18,6 +18,12 @@ The stem (Conv 7x7, BatchNorm, ReLU, MaxPool: 3 % of the flops, Cin = 3 fits non
 (batch statistics, running-statistic updates), ReLU, the residual adds and the average pool stay the trunk's own torch
 modules, called on channels-last fp16 tensors.  torch's batch norm takes fp16 input with fp32 parameters as it does
 under autocast (batch_norm is on neither autocast list: it runs in its input's dtype), so no autocast region is needed.
+
+With the model's second switch, `hip_train_norm`, on as well, the body's BatchNorm2d layers leave torch too
+(train_trunk_fused): bn_act_nhwc runs batch statistics, normalisation, the block's residual add and its ReLU as one
+pass over the fp16 NHWC map, forward and backward (hcir_bn2d_fwd_nhwc_f16 / hcir_bn2d_bwd_nhwc_f16, csrc/bn2d.hip), and
+updates the module's running statistics in the kernel.  The stem, the cast to fp16 NHWC and the average pool stay
+torch's on that path as well.
 """
 from __future__ import annotations
 
@@ -178,3 +184,73 @@ def hip_train_active(enabled: bool, trunk: nn.Module, x: torch.Tensor) -> bool:
     return (bool(enabled) and trunk.training and torch.is_grad_enabled() and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] == 3
             and x.shape[2] >= 7 and x.shape[3] >= 7)
+
+
+# ------------------------------------------------------------------ the `hip_train_norm` walk: BatchNorm2d on HIP too
+class _BnActNHWC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, resid, bn, relu):
+        x = x.contiguous()
+        if resid is not None:
+            resid = resid.contiguous()
+        # the running statistics are updated by the kernel, in place, outside autograd's view (buffers, no gradient)
+        y, mean, rstd = ops.bn2d_fwd(x, weight, bias, bn.eps, bn.momentum, resid, relu, bn.running_mean,
+                                     bn.running_var)
+        ctx.save_for_backward(x, weight, mean, rstd, *((y,) if relu else ()))
+        ctx.relu, ctx.has_resid = relu, resid is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, mean, rstd = ctx.saved_tensors[:4]
+        y = ctx.saved_tensors[4] if ctx.relu else None
+        dy = dy.contiguous()
+        want_resid = ctx.has_resid and ctx.needs_input_grad[3]
+        dx, dresid, dgamma, dbeta = ops.bn2d_bwd(dy, x, y, weight, mean, rstd, want_dresid=want_resid and ctx.relu)
+        if want_resid and not ctx.relu:
+            dresid = dy                                   # no mask: the residual branch's gradient is dy itself
+        return dx, dgamma, dbeta, dresid, None, None
+
+
+def bn_act_nhwc(x: torch.Tensor, bn: nn.BatchNorm2d, resid: torch.Tensor = None, relu: bool = False) -> torch.Tensor:
+    """Differentiable train-mode `relu?(bn(x) (+ resid))`: x and resid fp16 NHWC [B,H,W,C] -> fp16 [B,H,W,C].  Batch
+    statistics; bn.running_mean / running_var are updated with bn.momentum and bn.num_batches_tracked counts the call,
+    as the module's own forward does.  A module this has no kernel for raises HcirError."""
+    if not isinstance(bn, nn.BatchNorm2d) or bn.momentum is None or not bn.affine or not bn.track_running_stats \
+            or not bn.training:
+        raise HcirError("bn_act_nhwc needs a train-mode BatchNorm2d with affine=True, track_running_stats=True and a "
+                        f"numeric momentum, got {bn!r} (training={getattr(bn, 'training', None)})")
+    y = _BnActNHWC.apply(x, bn.weight, bn.bias, resid, bn, bool(relu))
+    bn.num_batches_tracked.add_(1)
+    return y
+
+
+def _cvn(conv: nn.Conv2d, a: torch.Tensor) -> torch.Tensor:
+    return conv2d_nhwc(a, conv.weight, conv.stride[0], conv.padding[0])
+
+
+def _block_fused(blk: nn.Module, a: torch.Tensor) -> torch.Tensor:
+    """_block on plain fp16 [B,H,W,C] tensors with every BatchNorm2d, the residual add and the ReLUs on bn_act_nhwc."""
+    identity = a
+    out = bn_act_nhwc(_cvn(blk.conv1, a), blk.bn1, relu=True)
+    if hasattr(blk, "conv3"):
+        out = bn_act_nhwc(_cvn(blk.conv2, out), blk.bn2, relu=True)
+        out, last = _cvn(blk.conv3, out), blk.bn3
+    else:
+        out, last = _cvn(blk.conv2, out), blk.bn2
+    if blk.downsample is not None:
+        identity = bn_act_nhwc(_cvn(blk.downsample[0], a), blk.downsample[1])
+    return bn_act_nhwc(out, last, resid=identity, relu=True)
+
+
+def train_trunk_fused(trunk: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+    """train_trunk with the body's normalisation on HIP as well: x fp32 [B,3,H,W] -> fp32 [B,C].  The stem, the one
+    cast to fp16 NHWC and the fp32 average pool are torch's, as in train_trunk."""
+    _check_trunk(trunk)
+    kids = list(trunk.children())
+    a = kids[3](kids[2](kids[1](kids[0](x))))
+    a = a.permute(0, 2, 3, 1).contiguous().half()
+    for layer in kids[4:8]:
+        for blk in layer:
+            a = _block_fused(blk, a)
+    return kids[8](a.permute(0, 3, 1, 2).float()).flatten(start_dim=1)

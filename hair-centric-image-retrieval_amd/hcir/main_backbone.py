@@ -8,7 +8,8 @@ signatures (HP/src/main_backbone.py:528-637), backed by the MI355X hot path.
 
 ViT compute goes through hcir.vit_engine -> libhcir.so (hand-written HIP);
 ResNet trunks are PyTorch-ROCm modules unless `hip_trunk` (eval mode, hcir.resnet_engine) or
-`hip_train` (train mode, hcir.conv_train) is switched on.  The ViT path has no CPU
+`hip_train` (train mode, hcir.conv_train; with `hip_train_norm` the body's BatchNorm2d layers too) is switched on.  The
+ViT path has no CPU
 fallback.  With autograd enabled on parameters that require grad, `forward_cls` runs the
 training forward of hcir.vit_train (activations kept, backward through hcir_gemm_f16_tn /
 hcir_attn_bwd / hcir_layernorm_bwd ...): `SHAM2.forward` in train mode is differentiable
@@ -25,7 +26,7 @@ from torch import nn
 from . import _lib
 from ._lib import HcirError, check
 from . import _tv_resnet, _tv_vit
-from .conv_train import hip_train_active, train_trunk
+from .conv_train import hip_train_active, train_trunk, train_trunk_fused
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 from .vit_train import VitTrainer, vit_cls_with_grad
@@ -210,12 +211,17 @@ class SHAM2(nn.Module):
         # the HIP kernels (hcir.conv_train); off, or with any condition unmet, nothing changes.  The momentum twin is
         # never trained and never takes this path.
         self.hip_train = False
+        # opt-in on top of hip_train (consulted only where that switch applies): the body's BatchNorm2d layers, residual
+        # adds and ReLUs run on the HIP kernels as well (hcir.conv_train.train_trunk_fused)
+        self.hip_train_norm = False
 
     def _hip_train(self, x):
         """fp32 [B, C] differentiable features of `backbone` from hcir.conv_train, or None when the `hip_train` switch
         does not apply to this call."""
         if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
             return None
+        if self.hip_train_norm:
+            return train_trunk_fused(self.backbone, x)
         return train_trunk(self.backbone, x)
 
     def _hip_trunk(self, which: str, x):

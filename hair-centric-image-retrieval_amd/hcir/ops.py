@@ -297,3 +297,83 @@ def spread2_nhwc(src: torch.Tensor, h: int, w: int, out: Optional[torch.Tensor] 
     check(_lib.lib().hcir_spread2_nhwc_f16(src.data_ptr(), b, hs, ws, c, h, w, out.data_ptr(), _stream(src)),
           "hcir_spread2_nhwc_f16")
     return out
+
+
+# ------------------------------------------------------------------ ResNet body BatchNorm2d, training (csrc/bn2d.hip)
+def _bn2d_map(t: torch.Tensor, name: str, like: Optional[torch.Tensor] = None) -> None:
+    _dev(t, name)
+    if t.dtype != torch.float16 or t.dim() != 4:
+        raise HcirError(f"`{name}` must be an fp16 NHWC [B,H,W,C] tensor, got {t.dtype} {tuple(t.shape)}")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise HcirError(f"`{name}` {tuple(t.shape)} on {t.device} does not match {tuple(like.shape)} on {like.device}")
+
+
+def _bn2d_vec(t: torch.Tensor, name: str, x: torch.Tensor) -> None:
+    _dev(t, name)
+    if t.dtype != torch.float32 or tuple(t.shape) != (x.shape[3],) or t.device != x.device:
+        raise HcirError(f"`{name}` must be fp32 [{x.shape[3]}] on {x.device}, got {t.dtype} {tuple(t.shape)} on "
+                        f"{t.device}")
+
+
+def bn2d_chunks(m: int, c: int) -> int:
+    """Number of row chunks the BatchNorm2d reductions run an [m, c] map with; raises for a shape without a kernel."""
+    n = _lib.lib().hcir_bn2d_chunks(m, c)
+    if n < 0:
+        check(n, "hcir_bn2d_chunks")
+    return n
+
+
+def bn2d_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, momentum: float,
+             resid: Optional[torch.Tensor] = None, relu: bool = False, running_mean: Optional[torch.Tensor] = None,
+             running_var: Optional[torch.Tensor] = None):
+    """Batch-statistics BatchNorm2d (+ resid) (+ ReLU) of x fp16 NHWC [B,H,W,C] -> (y fp16 like x, save_mean fp32 [C],
+    save_rstd fp32 [C]); running_mean / running_var fp32 [C], where given, are updated in place with `momentum`
+    (the unbiased variance for running_var), as F.batch_norm(training=True) does."""
+    _bn2d_map(x, "x")
+    _bn2d_vec(gamma, "gamma", x)
+    _bn2d_vec(beta, "beta", x)
+    if resid is not None:
+        _bn2d_map(resid, "resid", x)
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _bn2d_vec(t, name, x)
+    c = x.shape[3]
+    m = x.numel() // c
+    y = torch.empty_like(x)
+    save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
+    save_rstd = torch.empty(c, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    wsb = L.hcir_bn2d_workspace_bytes(m, c)
+    ws = _ws.get(x.device, wsb)
+    check(L.hcir_bn2d_fwd_nhwc_f16(x.data_ptr(), m, c, gamma.data_ptr(), beta.data_ptr(), eps, momentum, _ptr(resid),
+                                   int(bool(relu)), _ptr(running_mean), _ptr(running_var), save_mean.data_ptr(),
+                                   save_rstd.data_ptr(), y.data_ptr(), ws.data_ptr(), wsb, _stream(x)),
+          "hcir_bn2d_fwd_nhwc_f16")
+    return y, save_mean, save_rstd
+
+
+def bn2d_bwd(dy: torch.Tensor, x: torch.Tensor, y_relu: Optional[torch.Tensor], gamma: torch.Tensor,
+             save_mean: torch.Tensor, save_rstd: torch.Tensor, want_dresid: bool = False):
+    """Backward of bn2d_fwd: -> (dx fp16 like x, dresid fp16 like x or None, dgamma fp32 [C], dbeta fp32 [C]).
+    y_relu: the forward's output when it applied ReLU (its sign is the mask), else None."""
+    _bn2d_map(x, "x")
+    _bn2d_map(dy, "dy", x)
+    if y_relu is not None:
+        _bn2d_map(y_relu, "y_relu", x)
+    _bn2d_vec(gamma, "gamma", x)
+    _bn2d_vec(save_mean, "save_mean", x)
+    _bn2d_vec(save_rstd, "save_rstd", x)
+    c = x.shape[3]
+    m = x.numel() // c
+    dx = torch.empty_like(x)
+    dresid = torch.empty_like(x) if want_dresid else None
+    dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    wsb = L.hcir_bn2d_workspace_bytes(m, c)
+    ws = _ws.get(x.device, wsb)
+    check(L.hcir_bn2d_bwd_nhwc_f16(dy.data_ptr(), x.data_ptr(), _ptr(y_relu), m, c, gamma.data_ptr(),
+                                   save_mean.data_ptr(), save_rstd.data_ptr(), dx.data_ptr(), _ptr(dresid),
+                                   dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), wsb, _stream(x)),
+          "hcir_bn2d_bwd_nhwc_f16")
+    return dx, dresid, dgamma, dbeta

@@ -788,6 +788,43 @@ int32_t hcir_conv2d_wgrad_splits(int64_t b, int32_t h, int32_t w, int32_t cin, i
 int hcir_spread2_nhwc_f16(const void* src, int64_t b, int32_t hs, int32_t ws, int32_t c, int32_t h, int32_t w,
                           void* dst, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * ResNet-18 / ResNet-50 body normalisation in training: batch-statistics BatchNorm2d, optionally with the block's
+ * residual add and ReLU, forward and backward (csrc/bn2d.hip; hcir/conv_train.py, the model's `hip_train_norm`
+ * switch).  Serves the torchvision BatchNorm2d / ReLU / `out += identity` behind HP/src/main_backbone.py:576-579 in
+ * the step of HP/src/pretrain_engine.py:682-747.
+ * Maps are fp16 NHWC viewed as [m = B*H*W][c]; parameters, statistics and their gradients fp32 [c].  fp32 arithmetic,
+ * each stored activation rounded to fp16 once; the m rows are cut into hcir_bn2d_chunks(m, c) contiguous ranges whose
+ * partial results go to `workspace` ([chunk][c][2] fp32) and are merged in a fixed order: no atomics, two calls give
+ * the same bits.  Statuses, decided from the shape alone before a pointer is looked at: HCIR_ERR_UNSUPPORTED unless
+ * c % 64 == 0 and 64 <= c <= 65536 (and m < 2^31), HCIR_ERR_INVALID for m < 2 (one value per channel has no variance)
+ * or a required pointer that is NULL, HCIR_ERR_WORKSPACE when `workspace_bytes` is below
+ * hcir_bn2d_workspace_bytes(m, c).  The entry points allocate nothing and do not synchronise.
+ * ------------------------------------------------------------------ */
+
+/* y = fp16(relu?((x - mean) * rstd * gamma + beta (+ resid))) with mean and the biased variance of this batch
+ * (F.batch_norm(training=True)).  Three launches: per-chunk (mean, M2) from shifted sums, a merge by Chan's formula
+ * that writes save_mean [c] and save_rstd [c] = 1 / sqrt(var_biased + eps) and, where running_mean / running_var are
+ * not NULL, running = (1 - momentum) * running + momentum * (mean | M2 / (m - 1)), then the elementwise pass.
+ * resid: fp16 [m][c] or NULL; relu: 0 / 1. */
+int hcir_bn2d_fwd_nhwc_f16(const void* x, int64_t m, int32_t c, const float* gamma, const float* beta, float eps,
+                           float momentum, const void* resid, int relu, float* running_mean, float* running_var,
+                           float* save_mean, float* save_rstd, void* y, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* Backward of the above.  g = dy, or dy where y_relu > 0 and 0 elsewhere when y_relu (the forward's output y of a call
+ * with relu = 1) is not NULL; xhat = (x - mean) * rstd.  dbeta = sum g, dgamma = sum g * xhat (fp32 [c]),
+ * dx = fp16(gamma * rstd * (g - dbeta / m - xhat * dgamma / m)), and, where dresid is not NULL, dresid = fp16(g): the
+ * gradient of the residual branch, exactly dy or 0.  Three launches: per-chunk sums, their merge, the elementwise
+ * pass. */
+int hcir_bn2d_bwd_nhwc_f16(const void* dy, const void* x, const void* y_relu, int64_t m, int32_t c,
+                           const float* gamma, const float* save_mean, const float* save_rstd, void* dx, void* dresid,
+                           float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* HOST.  Workspace of either call for a shape: chunks * c * 2 * 4 bytes; 0 when the shape has no kernel. */
+size_t hcir_bn2d_workspace_bytes(int64_t m, int32_t c);
+/* HOST.  Number of row chunks the reductions run the shape with (a test uses it to know which path a case
+ * exercised).  Negative: the status the entry points return for the shape. */
+int32_t hcir_bn2d_chunks(int64_t m, int32_t c);
+
 #ifdef __cplusplus
 }
 #endif

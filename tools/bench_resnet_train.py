@@ -1,18 +1,20 @@
 """ResNet-18 / ResNet-50 trunk TRAINING timings on one GPU: forward + backward of the trunk at 224 x 224 (recorded in
 DESIGN.md §3.4, not gated; bench.py is the contract).
 
-Four paths, same process, same machine, same input; median over --steps iterations after --warmup (HIP events around
+Five paths, same process, same machine, same input; median over --steps iterations after --warmup (HIP events around
 forward + backward of loss = features.sum(); gradients are dropped between iterations, no optimizer):
   torch_fp32                 the torch trunk as SHAMTrainStep runs it today (fp32 NCHW, MIOpen)
   torch_autocast             torch.autocast(fp16), the reference's way (HP/src/pretrain_engine.py:681)
   torch_autocast_chlast      the same on a channels_last trunk and input: the fair vendor yardstick
   hip_train                  the model's `hip_train` switch: hcir.conv_train (body convolutions on the HIP kernels)
-then ONE more hip_train iteration with every libhcir call bracketed by HIP events, which splits its device time into
-forward convolutions, data gradients by plan (stride 1; 1x1 stride 2; the 3x3 stride 2 that does 4x the useful
-flops - each with its spread-by-2 copy), weight gradients, and the rest (torch: stem, BatchNorm, ReLU, adds, casts,
-pool).  Events, not a profiler's kernel trace: forward and data gradient run the SAME kernel and only the call site
-tells them apart.
-One JSON line per (model, batch).
+  hip_train_norm             `hip_train` and `hip_train_norm`: the body's BatchNorm2d + residual + ReLU on HIP as well
+then ONE more iteration of each of the last two with every libhcir call bracketed by HIP events, which splits its
+device time into forward convolutions, data gradients by plan (stride 1; 1x1 stride 2; the 3x3 stride 2 that does 4x
+the useful flops - each with its spread-by-2 copy), weight gradients, BatchNorm forward / backward (HIP; the second
+path only) and the rest (torch: stem, casts, pool and, on the first path, BatchNorm, ReLU, adds).  Events, not a
+profiler's kernel trace: forward and data gradient run the SAME kernel and only the call site tells them apart.
+One JSON line per (model, batch).  --bn2d-bandwidth adds one line: the BatchNorm2d entry points alone at ResNet-50's
+layer1 shape (M = 256 * 56 * 56, C = 256), in bytes the algorithm must move per second.
 
   python tools/bench_resnet_train.py [--model resnet50,resnet18] [--batch 64,256] [--steps 10] [--warmup 3]
 """
@@ -54,7 +56,8 @@ def fwd_bwd(features, params):
 
 def kernel_shares(model, x):
     """Device time of one hip_train forward + backward by kind of libhcir work (HIP events around every forward
-    convolution, every data gradient - its spread-by-2 copy included - and every weight gradient)."""
+    convolution, every data gradient - its spread-by-2 copy included - every weight gradient and, with
+    `hip_train_norm` on, every BatchNorm forward and backward)."""
     from hcir import conv_train, ops
     spans = []
     inside = {"dgrad": False}
@@ -68,6 +71,7 @@ def kernel_shares(model, x):
         return out
 
     real_conv, real_wgrad, real_dgrad = ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad
+    real_bn_fwd, real_bn_bwd = ops.bn2d_fwd, ops.bn2d_bwd
 
     def conv(*a, **k):
         return real_conv(*a, **k) if inside["dgrad"] else bracket("forward", real_conv, *a, **k)
@@ -82,6 +86,8 @@ def kernel_shares(model, x):
 
     ops.conv2d_f16, conv_train.conv2d_dgrad = conv, dgrad
     ops.conv2d_wgrad = lambda *a, **k: bracket("wgrad", real_wgrad, *a, **k)
+    ops.bn2d_fwd = lambda *a, **k: bracket("bn_forward_hip", real_bn_fwd, *a, **k)
+    ops.bn2d_bwd = lambda *a, **k: bracket("bn_backward_hip", real_bn_bwd, *a, **k)
     try:
         for p in model.backbone.parameters():
             p.grad = None
@@ -92,6 +98,7 @@ def kernel_shares(model, x):
         torch.cuda.synchronize()
     finally:
         ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad = real_conv, real_wgrad, real_dgrad
+        ops.bn2d_fwd, ops.bn2d_bwd = real_bn_fwd, real_bn_bwd
     total = t0.elapsed_time(t1)
     by = {}
     for label, e0, e1 in spans:
@@ -101,12 +108,32 @@ def kernel_shares(model, x):
             "share": {k: round(v / total, 4) for k, v in sorted(by.items())}}
 
 
+def bn2d_bandwidth(dev, warmup, steps, b=256, hw=56, c=256):
+    """ops.bn2d_fwd / ops.bn2d_bwd alone (residual + ReLU, the block-closing form): median ms and the bytes the
+    algorithm must move (forward: x twice, resid, y; backward: dy, x, y twice each, dx, dresid) per second."""
+    from hcir import ops
+    g = torch.Generator(device=dev).manual_seed(0)
+    shape = (b, hw, hw, c)
+    x, r, dy = (torch.randn(shape, device=dev, dtype=torch.float16, generator=g) for _ in range(3))
+    gamma = torch.rand(c, device=dev, generator=g) + 0.5
+    beta = torch.randn(c, device=dev, generator=g) * 0.2
+    y, mean, rstd = ops.bn2d_fwd(x, gamma, beta, 1e-5, 0.1, r, True)
+    nbytes = x.numel() * 2
+    f_ms = median_ms(lambda: ops.bn2d_fwd(x, gamma, beta, 1e-5, 0.1, r, True), warmup, steps)
+    b_ms = median_ms(lambda: ops.bn2d_bwd(dy, x, y, gamma, mean, rstd, want_dresid=True), warmup, steps)
+    return {"bn2d_bandwidth": {"shape": list(shape), "chunks": ops.bn2d_chunks(b * hw * hw, c),
+                               "fwd_ms": round(f_ms, 4), "fwd_TBps": round(4 * nbytes / f_ms / 1e9, 3),
+                               "bwd_ms": round(b_ms, 4), "bwd_TBps": round(8 * nbytes / b_ms / 1e9, 3),
+                               "counted_bytes": {"fwd": 4 * nbytes, "bwd": 8 * nbytes}}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="resnet50,resnet18")
     ap.add_argument("--batch", default="64,256")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--bn2d-bandwidth", action="store_true")
     args = ap.parse_args()
 
     from hcir.main_backbone import SHAM2
@@ -138,13 +165,23 @@ def main():
             ms["hip_train"] = median_ms(fwd_bwd(lambda: model.extract_features(x), list(trunk.parameters())),
                                         args.warmup, args.steps)
             shares = kernel_shares(model, x)
+            model.hip_train_norm = True
+            ms["hip_train_norm"] = median_ms(fwd_bwd(lambda: model.extract_features(x), list(trunk.parameters())),
+                                             args.warmup, args.steps)
+            shares_norm = kernel_shares(model, x)
+            model.hip_train_norm = False
             out = {"model": name, "batch": b, "steps": args.steps,
                    "ms": {k: round(v, 3) for k, v in ms.items()},
                    "img_per_s": {k: round(b / v * 1e3, 1) for k, v in ms.items()},
                    "fastest": min(ms, key=ms.get),
-                   "hip_train_vs": {k: round(ms["hip_train"] / v, 3) for k, v in ms.items() if k != "hip_train"},
-                   "hip_train_breakdown": shares}
+                   "hip_train_vs": {k: round(ms["hip_train"] / v, 3) for k, v in ms.items()
+                                    if k not in ("hip_train", "hip_train_norm")},
+                   "hip_train_norm_vs": {k: round(ms["hip_train_norm"] / v, 3) for k, v in ms.items()
+                                         if k != "hip_train_norm"},
+                   "hip_train_breakdown": shares, "hip_train_norm_breakdown": shares_norm}
             print(json.dumps(out), flush=True)
+    if args.bn2d_bandwidth:
+        print(json.dumps(bn2d_bandwidth(dev, args.warmup, args.steps)), flush=True)
 
 
 if __name__ == "__main__":

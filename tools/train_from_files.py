@@ -63,6 +63,9 @@ def main():
     ap.add_argument("--max-steps", type=int, default=0)
     ap.add_argument("--hip-train", action="store_true",
                     help="ResNet models: body convolutions forward and backward on the HIP kernels (hcir.conv_train)")
+    ap.add_argument("--hip-train-norm", action="store_true",
+                    help="ResNet models: the body's BatchNorm2d + residual + ReLU on the HIP kernels as well "
+                         "(implies --hip-train)")
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
@@ -73,7 +76,8 @@ def main():
                                          num_workers=a.workers, collate_fn=functools.partial(collate_train_views),
                                          pin_memory=False)
     model = SHAM2(a.model).cuda()
-    model.hip_train = a.hip_train
+    model.hip_train = a.hip_train or a.hip_train_norm
+    model.hip_train_norm = a.hip_train_norm
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
     step = SHAMTrainStep(model, opt, torch.amp.GradScaler("cuda"), warm_up_epochs=a.warm_up_epochs)
 
