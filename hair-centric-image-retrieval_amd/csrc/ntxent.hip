@@ -365,6 +365,7 @@ int hcir_ntxent_bwd(const void* z0, const void* z1, int64_t b, int32_t d, int dt
                     size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
   if (!z0 || !z1 || !row_lse || !dz0 || !dz1 || b <= 0 || d <= 0 || (d & 7) || (b & 3)) return HCIR_ERR_INVALID;
+  if (!(inv_t == inv_t) || inv_t == 0.f) return HCIR_ERR_INVALID;  // as hcir_ntxent_fwd: no gradient of a loss it refuses
   if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
   const NtWorkspace w = nt_carve(workspace, b, d, dtype, true);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;

@@ -124,6 +124,9 @@ int hcir_topk_merge(const float* vals, const int64_t* idx, int32_t nlists, int64
  *   loss = mean_i ( logsumexp_{j != i} logits[i][j] - logits[i][pos(i)] ).
  * Outputs: loss (1 float), row_lse[2B] (saved for a backward pass, may be NULL).
  * The 2B x 2B logits are never materialised.  d % 8 == 0.
+ * Status: HCIR_ERR_INVALID for a null z0/z1/loss, b <= 0, d <= 0, d % 8 != 0, inv_t == 0 or NaN;
+ * HCIR_ERR_UNSUPPORTED for a dtype other than HCIR_F32/F16/BF16; HCIR_ERR_WORKSPACE for a null or short
+ * workspace.  Nothing is written on an error.
  * ------------------------------------------------------------------ */
 size_t hcir_ntxent_workspace_bytes(int64_t b, int32_t d, int dtype);
 int hcir_ntxent_fwd(const void* z0, const void* z1, int64_t b, int32_t d, int dtype,
@@ -134,7 +137,8 @@ int hcir_ntxent_fwd(const void* z0, const void* z1, int64_t b, int32_t d, int dt
  *   G = (P - Y)/2B,  dU = (1/T)(G + G^T) U,  dz_i = grad_out * (dU_i - (dU_i.u_i) u_i) / ||z_i||
  * W = P + P^T - 2Y is written once as fp16 [2B][2B] into the workspace and dU = W.U runs on
  * hcir_gemm_f16 (fp16 MFMA: gradients carry fp16-level relative error for every input dtype).
- * row_lse: the [2B] vector saved by hcir_ntxent_fwd.  Requirements: d % 8 == 0, b % 4 == 0. */
+ * row_lse: the [2B] vector saved by hcir_ntxent_fwd.  Requirements: d % 8 == 0, b % 4 == 0.
+ * Statuses as hcir_ntxent_fwd (a null row_lse/dz0/dz1 and b % 4 != 0 are HCIR_ERR_INVALID too). */
 size_t hcir_ntxent_bwd_workspace_bytes(int64_t b, int32_t d, int dtype);
 int hcir_ntxent_bwd(const void* z0, const void* z1, int64_t b, int32_t d, int dtype, float inv_t,
                     const float* row_lse, float grad_out, void* dz0, void* dz1, void* workspace,
