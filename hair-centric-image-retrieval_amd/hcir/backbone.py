@@ -16,13 +16,11 @@ import torch
 from torch import nn
 
 from . import _tv_resnet, models_vit
-from .main_backbone import SimCLRProjectionHead, ViTWrapper
-from .conv_train import hip_train_active, train_trunk, train_trunk_fused
-from .resnet_engine import ResNetEngineCache, hip_trunk_active
+from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper
 from .vit_engine import EngineCache, VitLayer, VitSpec
 
 
-class SimCLR(nn.Module):
+class SimCLR(HipTrunkSwitches, nn.Module):
     def __init__(self, model="resnet18"):
         super().__init__()
         self.model = model
@@ -41,25 +39,6 @@ class SimCLR(nn.Module):
         else:
             raise ValueError(f"Unsupported model: {model}")
         self.projection_head = SimCLRProjectionHead(proj_input_dim, proj_input_dim, output_dim)
-        # opt-in HIP trunk for the ResNets (eval mode, HIP device, no_grad), as in SHAM2
-        self.hip_trunk = False
-        self._trunk_cache = ResNetEngineCache()
-        # opt-in HIP body convolutions for a ResNet in train mode with autograd on, as in SHAM2
-        self.hip_train = False
-        # opt-in on top of hip_train: the body's BatchNorm2d, residual adds and ReLUs on HIP as well, as in SHAM2
-        self.hip_train_norm = False
-
-    def _hip_train(self, x):
-        if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
-            return None
-        if self.hip_train_norm:
-            return train_trunk_fused(self.backbone, x)
-        return train_trunk(self.backbone, x)
-
-    def _hip_trunk(self, x):
-        if "vit" in self.model or not hip_trunk_active(self.hip_trunk, self.backbone, x):
-            return None
-        return self._trunk_cache.get(self.backbone, x.device).forward(x)
 
     def forward(self, x):
         if "vit" in self.model:
@@ -67,21 +46,15 @@ class SimCLR(nn.Module):
             # (HP/src/backbone.py:675-681).  Defined as SHAM2 does: project CLS.
             _, cls16 = self.backbone.forward_cls(x, want_f16=True)
             return self.projection_head.forward_hip(cls16)
-        f = self._hip_trunk(x)
-        if f is not None:
-            head = self.projection_head
-            return head(f) if head.training else head.forward_hip(f.half())
-        f = self._hip_train(x)
-        if f is not None:
-            return self.projection_head(f)
+        out = self._hip_features("backbone", x, self.projection_head)
+        if out is not None:
+            return out
         return self.projection_head(self.backbone(x).flatten(start_dim=1))
 
     def extract_features(self, x):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
-        f = self._hip_trunk(x)
-        if f is None:
-            f = self._hip_train(x)
+        f = self._hip_features("backbone", x)
         if f is not None:
             return f
         return self.backbone(x).flatten(start_dim=1)

@@ -20,22 +20,25 @@ modules, called on channels-last fp16 tensors.  torch's batch norm takes fp16 in
 under autocast (batch_norm is on neither autocast list: it runs in its input's dtype), so no autocast region is needed.
 
 With the model's second switch, `hip_train_norm`, on as well, the body's BatchNorm2d layers leave torch too
-(train_trunk_fused): bn_act_nhwc runs batch statistics, normalisation, the block's residual add and its ReLU as one
-pass over the fp16 NHWC map, forward and backward (hcir_bn2d_fwd_nhwc_f16 / hcir_bn2d_bwd_nhwc_f16, csrc/bn2d.hip), and
-updates the module's running statistics in the kernel.  The stem, the cast to fp16 NHWC and the average pool stay
-torch's on that path as well.
+(train_trunk with fused_norm=True): bn_act_nhwc runs batch statistics, normalisation, the block's residual add and its
+ReLU as one pass over the fp16 NHWC map, forward and backward (hcir_bn2d_fwd_nhwc_f16 / hcir_bn2d_bwd_nhwc_f16,
+csrc/bn2d.hip), and updates the module's running statistics in the kernel.  The stem, the cast to fp16 NHWC and the
+average pool stay torch's on that path as well.
+
+Both paths are one walk (walk) over resnet_engine's table of the body - which conv feeds which, where the residual
+enters, where the ReLU sits are written down there, once - with one of two `norm` callables: torch_norm or bn_act_nhwc.
 """
 from __future__ import annotations
 
 import weakref
-from typing import Tuple
+from typing import Callable, Sequence, Tuple
 
 import torch
 from torch import nn
 
 from . import ops
 from ._lib import HcirError
-from .resnet_engine import layer_table, pack_conv_weight
+from .resnet_engine import ConvSpec, layer_table, pack_conv_weight
 
 
 class _WeightCache:
@@ -131,62 +134,7 @@ def conv2d_nhwc(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) ->
     return _Conv2dNHWC.apply(x, weight, stride, pad)
 
 
-_checked = weakref.WeakKeyDictionary()
-
-
-def _check_trunk(trunk: nn.Module) -> None:
-    """resnet_engine's structure checks (stem, pooling, every body conv has a kernel), once per trunk object and
-    number of modules."""
-    n = sum(1 for _ in trunk.modules())
-    if _checked.get(trunk) != n:
-        layer_table(trunk)
-        _checked[trunk] = n
-
-
-def _cv(conv: nn.Conv2d, a: torch.Tensor) -> torch.Tensor:
-    # `a` is a logical [B,C,H,W] view of an NHWC tensor (what the BatchNorm2d modules take); so is the result
-    y = conv2d_nhwc(a.permute(0, 2, 3, 1), conv.weight, conv.stride[0], conv.padding[0])
-    return y.permute(0, 3, 1, 2)
-
-
-def _block(blk: nn.Module, a: torch.Tensor) -> torch.Tensor:
-    """torchvision BasicBlock.forward / Bottleneck.forward with the convolutions on conv2d_nhwc."""
-    identity = a
-    out = blk.relu(blk.bn1(_cv(blk.conv1, a)))
-    if hasattr(blk, "conv3"):
-        out = blk.relu(blk.bn2(_cv(blk.conv2, out)))
-        out = blk.bn3(_cv(blk.conv3, out))
-    else:
-        out = blk.bn2(_cv(blk.conv2, out))
-    if blk.downsample is not None:
-        identity = blk.downsample[1](_cv(blk.downsample[0], a))
-    out = out + identity
-    return blk.relu(out)
-
-
-def train_trunk(trunk: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    """The differentiable train-mode walk of nn.Sequential(children()[:-1]): x fp32 [B,3,H,W] -> fp32 [B,C]."""
-    _check_trunk(trunk)
-    kids = list(trunk.children())
-    a = kids[3](kids[2](kids[1](kids[0](x))))
-    # the one cast and layout change: fp16, NHWC in memory (a channels-last [B,C,H,W] tensor)
-    a = a.permute(0, 2, 3, 1).contiguous().half().permute(0, 3, 1, 2)
-    for layer in kids[4:8]:
-        for blk in layer:
-            a = _block(blk, a)
-    return kids[8](a.float()).flatten(start_dim=1)
-
-
-def hip_train_active(enabled: bool, trunk: nn.Module, x: torch.Tensor) -> bool:
-    """The conditions under which a model's `hip_train` switch routes a ResNet trunk through train_trunk: switched
-    on, trunk in train mode, autograd on, and an fp32 [B >= 1, 3, H >= 7, W >= 7] tensor on a HIP device.  Any other
-    call keeps the code it had."""
-    return (bool(enabled) and trunk.training and torch.is_grad_enabled() and x.is_cuda
-            and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] == 3
-            and x.shape[2] >= 7 and x.shape[3] >= 7)
-
-
-# ------------------------------------------------------------------ the `hip_train_norm` walk: BatchNorm2d on HIP too
+# --------------------------------------------- `hip_train_norm`: BatchNorm2d + residual + ReLU on HIP (bn_act_nhwc)
 class _BnActNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, resid, bn, relu):
@@ -225,32 +173,52 @@ def bn_act_nhwc(x: torch.Tensor, bn: nn.BatchNorm2d, resid: torch.Tensor = None,
     return y
 
 
-def _cvn(conv: nn.Conv2d, a: torch.Tensor) -> torch.Tensor:
-    return conv2d_nhwc(a, conv.weight, conv.stride[0], conv.padding[0])
+# ------------------------------------------------------------------------------------ the train-mode walk of the body
+def torch_norm(y: torch.Tensor, bn: nn.BatchNorm2d, resid: torch.Tensor = None, relu: bool = False) -> torch.Tensor:
+    """bn_act_nhwc's contract on the module's own torch forward (`hip_train` alone): BatchNorm2d sees the logical
+    [B,C,H,W] view of the NHWC map, as under channels-last; the ReLU is in place, as torchvision's block.relu is."""
+    y = bn(y.permute(0, 3, 1, 2))
+    if resid is not None:
+        y = y + resid.permute(0, 3, 1, 2)
+    if relu:
+        y = torch.relu_(y)
+    return y.permute(0, 2, 3, 1)
 
 
-def _block_fused(blk: nn.Module, a: torch.Tensor) -> torch.Tensor:
-    """_block on plain fp16 [B,H,W,C] tensors with every BatchNorm2d, the residual add and the ReLUs on bn_act_nhwc."""
-    identity = a
-    out = bn_act_nhwc(_cvn(blk.conv1, a), blk.bn1, relu=True)
-    if hasattr(blk, "conv3"):
-        out = bn_act_nhwc(_cvn(blk.conv2, out), blk.bn2, relu=True)
-        out, last = _cvn(blk.conv3, out), blk.bn3
-    else:
-        out, last = _cvn(blk.conv2, out), blk.bn2
-    if blk.downsample is not None:
-        identity = bn_act_nhwc(_cvn(blk.downsample[0], a), blk.downsample[1])
-    return bn_act_nhwc(out, last, resid=identity, relu=True)
+def conv_nhwc(a: torch.Tensor, sp: ConvSpec) -> torch.Tensor:
+    return conv2d_nhwc(a, sp.conv.weight, sp.stride, sp.pad)
 
 
-def train_trunk_fused(trunk: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    """train_trunk with the body's normalisation on HIP as well: x fp32 [B,3,H,W] -> fp32 [B,C].  The stem, the one
-    cast to fp16 NHWC and the fp32 average pool are torch's, as in train_trunk."""
-    _check_trunk(trunk)
+def walk(table: Sequence[ConvSpec], a: torch.Tensor, conv: Callable = conv_nhwc,
+         norm: Callable = bn_act_nhwc) -> torch.Tensor:
+    """The train-mode pass over resnet_engine's table (block_table of one block, layer_table of a trunk) on plain NHWC
+    tensors [B,H,W,C]: per spec `norm(conv(input, spec), spec.bn, residual, spec.relu)`, the tensors named as in
+    ConvSpec.  A block's output "y" is the next block's "x", and nothing else outlives the block."""
+    live = {"x": a}
+    for sp in table:
+        live[sp.out] = norm(conv(live[sp.inp], sp), sp.bn, live[sp.resid] if sp.resid else None, sp.relu)
+        if sp.out == "y":
+            live = {"x": live["y"]}
+    return live["x"]
+
+
+def train_trunk(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool = False) -> torch.Tensor:
+    """The differentiable train-mode walk of nn.Sequential(children()[:-1]): x fp32 [B,3,H,W] -> fp32 [B,C].  The stem,
+    the one cast to fp16 NHWC and the fp32 average pool are torch's; the body's BatchNorm2d, residual adds and ReLUs
+    are torch's as well (torch_norm) unless `fused_norm` puts them on bn_act_nhwc.  The table is rebuilt, and with it
+    resnet_engine's structure checks (stem, pooling, every body conv has a kernel) are repeated, on every call: an
+    edited trunk raises HcirError whenever the edit was made (host cost: DESIGN.md §3.4)."""
+    table = layer_table(trunk)
     kids = list(trunk.children())
     a = kids[3](kids[2](kids[1](kids[0](x))))
-    a = a.permute(0, 2, 3, 1).contiguous().half()
-    for layer in kids[4:8]:
-        for blk in layer:
-            a = _block_fused(blk, a)
+    a = walk(table, a.permute(0, 2, 3, 1).contiguous().half(), norm=bn_act_nhwc if fused_norm else torch_norm)
     return kids[8](a.permute(0, 3, 1, 2).float()).flatten(start_dim=1)
+
+
+def hip_train_active(enabled: bool, trunk: nn.Module, x: torch.Tensor) -> bool:
+    """The conditions under which a model's `hip_train` switch routes a ResNet trunk through train_trunk: switched
+    on, trunk in train mode, autograd on, and an fp32 [B >= 1, 3, H >= 7, W >= 7] tensor on a HIP device.  Any other
+    call keeps the code it had."""
+    return (bool(enabled) and trunk.training and torch.is_grad_enabled() and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] == 3
+            and x.shape[2] >= 7 and x.shape[3] >= 7)

@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib
 from ._lib import HcirError, check
 from . import _tv_resnet, _tv_vit
-from .conv_train import hip_train_active, train_trunk, train_trunk_fused
+from .conv_train import hip_train_active, train_trunk
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 from .vit_train import VitTrainer, vit_cls_with_grad
@@ -173,7 +173,50 @@ class ViTWrapper(nn.Module):
         return eng.cls_embedding(tok, final_norm=True, l2_normalize=l2_normalize, want_f16=want_f16)
 
 
-class SHAM2(nn.Module):
+class HipTrunkSwitches:
+    """The opt-in HIP paths of a model with ResNet trunks (SHAM2, hcir.backbone.SimCLR): the three switches, the engine
+    caches and the one place that decides which path a call takes.  A plain mixin, not a Module: no state_dict key.
+
+      hip_trunk        trunks in eval mode, on a HIP device, under no_grad run on hcir.resnet_engine (the HIP convolution
+                       kernels) instead of torch / MIOpen
+      hip_train        the trunk in train mode with autograd on runs its body convolutions, forward and backward, on the
+                       HIP kernels (hcir.conv_train.train_trunk)
+      hip_train_norm   on top of hip_train (consulted only where that switch applies): the body's BatchNorm2d layers,
+                       residual adds and ReLUs run on the HIP kernels as well (train_trunk with fused_norm=True)
+
+    Off, or with any condition of hip_trunk_active / hip_train_active unmet, a call keeps the torch path untouched."""
+
+    hip_trunk = False
+    hip_train = False
+    hip_train_norm = False
+
+    def trunk_engine(self, which: str, device: torch.device):
+        """The ResNetEngine of trunk attribute `which` ("backbone", "backbone_momentum"), from that trunk's own cache."""
+        caches = self.__dict__.setdefault("_trunk_caches", {})
+        return caches.setdefault(which, ResNetEngineCache()).get(getattr(self, which), device)
+
+    @staticmethod
+    def _project(head, f):
+        # eval-mode head on the two affine-epilogue GEMMs (forward_hip); a head in train mode keeps its torch modules
+        return head(f) if head.training else head.forward_hip(f.half())
+
+    def _hip_features(self, which: str, x, head=None, walk: bool = True):
+        """fp32 [B, C] features of trunk attribute `which` from the eval engine or, where `walk` allows it (never for
+        a momentum trunk, which is not trained), from the differentiable train-mode walk - through `head`, when one is
+        given - or None when no switch applies to this call."""
+        trunk = getattr(self, which)
+        if "vit" in self.model:
+            return None
+        if hip_trunk_active(self.hip_trunk, trunk, x):
+            f = self.trunk_engine(which, x.device).forward(x)
+            return f if head is None else self._project(head, f)
+        if walk and hip_train_active(self.hip_train, trunk, x):
+            f = train_trunk(trunk, x, fused_norm=bool(self.hip_train_norm))
+            return f if head is None else head(f)
+        return None
+
+
+class SHAM2(HipTrunkSwitches, nn.Module):
     """HSimCLR model (README 'HSimCLR' == class SHAM2, HP/src/main_backbone.py:565-637)."""
 
     def __init__(self, model="resnet18"):
@@ -203,41 +246,6 @@ class SHAM2(nn.Module):
         deactivate_requires_grad(self.backbone_momentum)
         deactivate_requires_grad(self.projection_head_momentum)
 
-        # opt-in: ResNet trunks in eval mode, on a HIP device, under no_grad run on hcir.resnet_engine (the HIP
-        # convolution kernels) instead of torch / MIOpen; off, or with any condition unmet, the torch path is untouched
-        self.hip_trunk = False
-        self._trunk_caches = {}
-        # opt-in: ResNet trunks in train mode with autograd on run their body convolutions, forward and backward, on
-        # the HIP kernels (hcir.conv_train); off, or with any condition unmet, nothing changes.  The momentum twin is
-        # never trained and never takes this path.
-        self.hip_train = False
-        # opt-in on top of hip_train (consulted only where that switch applies): the body's BatchNorm2d layers, residual
-        # adds and ReLUs run on the HIP kernels as well (hcir.conv_train.train_trunk_fused)
-        self.hip_train_norm = False
-
-    def _hip_train(self, x):
-        """fp32 [B, C] differentiable features of `backbone` from hcir.conv_train, or None when the `hip_train` switch
-        does not apply to this call."""
-        if "vit" in self.model or not hip_train_active(self.hip_train, self.backbone, x):
-            return None
-        if self.hip_train_norm:
-            return train_trunk_fused(self.backbone, x)
-        return train_trunk(self.backbone, x)
-
-    def _hip_trunk(self, which: str, x):
-        """fp32 [B, C] features of `backbone` / `backbone_momentum` from the HIP engine, or None when the switch
-        does not apply to this call."""
-        trunk = getattr(self, which)
-        if "vit" in self.model or not hip_trunk_active(self.hip_trunk, trunk, x):
-            return None
-        cache = self._trunk_caches.setdefault(which, ResNetEngineCache())
-        return cache.get(trunk, x.device).forward(x)
-
-    @staticmethod
-    def _project(head, f):
-        # eval-mode head on the two affine-epilogue GEMMs (forward_hip); a head in train mode keeps its torch modules
-        return head(f) if head.training else head.forward_hip(f.half())
-
     def _vit_project(self, backbone, head, x):
         if head.training:
             # train mode (HP/src/pretrain_engine.py:603 model.train()): the backbone forward is differentiable on the
@@ -250,12 +258,9 @@ class SHAM2(nn.Module):
     def forward(self, x):
         if "vit" in self.model:
             return self._vit_project(self.backbone, self.projection_head, x)
-        f = self._hip_trunk("backbone", x)
-        if f is not None:
-            return self._project(self.projection_head, f)
-        f = self._hip_train(x)
-        if f is not None:
-            return self.projection_head(f)
+        out = self._hip_features("backbone", x, self.projection_head)
+        if out is not None:
+            return out
         x = self.backbone(x).flatten(start_dim=1)
         return self.projection_head(x)
 
@@ -276,18 +281,16 @@ class SHAM2(nn.Module):
     def forward_momentum(self, x):
         if "vit" in self.model:
             return self._vit_project(self.backbone_momentum, self.projection_head_momentum, x)
-        f = self._hip_trunk("backbone_momentum", x)
-        if f is not None:
-            return self._project(self.projection_head_momentum, f)
+        out = self._hip_features("backbone_momentum", x, self.projection_head_momentum, walk=False)
+        if out is not None:
+            return out
         x = self.backbone_momentum(x).flatten(start_dim=1)
         return self.projection_head_momentum(x)
 
     def extract_features(self, x):
         if "vit" in self.model:
             return self.backbone.forward_cls(x)
-        f = self._hip_trunk("backbone", x)
-        if f is None:
-            f = self._hip_train(x)
+        f = self._hip_features("backbone", x)
         if f is not None:
             return f
         return self.backbone(x).flatten(start_dim=1)
@@ -296,7 +299,7 @@ class SHAM2(nn.Module):
     def extract_features_ema(self, x):
         if "vit" in self.model:
             return self.backbone_momentum.forward_cls(x)
-        f = self._hip_trunk("backbone_momentum", x)
+        f = self._hip_features("backbone_momentum", x, walk=False)
         if f is not None:
             return f
         return self.backbone_momentum(x).flatten(start_dim=1)

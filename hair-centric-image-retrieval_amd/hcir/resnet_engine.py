@@ -126,30 +126,31 @@ def _check_stem(kids) -> None:
         raise HcirError(f"expected AdaptiveAvgPool2d((1, 1)) at the end of the trunk, got {avg}")
 
 
+def block_table(blk: nn.Module, group: str = "", prefix: str = "") -> List[ConvSpec]:
+    """The convolutions of one torchvision BasicBlock / Bottleneck, in execution order: the downsample conv first (it
+    writes the residual); the last conv carries the residual add and the block's single ReLU.  The one description of
+    a block's wiring: ResNetEngine.forward and conv_train.walk both run it."""
+    table, resid = [], "x"
+    if blk.downsample is not None:
+        table.append(_spec(prefix + "downsample", group, blk.downsample[0], blk.downsample[1], False, "x", "ds"))
+        resid = "ds"
+    table.append(_spec(prefix + "conv1", group, blk.conv1, blk.bn1, True, "x", "o1"))
+    if hasattr(blk, "conv3"):
+        table.append(_spec(prefix + "conv2", group, blk.conv2, blk.bn2, True, "o1", "o2"))
+        table.append(_spec(prefix + "conv3", group, blk.conv3, blk.bn3, True, "o2", "y", resid))
+    else:
+        table.append(_spec(prefix + "conv2", group, blk.conv2, blk.bn2, True, "o1", "y", resid))
+    return table
+
+
 def layer_table(trunk: nn.Sequential) -> List[ConvSpec]:
-    """The trunk's convolutions after the stem, in execution order.  Within a block the downsample conv comes first
-    (it writes the residual); the last conv carries the residual add and the block's single ReLU."""
+    """The trunk's convolutions after the stem, in execution order: block_table of every block of layer1..4."""
     kids = list(trunk.children())
     if len(kids) != 9 or not isinstance(kids[0], nn.Conv2d) or not isinstance(kids[3], nn.MaxPool2d):
         raise HcirError("expected nn.Sequential(conv1, bn1, relu, maxpool, layer1..4, avgpool)")
     _check_stem(kids)
-    table: List[ConvSpec] = []
-    for li, layer in enumerate(kids[4:8], start=1):
-        g = f"layer{li}"
-        for bi, blk in enumerate(layer):
-            q = f"{g}.{bi}."
-            resid = "x"
-            if blk.downsample is not None:
-                table.append(_spec(q + "downsample", g, blk.downsample[0], blk.downsample[1], False, "x", "ds"))
-                resid = "ds"
-            if hasattr(blk, "conv3"):
-                table.append(_spec(q + "conv1", g, blk.conv1, blk.bn1, True, "x", "o1"))
-                table.append(_spec(q + "conv2", g, blk.conv2, blk.bn2, True, "o1", "o2"))
-                table.append(_spec(q + "conv3", g, blk.conv3, blk.bn3, True, "o2", "y", resid))
-            else:
-                table.append(_spec(q + "conv1", g, blk.conv1, blk.bn1, True, "x", "o1"))
-                table.append(_spec(q + "conv2", g, blk.conv2, blk.bn2, True, "o1", "y", resid))
-    return table
+    return [sp for li, layer in enumerate(kids[4:8], start=1) for bi, blk in enumerate(layer)
+            for sp in block_table(blk, f"layer{li}", f"layer{li}.{bi}.")]
 
 
 class ResNetEngine:

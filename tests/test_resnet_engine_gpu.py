@@ -192,8 +192,8 @@ def test_load_state_dict_invalidates_the_cache():
     x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(3))
     with torch.no_grad():
         a = m.extract_features(x.cuda())
-        eng = m._trunk_cache.get(m.backbone, x.cuda().device)
-        assert m._trunk_cache.get(m.backbone, x.cuda().device) is eng      # unchanged weights: no repack
+        eng = m.trunk_engine("backbone", x.cuda().device)
+        assert m.trunk_engine("backbone", x.cuda().device) is eng          # unchanged weights: no repack
         m.load_state_dict(sd2)
         b = m.extract_features(x.cuda())
     assert _cos_err(a.cpu(), ovit.sham2_extract_features(sd1, x, "resnet18")) <= 1e-3

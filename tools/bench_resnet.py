@@ -56,7 +56,7 @@ def main():
 
     from hcir.main_backbone import SHAM2
     from hcir.profiling import EventProfiler
-    from hcir.resnet_engine import GROUPS, ResNetEngineCache
+    from hcir.resnet_engine import GROUPS
 
     dev = torch.device("cuda", 0)
     for name in args.models.split(","):
@@ -65,7 +65,7 @@ def main():
         model.hip_trunk = True
         trunk = model.backbone
         trunk16 = copy.deepcopy(trunk).half().to(memory_format=torch.channels_last)
-        eng = model._trunk_caches.setdefault("backbone", ResNetEngineCache()).get(trunk, dev)   # the model's own engine
+        eng = model.trunk_engine("backbone", dev)   # the model's own engine
         for b in (int(v) for v in args.batches.split(",")):
             x = torch.randn(b, 3, 224, 224, device=dev)
             x16 = x.half().contiguous(memory_format=torch.channels_last)
