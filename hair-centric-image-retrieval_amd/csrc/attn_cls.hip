@@ -135,6 +135,7 @@ extern "C" int hcir_attn_cls_fwd_lse(const void* qkv, int64_t b, int32_t t, int3
   HCIR_ENTER();
   if (!qkv || !out || !lse || b <= 0 || t <= 0 || h <= 0) return HCIR_ERR_INVALID;
   if (hd != 64 || t > 256) return HCIR_ERR_UNSUPPORTED;
+  if (b * h > 0x7fffffff) return HCIR_ERR_INVALID;   // as hcir_attn_fwd / hcir_attn_bwd: the grid is cdiv(b * h, 4) as unsigned
   AttnClsArgs a{static_cast<const _Float16*>(qkv), b, t, h, scale};
   hipLaunchKernelGGL(attn_cls_fwd_kernel, dim3((unsigned)hcir_cdiv(b * h, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      a, static_cast<_Float16*>(out), lse);
@@ -147,6 +148,7 @@ extern "C" int hcir_attn_cls_bwd(const void* qkv, const void* out, const void* d
   HCIR_ENTER();
   if (!qkv || !out || !d_out || !lse || !d_qkv || b <= 0 || t <= 0 || h <= 0) return HCIR_ERR_INVALID;
   if (hd != 64 || t > 256) return HCIR_ERR_UNSUPPORTED;
+  if (b * h > 0x7fffffff) return HCIR_ERR_INVALID;   // as hcir_attn_fwd / hcir_attn_bwd: the grid is cdiv(b * h, 4) as unsigned
   AttnClsArgs a{static_cast<const _Float16*>(qkv), b, t, h, scale};
   hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3((unsigned)hcir_cdiv(b * h, 4)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      a, static_cast<const _Float16*>(out), static_cast<const _Float16*>(d_out), lse,

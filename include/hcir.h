@@ -431,7 +431,8 @@ int hcir_attn_bwd(const void* qkv, const void* out, const void* d_out, const flo
 /* The same pair for the CLASS-TOKEN query only (token 0 of every image): the last block of a training pass whose loss
  * reads cls_token = x[:, 0] alone (HP/src/main_backbone.py:625-627).  out / d_out fp16 [B][H*64] (compact), lse fp32
  * [B][H]; d_qkv [B][T][3][H][64] receives dK, dV of every token, dQ of token 0 and ZERO for the other tokens' dQ.
- * hd == 64, T <= 256. */
+ * hd == 64, T <= 256 (else HCIR_ERR_UNSUPPORTED); b * h <= 2^31 - 1 (else HCIR_ERR_INVALID, as hcir_attn_fwd and
+ * hcir_attn_bwd). */
 int hcir_attn_cls_fwd_lse(const void* qkv, int64_t b, int32_t t, int32_t h, int32_t hd, float scale, void* out,
                           float* lse, void* stream);
 int hcir_attn_cls_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, int64_t b, int32_t t,
