@@ -356,6 +356,27 @@ extern "C" int hcir_bn2d_fwd_nhwc_f16(const void* x, int64_t m, int32_t c, const
   return HCIR_OK;
 }
 
+// The forward's first two launches alone: the stem normalises inside its pooling kernel (stem_train.hip).
+extern "C" int hcir_bn2d_stats_nhwc_f16(const void* x, int64_t m, int32_t c, float eps, float momentum,
+                                        float* running_mean, float* running_var, float* save_mean, float* save_rstd,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  Bn2dPlan p;
+  const int st = bn2d_plan(m, c, &p);
+  if (st != HCIR_OK) return st;
+  if (!x || !save_mean || !save_rstd) return HCIR_ERR_INVALID;
+  if (!workspace || workspace_bytes < bn2d_workspace_bytes(p, c)) return HCIR_ERR_WORKSPACE;
+  HCIR_ENTER();
+  hipStream_t hs = (hipStream_t)stream;
+  hipLaunchKernelGGL(bn2d_stats_kernel, dim3((unsigned)(p.chunks * p.slabs)), dim3(BN2D_THREADS), 0, hs,
+                     (const f16x8*)x, m, p.cv, p.wv_log2, p.slabs, p.rows_per_chunk, (f32x2*)workspace);
+  HCIR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn2d_stats_finalize_kernel, dim3((unsigned)(c / 4)), dim3(BN2D_THREADS), 0, hs,
+                     (const f32x2*)workspace, p.chunks, p.rows_per_chunk, m, c, eps, momentum, running_mean,
+                     running_var, save_mean, save_rstd);
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
 extern "C" int hcir_bn2d_bwd_nhwc_f16(const void* dy, const void* x, const void* y_relu, int64_t m, int32_t c,
                                       const float* gamma, const float* save_mean, const float* save_rstd, void* dx,
                                       void* dresid, float* dgamma, float* dbeta, void* workspace,

@@ -140,6 +140,13 @@ SIGNATURES = {
                                        c_sz, c_vp]),
     "hcir_bn2d_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "hcir_bn2d_chunks": (c_i32, [c_i64, c_i32]),
+    "hcir_bn2d_stats_nhwc_f16": (c_int, [c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_stem_conv_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "hcir_stem_bn_relu_pool_f16": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_stem_pool_relu_bwd_f16": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_stem_wgrad_f16": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_stem_wgrad_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "hcir_stem_wgrad_parts": (c_i32, [c_i64, c_i32, c_i32]),
 }
 
 

@@ -23,9 +23,21 @@ With the model's second switch, `hip_train_norm`, on as well, the body's BatchNo
 (train_trunk with fused_norm=True): bn_act_nhwc runs batch statistics, normalisation, the block's residual add and its
 ReLU as one pass over the fp16 NHWC map, forward and backward (hcir_bn2d_fwd_nhwc_f16 / hcir_bn2d_bwd_nhwc_f16,
 csrc/bn2d.hip), and updates the module's running statistics in the kernel.  The stem, the cast to fp16 NHWC and the
-average pool stay torch's on that path as well.
+average pool stay torch's on that path.
 
-Both paths are one walk (walk) over resnet_engine's table of the body - which conv feeds which, where the residual
+With the third switch, `hip_train_stem` (independent of the second), the stem leaves torch as well (train_trunk with
+fused_stem=True): stem_train maps the fp32 NCHW image to the fp16 NHWC [B,Hp,Wp,64] map the walk starts from, with no
+permute or cast in between (csrc/stem_train.hip):
+
+  forward   hcir_stem_conv_f16 (the pre-norm map c, fp16 NHWC), hcir_bn2d_stats_nhwc_f16 (batch statistics; running
+            statistics updated in the kernel), hcir_stem_bn_relu_pool_f16 (normalise + ReLU + max pool in one pass)
+  backward  hcir_stem_pool_relu_bwd_f16 (the gradient at the conv map: torch's first-maximum rule, found on c itself),
+            hcir_bn2d_bwd_nhwc_f16 over it (dc, dgamma, dbeta), hcir_stem_wgrad_f16 (dW, fp32 [64,3,7,7])
+
+The image needs no gradient, and there is no image-gradient kernel: when x.requires_grad, train_trunk keeps the torch
+stem.  The packed stem weight is cached per parameter by _WeightCache's rule (stem_weights).
+
+All paths are one walk (walk) over resnet_engine's table of the body - which conv feeds which, where the residual
 enters, where the ReLU sits are written down there, once - with one of two `norm` callables: torch_norm or bn_act_nhwc.
 """
 from __future__ import annotations
@@ -38,7 +50,7 @@ from torch import nn
 
 from . import ops
 from ._lib import HcirError
-from .resnet_engine import ConvSpec, layer_table, pack_conv_weight
+from .resnet_engine import ConvSpec, layer_table, pack_conv_weight, pack_stem_weight
 
 
 class _WeightCache:
@@ -46,14 +58,16 @@ class _WeightCache:
     the parameter's (_version, data_ptr, device) changes - an optimizer step, load_state_dict, .to() - as VitTrainer
     does for the ViT's operand copies.  A write through `p.data` bumps none of them: call clear() after such an edit."""
 
-    def __init__(self):
+    def __init__(self, pack: Callable = None):
         self._ent = {}    # id(parameter) -> (weak reference, key, w16, wt16); a tensor's == is elementwise, so no
                           # WeakKeyDictionary
+        # what is kept per parameter: a tuple of copies (the stem keeps one, in pack_stem_weight's layout)
+        self._pack = pack or (lambda w: (pack_conv_weight(w), flip_transpose_packed(w)))
 
     def clear(self) -> None:
         self._ent.clear()
 
-    def get(self, w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def get(self, w: torch.Tensor) -> Tuple[torch.Tensor, ...]:
         key = (w._version, w.data_ptr(), str(w.device))
         ent = self._ent.get(id(w))
         if ent is None or ent[0]() is not w or ent[1] != key:
@@ -63,9 +77,9 @@ class _WeightCache:
                 if i in ents and ents[i][0] is ref:
                     del ents[i]
 
-            ent = (weakref.ref(w, drop), key, pack_conv_weight(w), flip_transpose_packed(w))
+            ent = (weakref.ref(w, drop), key, *self._pack(w))
             ents[i] = ent
-        return ent[2], ent[3]
+        return ent[2:]
 
 
 def flip_transpose_packed(w: torch.Tensor) -> torch.Tensor:
@@ -74,6 +88,7 @@ def flip_transpose_packed(w: torch.Tensor) -> torch.Tensor:
 
 
 weights = _WeightCache()
+stem_weights = _WeightCache(lambda w: (pack_stem_weight(w),))
 _identity = {}
 
 
@@ -173,6 +188,46 @@ def bn_act_nhwc(x: torch.Tensor, bn: nn.BatchNorm2d, resid: torch.Tensor = None,
     return y
 
 
+# ------------------------------------- `hip_train_stem`: conv 7x7 + BatchNorm2d + ReLU + MaxPool on HIP (stem_train)
+class _StemTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, bn):
+        x = x.contiguous()
+        (wp,) = stem_weights.get(weight)
+        c = ops.stem_conv(x, wp)
+        # the running statistics are updated by the kernel, in place, outside autograd's view (buffers, no gradient)
+        mean, rstd = ops.bn2d_stats(c, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
+        p = ops.stem_bn_relu_pool(c, gamma, beta, mean, rstd)
+        ctx.save_for_backward(x, c, gamma, beta, mean, rstd)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        x, c, gamma, beta, mean, rstd = ctx.saved_tensors
+        g = ops.stem_pool_relu_bwd(dp.contiguous(), c, gamma, beta, mean, rstd)
+        dc, _, dgamma, dbeta = ops.bn2d_bwd(g, c, None, gamma, mean, rstd)
+        dw = ops.stem_wgrad(x, dc) if ctx.needs_input_grad[1] else None
+        return None, dw, dgamma, dbeta, None
+
+
+def stem_train(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d) -> torch.Tensor:
+    """Differentiable train-mode `maxpool(relu(bn(conv(x))))` of the trunk's stem: x fp32 NCHW [B,3,H,W] -> fp16 NHWC
+    [B,Hp,Wp,64], the walk's input as it is.  Differentiable in conv.weight, bn.weight and bn.bias, NOT in x: there
+    is no image-gradient kernel, and a caller whose image requires a gradient must keep the torch stem (train_trunk
+    does).  Batch statistics; bn.running_mean / running_var are updated with bn.momentum and bn.num_batches_tracked
+    counts the call.  The conv / pool structure is layer_table's to check; a BatchNorm2d the kernels cannot serve
+    raises HcirError, the conditions being bn_act_nhwc's."""
+    if not isinstance(bn, nn.BatchNorm2d) or bn.momentum is None or not bn.affine or not bn.track_running_stats \
+            or not bn.training:
+        raise HcirError("stem_train needs a train-mode BatchNorm2d with affine=True, track_running_stats=True and a "
+                        f"numeric momentum, got {bn!r} (training={getattr(bn, 'training', None)})")
+    if x.requires_grad:
+        raise HcirError("stem_train has no gradient with respect to the image")
+    p = _StemTrain.apply(x, conv.weight, bn.weight, bn.bias, bn)
+    bn.num_batches_tracked.add_(1)
+    return p
+
+
 # ------------------------------------------------------------------------------------ the train-mode walk of the body
 def torch_norm(y: torch.Tensor, bn: nn.BatchNorm2d, resid: torch.Tensor = None, relu: bool = False) -> torch.Tensor:
     """bn_act_nhwc's contract on the module's own torch forward (`hip_train` alone): BatchNorm2d sees the logical
@@ -202,16 +257,22 @@ def walk(table: Sequence[ConvSpec], a: torch.Tensor, conv: Callable = conv_nhwc,
     return live["x"]
 
 
-def train_trunk(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool = False) -> torch.Tensor:
+def train_trunk(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool = False,
+                fused_stem: bool = False) -> torch.Tensor:
     """The differentiable train-mode walk of nn.Sequential(children()[:-1]): x fp32 [B,3,H,W] -> fp32 [B,C].  The stem,
     the one cast to fp16 NHWC and the fp32 average pool are torch's; the body's BatchNorm2d, residual adds and ReLUs
-    are torch's as well (torch_norm) unless `fused_norm` puts them on bn_act_nhwc.  The table is rebuilt, and with it
-    resnet_engine's structure checks (stem, pooling, every body conv has a kernel) are repeated, on every call: an
-    edited trunk raises HcirError whenever the edit was made (host cost: DESIGN.md §3.4)."""
+    are torch's as well (torch_norm) unless `fused_norm` puts them on bn_act_nhwc.  `fused_stem` replaces the torch
+    stem and the cast by stem_train, unless x requires a gradient (there is no image-gradient kernel: the torch stem
+    runs then).  The table is rebuilt, and with it resnet_engine's structure checks (stem, pooling, every body conv
+    has a kernel) are repeated, on every call: an edited trunk raises HcirError whenever the edit was made (host cost:
+    DESIGN.md §3.4)."""
     table = layer_table(trunk)
     kids = list(trunk.children())
-    a = kids[3](kids[2](kids[1](kids[0](x))))
-    a = walk(table, a.permute(0, 2, 3, 1).contiguous().half(), norm=bn_act_nhwc if fused_norm else torch_norm)
+    if fused_stem and not x.requires_grad:
+        a = stem_train(x, kids[0], kids[1])
+    else:
+        a = kids[3](kids[2](kids[1](kids[0](x)))).permute(0, 2, 3, 1).contiguous().half()
+    a = walk(table, a, norm=bn_act_nhwc if fused_norm else torch_norm)
     return kids[8](a.permute(0, 3, 1, 2).float()).flatten(start_dim=1)
 
 

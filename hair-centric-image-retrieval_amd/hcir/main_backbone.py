@@ -174,7 +174,7 @@ class ViTWrapper(nn.Module):
 
 
 class HipTrunkSwitches:
-    """The opt-in HIP paths of a model with ResNet trunks (SHAM2, hcir.backbone.SimCLR): the three switches, the engine
+    """The opt-in HIP paths of a model with ResNet trunks (SHAM2, hcir.backbone.SimCLR): the four switches, the engine
     caches and the one place that decides which path a call takes.  A plain mixin, not a Module: no state_dict key.
 
       hip_trunk        trunks in eval mode, on a HIP device, under no_grad run on hcir.resnet_engine (the HIP convolution
@@ -184,11 +184,18 @@ class HipTrunkSwitches:
       hip_train_norm   on top of hip_train (consulted only where that switch applies): the body's BatchNorm2d layers,
                        residual adds and ReLUs run on the HIP kernels as well (train_trunk with fused_norm=True)
 
+      hip_train_stem   on top of hip_train (consulted only where that switch applies, independent of
+                       hip_train_norm): the stem - conv 7x7, batch-statistics BatchNorm2d, ReLU, max pool - and the
+                       cast to fp16 NHWC run on the HIP kernels, forward and backward (train_trunk with
+                       fused_stem=True -> hcir.conv_train.stem_train).  There is no image-gradient kernel: a call
+                       whose input requires a gradient keeps the torch stem.
+
     Off, or with any condition of hip_trunk_active / hip_train_active unmet, a call keeps the torch path untouched."""
 
     hip_trunk = False
     hip_train = False
     hip_train_norm = False
+    hip_train_stem = False
 
     def trunk_engine(self, which: str, device: torch.device):
         """The ResNetEngine of trunk attribute `which` ("backbone", "backbone_momentum"), from that trunk's own cache."""
@@ -211,7 +218,10 @@ class HipTrunkSwitches:
             f = self.trunk_engine(which, x.device).forward(x)
             return f if head is None else self._project(head, f)
         if walk and hip_train_active(self.hip_train, trunk, x):
-            f = train_trunk(trunk, x, fused_norm=bool(self.hip_train_norm))
+            if self.hip_train_stem:
+                f = train_trunk(trunk, x, fused_norm=bool(self.hip_train_norm), fused_stem=True)
+            else:
+                f = train_trunk(trunk, x, fused_norm=bool(self.hip_train_norm))
             return f if head is None else head(f)
         return None
 

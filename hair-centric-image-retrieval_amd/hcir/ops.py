@@ -377,3 +377,124 @@ def bn2d_bwd(dy: torch.Tensor, x: torch.Tensor, y_relu: Optional[torch.Tensor], 
                                    dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), wsb, _stream(x)),
           "hcir_bn2d_bwd_nhwc_f16")
     return dx, dresid, dgamma, dbeta
+
+
+def bn2d_stats(x: torch.Tensor, eps: float, momentum: float, running_mean: Optional[torch.Tensor] = None,
+               running_var: Optional[torch.Tensor] = None):
+    """The statistics half of bn2d_fwd alone (its kernels, its bits): x fp16 NHWC [B,H,W,C] -> (save_mean, save_rstd)
+    fp32 [C]; running_mean / running_var, where given, are updated in place."""
+    _bn2d_map(x, "x")
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _bn2d_vec(t, name, x)
+    c = x.shape[3]
+    m = x.numel() // c
+    save_mean = torch.empty(c, dtype=torch.float32, device=x.device)
+    save_rstd = torch.empty(c, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    wsb = L.hcir_bn2d_workspace_bytes(m, c)
+    ws = _ws.get(x.device, wsb)
+    check(L.hcir_bn2d_stats_nhwc_f16(x.data_ptr(), m, c, eps, momentum, _ptr(running_mean), _ptr(running_var),
+                                     save_mean.data_ptr(), save_rstd.data_ptr(), ws.data_ptr(), wsb, _stream(x)),
+          "hcir_bn2d_stats_nhwc_f16")
+    return save_mean, save_rstd
+
+
+# ------------------------------------------------------------------ ResNet stem, training (csrc/stem_train.hip)
+def stem_conv_size(n: int) -> int:
+    """Side of the stem's conv map: conv 7 / 2 / pad 3."""
+    return (n - 1) // 2 + 1
+
+
+def _stem_img(img: torch.Tensor, what: str):
+    _dev(img, "img")
+    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 3:
+        raise HcirError(f"{what} expects an fp32 [B,3,H,W] image, got {img.dtype} {tuple(img.shape)}")
+    return img.shape[0], img.shape[2], img.shape[3]
+
+
+def _stem_out(out: Optional[torch.Tensor], shape, dtype, like: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    _dev(out, "out")
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != like.device:
+        raise HcirError(f"`out` must be {dtype} {tuple(shape)} on {like.device}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def _stem_map(c: torch.Tensor, name: str) -> None:
+    _bn2d_map(c, name)
+    if c.shape[3] != 64:
+        raise HcirError(f"`{name}` must be an fp16 NHWC [B,H,W,64] stem map, got {tuple(c.shape)}")
+
+
+def stem_conv(img: torch.Tensor, w_packed: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16(conv7x7/2/pad3(fp16(img), w)) with no epilogue: img fp32 NCHW [B,3,H,W], w_packed from
+    resnet_engine.pack_stem_weight -> the pre-norm map, fp16 NHWC [B,Hc,Wc,64]."""
+    b, h, wd = _stem_img(img, "stem_conv")
+    _dev(w_packed, "w_packed")
+    if w_packed.dtype != torch.float16 or w_packed.numel() != 10 * 2 * 64 * 8:
+        raise HcirError("stem_conv expects the packed fp16 stem weight (pack_stem_weight)")
+    out = _stem_out(out, (b, stem_conv_size(h), stem_conv_size(wd), 64), torch.float16, img)
+    check(_lib.lib().hcir_stem_conv_f16(img.data_ptr(), b, h, wd, w_packed.data_ptr(), out.data_ptr(), _stream(img)),
+          "hcir_stem_conv_f16")
+    return out
+
+
+def stem_bn_relu_pool(c: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, save_mean: torch.Tensor,
+                      save_rstd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """maxpool3x3/2/pad1(relu((c - mean) * rstd * gamma + beta)): c fp16 NHWC [B,Hc,Wc,64] -> fp16 [B,Hp,Wp,64]."""
+    _stem_map(c, "c")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (save_mean, "save_mean"), (save_rstd, "save_rstd")):
+        _bn2d_vec(t, name, c)
+    b, hc, wc, _ = c.shape
+    out = _stem_out(out, (b, (hc - 1) // 2 + 1, (wc - 1) // 2 + 1, 64), torch.float16, c)
+    check(_lib.lib().hcir_stem_bn_relu_pool_f16(c.data_ptr(), b, hc, wc, gamma.data_ptr(), beta.data_ptr(),
+                                                save_mean.data_ptr(), save_rstd.data_ptr(), out.data_ptr(),
+                                                _stream(c)), "hcir_stem_bn_relu_pool_f16")
+    return out
+
+
+def stem_pool_relu_bwd(dp: torch.Tensor, c: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                       save_mean: torch.Tensor, save_rstd: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of stem_bn_relu_pool down to the conv map: dp fp16 [B,Hp,Wp,64], c fp16 [B,Hc,Wc,64] -> the gradient
+    with respect to the normalised map, fp16 like c, every element written."""
+    _stem_map(c, "c")
+    _stem_map(dp, "dp")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (save_mean, "save_mean"), (save_rstd, "save_rstd")):
+        _bn2d_vec(t, name, c)
+    b, hc, wc, _ = c.shape
+    want = (b, (hc - 1) // 2 + 1, (wc - 1) // 2 + 1, 64)
+    if tuple(dp.shape) != want or dp.device != c.device:
+        raise HcirError(f"shape mismatch: c {tuple(c.shape)} pools to {want}, got dp {tuple(dp.shape)}")
+    out = _stem_out(out, tuple(c.shape), torch.float16, c)
+    check(_lib.lib().hcir_stem_pool_relu_bwd_f16(dp.data_ptr(), c.data_ptr(), b, hc, wc, gamma.data_ptr(),
+                                                 beta.data_ptr(), save_mean.data_ptr(), save_rstd.data_ptr(),
+                                                 out.data_ptr(), _stream(c)), "hcir_stem_pool_relu_bwd_f16")
+    return out
+
+
+def stem_wgrad_parts(b: int, h: int, w: int) -> int:
+    """Number of persistent parts hcir_stem_wgrad_f16 runs the shape with; raises for a shape without a kernel."""
+    n = _lib.lib().hcir_stem_wgrad_parts(b, h, w)
+    if n < 0:
+        check(n, "hcir_stem_wgrad_parts")
+    return n
+
+
+def stem_wgrad(img: torch.Tensor, dc: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Weight gradient of stem_conv: img fp32 [B,3,H,W], dc fp16 NHWC [B,Hc,Wc,64] -> fp32 [64,3,7,7] (torch's
+    layout), deterministic."""
+    b, h, wd = _stem_img(img, "stem_wgrad")
+    _stem_map(dc, "dc")
+    want = (b, stem_conv_size(h), stem_conv_size(wd), 64)
+    if tuple(dc.shape) != want or dc.device != img.device:
+        raise HcirError(f"shape mismatch: img {tuple(img.shape)} gives a conv map {want}, got dc {tuple(dc.shape)}")
+    out = _stem_out(out, (64, 3, 7, 7), torch.float32, img)
+    L = _lib.lib()
+    wsb = L.hcir_stem_wgrad_workspace_bytes(b, h, wd)
+    ws = _ws.get(img.device, wsb) if wsb else None
+    check(L.hcir_stem_wgrad_f16(img.data_ptr(), dc.data_ptr(), b, h, wd, out.data_ptr(), _ptr(ws), wsb,
+                                _stream(img)), "hcir_stem_wgrad_f16")
+    return out

@@ -829,6 +829,59 @@ size_t hcir_bn2d_workspace_bytes(int64_t m, int32_t c);
 /* HOST.  Number of row chunks the reductions run the shape with (a test uses it to know which path a case
  * exercised).  Negative: the status the entry points return for the shape. */
 int32_t hcir_bn2d_chunks(int64_t m, int32_t c);
+/* The statistics half of hcir_bn2d_fwd_nhwc_f16 alone - its first two launches, the same kernels, the same bits:
+ * save_mean, save_rstd and the running-statistic update, no elementwise pass.  Same shape rules, statuses and
+ * workspace.  The stem normalises inside its pooling kernel (below). */
+int hcir_bn2d_stats_nhwc_f16(const void* x, int64_t m, int32_t c, float eps, float momentum, float* running_mean,
+                             float* running_var, float* save_mean, float* save_rstd, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * The ResNet stem in training: Conv2d(3, 64, 7, stride 2, pad 3), batch-statistics BatchNorm2d, ReLU and
+ * MaxPool2d(3, stride 2, pad 1), forward and backward (csrc/stem_train.hip; hcir/conv_train.py stem_train, the
+ * model's `hip_train_stem` switch).  Serves the first four torchvision modules of the trunk behind
+ * HP/src/main_backbone.py:576-579 in the step of HP/src/pretrain_engine.py:682-747.
+ *   forward    c = hcir_stem_conv_f16(img);  hcir_bn2d_stats_nhwc_f16(c);  p = hcir_stem_bn_relu_pool_f16(c)
+ *   backward   g = hcir_stem_pool_relu_bwd_f16(dp, c);  dc, dgamma, dbeta = hcir_bn2d_bwd_nhwc_f16(dy = g, x = c,
+ *              y_relu = NULL);  dw = hcir_stem_wgrad_f16(img, dc).  The image needs no gradient: no data gradient.
+ * Sizes as hcir_resnet_stem: Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1.  img fp32 NCHW [B][3][H][W]; the conv-level
+ * maps c, g, dc fp16 NHWC [B][Hc][Wc][64]; the pooled maps p, dp fp16 NHWC [B][Hp][Wp][64].  Statuses are decided
+ * from the shape alone before a pointer is looked at: HCIR_ERR_INVALID for a size below 1, HCIR_ERR_UNSUPPORTED for
+ * H < 7 or W < 7 (Hc < 4 or Wc < 4 where the entry point takes the conv map's size), then HCIR_ERR_INVALID for a NULL
+ * pointer.  No atomics; the caller's stream; no allocation or synchronisation inside; two calls give the same bits.
+ * ------------------------------------------------------------------ */
+
+/* c = fp16(conv7x7/2/pad3(fp16(img), fp16(W))), fp32 accumulation, no epilogue.  w_packed: hcir_resnet_stem's
+ * (hcir.resnet_engine.pack_stem_weight).  Non-overlapping 16 x 16 tiles of conv pixels; 16-byte stores. */
+int hcir_stem_conv_f16(const float* img, int64_t b, int32_t h, int32_t w, const void* w_packed, void* out,
+                       void* stream);
+/* p = fp16(max over the window's positions INSIDE the conv map of relu((c - mean) * (rstd * gamma) + beta)): fp32
+ * arithmetic, one rounding; padding is excluded from the max, not zero (as in hcir_resnet_stem). */
+int hcir_stem_bn_relu_pool_f16(const void* c, int64_t b, int32_t hc, int32_t wc, const float* gamma,
+                               const float* beta, const float* save_mean, const float* save_rstd, void* out,
+                               void* stream);
+/* Backward of the above down to the conv map, the gradient with respect to y = (c - mean) * (rstd * gamma) + beta:
+ *   g[i][j] = fp16(sum over the 1, 2 or 4 windows containing (i, j) of
+ *                  dp[window] * [(i, j) is the window's selected position] * [y(i, j) > 0]),
+ * fp32 sum in a fixed order, every element of g written by a plain store.  The selected position is torch's: the first,
+ * in row-major order of the window, among the positions inside the map at which y is maximal; y is monotone in c per
+ * channel, so it is found on the fp16 values of c (first maximum where rstd * gamma > 0, first minimum where < 0,
+ * first position where == 0). */
+int hcir_stem_pool_relu_bwd_f16(const void* dp, const void* c, int64_t b, int32_t hc, int32_t wc, const float* gamma,
+                                const float* beta, const float* save_mean, const float* save_rstd, void* g,
+                                void* stream);
+/* dw[n][(ch * 7 + ky) * 7 + kx] = sum_{b,i,j} dc[b][i][j][n] * fp16(img[b][ch][2i - 3 + ky][2j - 3 + kx]) (zero
+ * outside the image): dw fp32 [64][3][7][7], torch's layout, overwritten.  hcir_stem_wgrad_parts(b, h, w) persistent
+ * workgroups each add a contiguous run of 16 x 16 conv tiles in registers and write one partial to `workspace`; a second
+ * launch adds the partials in part order.  With one part dw is stored directly and `workspace` may be NULL.
+ * HCIR_ERR_WORKSPACE when `workspace_bytes` is below hcir_stem_wgrad_workspace_bytes(b, h, w). */
+int hcir_stem_wgrad_f16(const float* img, const void* dc, int64_t b, int32_t h, int32_t w, float* dw, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* HOST.  parts * 64 * 147 * 4 bytes; 0 with one part or for a shape without a kernel. */
+size_t hcir_stem_wgrad_workspace_bytes(int64_t b, int32_t h, int32_t w);
+/* HOST.  Number of parts: conv tiles / max(4, ceil(conv tiles / 512)), rounded up.  Negative: the status the weight
+ * gradient returns for the shape. */
+int32_t hcir_stem_wgrad_parts(int64_t b, int32_t h, int32_t w);
 
 #ifdef __cplusplus
 }

@@ -1,20 +1,23 @@
 """ResNet-18 / ResNet-50 trunk TRAINING timings on one GPU: forward + backward of the trunk at 224 x 224 (recorded in
 DESIGN.md §3.4, not gated; bench.py is the contract).
 
-Five paths, same process, same machine, same input; median over --steps iterations after --warmup (HIP events around
+Six paths, same process, same machine, same input; median over --steps iterations after --warmup (HIP events around
 forward + backward of loss = features.sum(); gradients are dropped between iterations, no optimizer):
   torch_fp32                 the torch trunk as SHAMTrainStep runs it today (fp32 NCHW, MIOpen)
   torch_autocast             torch.autocast(fp16), the reference's way (HP/src/pretrain_engine.py:681)
   torch_autocast_chlast      the same on a channels_last trunk and input: the fair vendor yardstick
   hip_train                  the model's `hip_train` switch: hcir.conv_train (body convolutions on the HIP kernels)
   hip_train_norm             `hip_train` and `hip_train_norm`: the body's BatchNorm2d + residual + ReLU on HIP as well
-then ONE more iteration of each of the last two with every libhcir call bracketed by HIP events, which splits its
+  hip_train_stem             all three switches: the stem (conv 7x7, BatchNorm2d, ReLU, max pool) on HIP as well
+then ONE more iteration of each of the last three with every libhcir call bracketed by HIP events, which splits its
 device time into forward convolutions, data gradients by plan (stride 1; 1x1 stride 2; the 3x3 stride 2 that does 4x
 the useful flops - each with its spread-by-2 copy), weight gradients, BatchNorm forward / backward (HIP; the second
-path only) and the rest (torch: stem, casts, pool and, on the first path, BatchNorm, ReLU, adds).  Events, not a
+and third path), stem forward / stem backward (HIP; the third path only) and the rest (torch: casts, pool and, where
+the switches leave them to it, the stem, BatchNorm, ReLU, adds).  Events, not a
 profiler's kernel trace: forward and data gradient run the SAME kernel and only the call site tells them apart.
 One JSON line per (model, batch).  --bn2d-bandwidth adds one line: the BatchNorm2d entry points alone at ResNet-50's
-layer1 shape (M = 256 * 56 * 56, C = 256), in bytes the algorithm must move per second.
+layer1 shape (M = 256 * 56 * 56, C = 256), in bytes the algorithm must move per second.  --stem-bandwidth adds the
+same for the stem entry points at (256, 224, 224).
 
   python tools/bench_resnet_train.py [--model resnet50,resnet18] [--batch 64,256] [--steps 10] [--warmup 3]
 """
@@ -72,6 +75,8 @@ def kernel_shares(model, x):
 
     real_conv, real_wgrad, real_dgrad = ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad
     real_bn_fwd, real_bn_bwd = ops.bn2d_fwd, ops.bn2d_bwd
+    stem_names = ("stem_conv", "bn2d_stats", "stem_bn_relu_pool", "stem_pool_relu_bwd", "stem_wgrad")
+    real_stem = {n: getattr(ops, n) for n in stem_names}
 
     def conv(*a, **k):
         return real_conv(*a, **k) if inside["dgrad"] else bracket("forward", real_conv, *a, **k)
@@ -87,7 +92,19 @@ def kernel_shares(model, x):
     ops.conv2d_f16, conv_train.conv2d_dgrad = conv, dgrad
     ops.conv2d_wgrad = lambda *a, **k: bracket("wgrad", real_wgrad, *a, **k)
     ops.bn2d_fwd = lambda *a, **k: bracket("bn_forward_hip", real_bn_fwd, *a, **k)
-    ops.bn2d_bwd = lambda *a, **k: bracket("bn_backward_hip", real_bn_bwd, *a, **k)
+
+    def bn_bwd(*a, **k):    # the BatchNorm backward that follows the stem's pool backward is the stem's
+        label = "stem_backward_hip" if inside.pop("stem_bwd", False) else "bn_backward_hip"
+        return bracket(label, real_bn_bwd, *a, **k)
+
+    def pool_bwd(*a, **k):
+        inside["stem_bwd"] = True
+        return bracket("stem_backward_hip", real_stem["stem_pool_relu_bwd"], *a, **k)
+
+    ops.bn2d_bwd, ops.stem_pool_relu_bwd = bn_bwd, pool_bwd
+    for n in ("stem_conv", "bn2d_stats", "stem_bn_relu_pool"):
+        setattr(ops, n, lambda *a, _f=real_stem[n], **k: bracket("stem_forward_hip", _f, *a, **k))
+    ops.stem_wgrad = lambda *a, **k: bracket("stem_backward_hip", real_stem["stem_wgrad"], *a, **k)
     try:
         for p in model.backbone.parameters():
             p.grad = None
@@ -99,6 +116,8 @@ def kernel_shares(model, x):
     finally:
         ops.conv2d_f16, ops.conv2d_wgrad, conv_train.conv2d_dgrad = real_conv, real_wgrad, real_dgrad
         ops.bn2d_fwd, ops.bn2d_bwd = real_bn_fwd, real_bn_bwd
+        for n in stem_names:
+            setattr(ops, n, real_stem[n])
     total = t0.elapsed_time(t1)
     by = {}
     for label, e0, e1 in spans:
@@ -127,6 +146,38 @@ def bn2d_bandwidth(dev, warmup, steps, b=256, hw=56, c=256):
                                "counted_bytes": {"fwd": 4 * nbytes, "bwd": 8 * nbytes}}}
 
 
+def stem_bandwidth(dev, warmup, steps, b=256, hw=224):
+    """The stem entry points alone at (b, hw, hw): median ms and the bytes the algorithm must move per second, with
+    N = the fp16 conv-level map and I = the fp32 image: conv I + N; pool N + N / 4; pool backward N / 4 + 2 N; weight
+    gradient I + N (its partials, 37 KB a part, are not counted)."""
+    from hcir import ops
+    from hcir.resnet_engine import pack_stem_weight
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(b, 3, hw, hw, device=dev, generator=g)
+    wp = pack_stem_weight(torch.randn(64, 3, 7, 7, device=dev, generator=g) / 12.0)
+    gamma = torch.rand(64, device=dev, generator=g) + 0.5
+    beta = torch.randn(64, device=dev, generator=g) * 0.2
+    c = ops.stem_conv(x, wp)
+    mean, rstd = ops.bn2d_stats(c, 1e-5, 0.1)
+    p = ops.stem_bn_relu_pool(c, gamma, beta, mean, rstd)
+    dp = torch.randn(p.shape, device=dev, dtype=torch.float16, generator=g)
+    gy = ops.stem_pool_relu_bwd(dp, c, gamma, beta, mean, rstd)
+    n_b, i_b = c.numel() * 2, x.numel() * 4
+    runs = {"conv": (lambda: ops.stem_conv(x, wp, out=c), i_b + n_b),
+            "stats": (lambda: ops.bn2d_stats(c, 1e-5, 0.1), n_b),
+            "bn_relu_pool": (lambda: ops.stem_bn_relu_pool(c, gamma, beta, mean, rstd, out=p), n_b + n_b // 4),
+            "pool_relu_bwd": (lambda: ops.stem_pool_relu_bwd(dp, c, gamma, beta, mean, rstd, out=gy),
+                              n_b // 4 + 2 * n_b),
+            "bn_bwd": (lambda: ops.bn2d_bwd(gy, c, None, gamma, mean, rstd), 5 * n_b),
+            "wgrad": (lambda: ops.stem_wgrad(x, gy), i_b + n_b)}
+    out = {"shape": [b, hw, hw], "wgrad_parts": ops.stem_wgrad_parts(b, hw, hw), "peak_TBps": 6.3}
+    for k, (fn, nbytes) in runs.items():
+        ms = median_ms(fn, warmup, steps)
+        out[k] = {"ms": round(ms, 4), "TBps": round(nbytes / ms / 1e9, 3), "of_peak": round(nbytes / ms / 1e9 / 6.3, 3),
+                  "counted_bytes": nbytes}
+    return {"stem_bandwidth": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="resnet50,resnet18")
@@ -134,6 +185,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bn2d-bandwidth", action="store_true")
+    ap.add_argument("--stem-bandwidth", action="store_true")
     args = ap.parse_args()
 
     from hcir.main_backbone import SHAM2
@@ -169,19 +221,28 @@ def main():
             ms["hip_train_norm"] = median_ms(fwd_bwd(lambda: model.extract_features(x), list(trunk.parameters())),
                                              args.warmup, args.steps)
             shares_norm = kernel_shares(model, x)
-            model.hip_train_norm = False
+            model.hip_train_stem = True
+            ms["hip_train_stem"] = median_ms(fwd_bwd(lambda: model.extract_features(x), list(trunk.parameters())),
+                                             args.warmup, args.steps)
+            shares_stem = kernel_shares(model, x)
+            model.hip_train_norm = model.hip_train_stem = False
             out = {"model": name, "batch": b, "steps": args.steps,
                    "ms": {k: round(v, 3) for k, v in ms.items()},
                    "img_per_s": {k: round(b / v * 1e3, 1) for k, v in ms.items()},
                    "fastest": min(ms, key=ms.get),
                    "hip_train_vs": {k: round(ms["hip_train"] / v, 3) for k, v in ms.items()
-                                    if k not in ("hip_train", "hip_train_norm")},
+                                    if k not in ("hip_train", "hip_train_norm", "hip_train_stem")},
                    "hip_train_norm_vs": {k: round(ms["hip_train_norm"] / v, 3) for k, v in ms.items()
-                                         if k != "hip_train_norm"},
-                   "hip_train_breakdown": shares, "hip_train_norm_breakdown": shares_norm}
+                                         if k not in ("hip_train_norm", "hip_train_stem")},
+                   "hip_train_stem_vs": {k: round(ms["hip_train_stem"] / v, 3) for k, v in ms.items()
+                                         if k != "hip_train_stem"},
+                   "hip_train_breakdown": shares, "hip_train_norm_breakdown": shares_norm,
+                   "hip_train_stem_breakdown": shares_stem}
             print(json.dumps(out), flush=True)
     if args.bn2d_bandwidth:
         print(json.dumps(bn2d_bandwidth(dev, args.warmup, args.steps)), flush=True)
+    if args.stem_bandwidth:
+        print(json.dumps(stem_bandwidth(dev, args.warmup, args.steps)), flush=True)
 
 
 if __name__ == "__main__":

@@ -66,6 +66,9 @@ def main():
     ap.add_argument("--hip-train-norm", action="store_true",
                     help="ResNet models: the body's BatchNorm2d + residual + ReLU on the HIP kernels as well "
                          "(implies --hip-train)")
+    ap.add_argument("--hip-train-stem", action="store_true",
+                    help="ResNet models: the stem (conv 7x7, BatchNorm2d, ReLU, max pool) on the HIP kernels as well "
+                         "(implies --hip-train)")
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
@@ -76,8 +79,9 @@ def main():
                                          num_workers=a.workers, collate_fn=functools.partial(collate_train_views),
                                          pin_memory=False)
     model = SHAM2(a.model).cuda()
-    model.hip_train = a.hip_train or a.hip_train_norm
+    model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
     model.hip_train_norm = a.hip_train_norm
+    model.hip_train_stem = a.hip_train_stem
     opt = torch.optim.Adam(model.parameters(), lr=a.lr)
     step = SHAMTrainStep(model, opt, torch.amp.GradScaler("cuda"), warm_up_epochs=a.warm_up_epochs)
 
