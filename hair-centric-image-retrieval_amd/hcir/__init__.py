@@ -8,6 +8,7 @@ Mirrors the reference's interfaces for the hot path only:
   hcir.neg_sampling   NegSamplerStatic           (HP/src/neg_sampling.py:26-53)
   hcir.hair_encoder   retrieve_similar_images    (src/models/hair_encoder.py:180-198)
   hcir.losses         NTXentLoss                 (lightly; HP/src/pretrain_engine.py:93,725)
+  hcir.optim          get_optimizer, Adam, GradScaler   (HP/utils/utils.py:59-71; HP/src/pretrain_engine.py:745-749)
 Compute goes through hcir.ops -> libhcir.so (HIP, gfx950).  No CPU fallback.
 """
 from ._lib import HcirError, build, lib  # noqa: F401

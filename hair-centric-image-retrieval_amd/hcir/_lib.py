@@ -28,6 +28,7 @@ _lib = None
 
 c_i32, c_i64, c_f32, c_vp, c_sz, c_int = (
     ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int)
+c_f64 = ctypes.c_double
 
 # name -> (restype, argtypes); must list every symbol of include/hcir.h
 SIGNATURES = {
@@ -64,6 +65,11 @@ SIGNATURES = {
     "hcir_patch_mean": (c_int, [c_vp, c_int, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
     "hcir_knn_transform_u8": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "hcir_ema_update": (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_vp]),
+    "hcir_grad_sumsq": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_optim_finalize": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_i32, c_int, c_f64, c_vp, c_vp,
+                                    c_i32, c_f64, c_f64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_adam_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f32, c_f32,
+                               c_f32, c_f32, c_vp]),
     "hcir_positive_masking": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp,
                                       c_vp]),
     "hcir_convert_f32": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp]),

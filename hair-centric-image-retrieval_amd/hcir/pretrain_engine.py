@@ -14,15 +14,21 @@
     F.mse_loss(pos, masked_pos)                                hcir.train_ops        hcir_mse_fwd / _bwd
     total = contrastive + 0.5 triplet + 0.2 mse                (:735-742, ablation switches kept)
     scaler.scale(total).backward(); unscale_; clip_grad_norm_(1.0); scaler.step; scaler.update    (:745-749)
+        with hcir.optim.Adam + hcir.optim.GradScaler           hcir.optim            hcir_grad_sumsq, hcir_optim_finalize,
+                                                                                     hcir_adam_step: no host read
+        with any other optimizer / scaler                      torch                 the five lines as written
 
     positive_transform(pos)  (RandomRotation + GaussianBlur)   hcir.transform        hcir_positive_transform
     projection head in train mode (Linear/BN/ReLU/Linear/BN)   hcir.head_train       hcir_gemm_f16 / _tn, hcir_bn1d_*
 
 The step's DEFAULT path is the reference's default path: `positive_transform` on (ablation "No_pos_transform" turns
 it off, :684-685), hard negatives mined once in the epoch that ends the warm-up with k from the previous epoch's margin
-violations and cached per batch (:633-654), "fixed_hard" and "randomly" as in the reference.  What stays torch: the
-optimizer (torch.optim.Adam from utils.get_optimizer, :108), GradScaler and clip_grad_norm_ — no vendor GEMM is left
-in the step.  The data loader, the epoch bookkeeping, logging and checkpointing of the reference's Trainer are outside
+violations and cached per batch (:633-654), "fixed_hard" and "randomly" as in the reference.  The optimizer tail is
+opt-in: with the optimizer of hcir.optim.get_optimizer (utils.get_optimizer, :108) and an hcir.optim.GradScaler (or no
+scaler) unscale, clip, Adam and the loss-scale update run as three HIP launches with no host read, and the gradient
+buffers keep what backward() left; with a torch.optim optimizer or a torch.amp.GradScaler those lines stay torch's.
+What stays torch either way: the multiply of the loss by the scale and autograd's own bookkeeping — no vendor GEMM is
+left in the step.  The data loader, the epoch bookkeeping, logging and checkpointing of the reference's Trainer are outside
 the hot path.
 """
 from __future__ import annotations
@@ -33,6 +39,8 @@ import torch
 import torch.nn.functional as F
 
 from .losses import NTXentLoss
+from . import optim as hcir_optim
+from ._lib import HcirError
 from .momentum import update_momentum
 from .neg_sampling import NegSamplerRandomly, NegSamplerStatic
 from .train_ops import TripletMarginLoss, mse_loss
@@ -91,6 +99,26 @@ class SHAMTrainStep:
                              f"{self.warm_up_epochs - 1} (epoch + 1 == warm_up_epochs), HP/src/pretrain_engine.py:633-654")
         return x_pos_1[self.negative_batch_idx[batch_id]]                                       # :654,680
 
+    def _check_clip_set(self):
+        """The fused tail clips the optimizer's parameters that have a gradient; the reference clips
+        model.parameters() (:747).  The two sets must be the same one."""
+        in_opt = {id(p): (gi, k) for gi, g in enumerate(self.optimizer.param_groups)
+                  for k, p in enumerate(g["params"]) if p.grad is not None}
+        seen = set()
+        for name, p in self.model.named_parameters():
+            if p.grad is None:
+                continue
+            if id(p) not in in_opt:
+                raise HcirError(f"fused optimizer tail: {name} has a gradient but is not a parameter of the optimizer; "
+                                "clip_grad_norm_(model.parameters()) would include it")
+            seen.add(id(p))
+        for i, (gi, k) in in_opt.items():
+            if i not in seen:
+                p = self.optimizer.param_groups[gi]["params"][k]
+                raise HcirError(f"fused optimizer tail: parameter {k} of optimizer group {gi} (shape "
+                                f"{tuple(p.shape)}) has a gradient but is not in model.parameters(); "
+                                "clip_grad_norm_(model.parameters()) would leave it out")
+
     def __call__(self, batch: Dict[str, torch.Tensor], epoch: int = 0, negative_idx: Optional[torch.Tensor] = None,
                  generator=None, batch_id: int = 0, prev_margin_violations: float = 0.0) -> Dict[str, float]:
         """One optimisation step on {'anchor', 'pos1'} image batches [B,3,224,224] (HIP device): the body of the
@@ -142,7 +170,12 @@ class SHAMTrainStep:
         else:
             total_loss = contrastive_loss + 0.5 * triplet_loss + 0.2 * mse
 
-        if scaler is not None:                                                                  # :745-749
+        fused = isinstance(opt, hcir_optim.Adam) and (scaler is None or isinstance(scaler, hcir_optim.GradScaler))
+        if fused:                       # :745-751 as three launches, no host read; the gradients stay scaled
+            (scaler.scale(total_loss) if scaler is not None else total_loss).backward()
+            self._check_clip_set()
+            opt.step_scaled(scaler, max_norm=1.0)
+        elif scaler is not None:                                                                # :745-749
             scaler.scale(total_loss).backward()
             scaler.unscale_(opt)
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)

@@ -281,6 +281,59 @@ int hcir_knn_transform_u8(const uint8_t* img, int64_t b, int32_t h, int32_t w, i
 int hcir_ema_update(const uint64_t* dst_ptrs, const uint64_t* src_ptrs, const int64_t* counts,
                     int64_t n_chunks, float m, float one_minus_m, void* stream);
 
+/* ------------------------------------------------------------------ *
+ * The optimizer tail of the training step on the device, with no host read:
+ *     scaler.unscale_(opt); clip_grad_norm_(params, max_norm); scaler.step(opt); scaler.update()
+ *                                                              (HP/src/pretrain_engine.py:746-749)
+ * for torch.optim.Adam with coupled L2 weight decay and per-group weight_decay / lr, as built by get_optimizer
+ * (HP/utils/utils.py:59-71, called at HP/src/pretrain_engine.py:108).  Three launches over a chunk table in DEVICE
+ * memory (hcir.optim builds and caches it): chunk c covers counts[c] (1 .. 65 536) consecutive floats of ONE
+ * parameter at p_ptrs[c] / g_ptrs[c] / m_ptrs[c] (exp_avg) / v_ptrs[c] (exp_avg_sq); param_idx[c] is that
+ * parameter's index into steps / step_size / bc2_sqrt and weight_decay[c] its group's weight decay.  16-byte
+ * accesses where a chunk's pointers are 16-byte aligned, 4-byte accesses otherwise.  No atomics; two calls on the
+ * same inputs give the same bits.  fp contraction is off: every product and sum is rounded on its own.
+ * The GRADIENT BUFFERS ARE NEVER WRITTEN: after the step they still hold what backward() left, scaled and unclipped.
+ *
+ * ctl is 4 device floats written by hcir_optim_finalize and read by hcir_adam_step:
+ *     ctl[0] total_norm   ctl[1] c = inv_scale * clip_coef   ctl[2] found_inf (0 / 1)   ctl[3] clip_coef
+ * ------------------------------------------------------------------ */
+
+/* scaler.unscale_ + the norm half of clip_grad_norm_ (:746-747): partial[c] = sum over chunk c of
+ * (g * inv_scale)^2 in fp32, flags[c] = 1 if some g * inv_scale of the chunk is inf or NaN, else 0; plain stores,
+ * one slot per chunk.  inv_scale = float(1 / double(scale[0])) read from DEVICE memory (GradScaler._scale);
+ * scale == NULL means 1. */
+int hcir_grad_sumsq(const uint64_t* g_ptrs, const int64_t* counts, int64_t n_chunks, const float* scale,
+                    float* partial, int32_t* flags, void* stream);
+
+/* One workgroup: sum = partial[0 .. n_chunks) added in fp64 in a fixed order; total_norm = sqrt(sum);
+ * clip_coef = use_clip ? min(1, max_norm / (total_norm + 1e-6)) : 1 (clip_grad_norm_, :747; a NaN stays a NaN);
+ * found_inf = scale != NULL and some flag is set (without a scaler the step is unconditional, as in the reference's
+ * else branch :750-751).  With a scaler, GradScaler.update (:749): on found_inf scale *= backoff_factor and the
+ * tracker is reset; otherwise the tracker is incremented and, when it reaches growth_interval, scale *= growth_factor
+ * (kept if that overflows) and the tracker is reset.  If not found_inf, for each of the n_part participating
+ * parameters i = part_idx[j]: steps[i] += 1, step_size[i] = lr / (1 - beta1^step), bc2_sqrt[i] =
+ * sqrt(1 - beta2^step), both computed in double and rounded to fp32.  Participating parameters [group_end[g-1],
+ * group_end[g]) take group_lr[g]; group_end / group_lr are HOST arrays of n_groups (<= 16) entries, group_end
+ * ascending and ending at n_part.  n_chunks may be 0 (a plain step: no norm, no scaler); partial / flags may then
+ * be NULL.  scale and growth_tracker are both NULL or both set. */
+int hcir_optim_finalize(const float* partial, const int32_t* flags, int64_t n_chunks, float* scale,
+                        int32_t* growth_tracker, float growth_factor, float backoff_factor,
+                        int32_t growth_interval, int use_clip, double max_norm, const int32_t* group_end,
+                        const double* group_lr, int32_t n_groups, double beta1, double beta2,
+                        const int32_t* part_idx, int32_t n_part, float* steps, float* step_size,
+                        float* bc2_sqrt, float* ctl, void* stream);
+
+/* scaler.step(opt) (:748) = torch.optim.Adam.step on the unscaled, clipped gradient.  Per chunk, nothing is written
+ * if ctl[2] (found_inf) is set; otherwise per element, in fp32, each operation rounded on its own:
+ *     g = grad * c + wd * p;   m = m + (g - m) * one_minus_beta1;   v = v * beta2 + one_minus_beta2 * (g * g)
+ *     p = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * p, m and v are written; grad is only read. */
+int hcir_adam_step(const uint64_t* p_ptrs, const uint64_t* g_ptrs, const uint64_t* m_ptrs,
+                   const uint64_t* v_ptrs, const int64_t* counts, const int32_t* param_idx,
+                   const float* weight_decay, int64_t n_chunks, const float* step_size,
+                   const float* bc2_sqrt, const float* ctl, float beta2, float one_minus_beta1,
+                   float one_minus_beta2, float eps, void* stream);
+
 /* PositiveMaskingTransform on the device (HP/utils/transform.py:84-150; the masked positive view of the
  * pretrain step, HP/src/pretrain_engine.py:692-694).  images/out fp32 [B][C][H][W] (may not alias).  A patch
  * (patch x patch, non-overlapping grid) is a "hair" patch when its mean over (C, patch, patch) > threshold;

@@ -69,6 +69,13 @@ def main():
     ap.add_argument("--hip-train-stem", action="store_true",
                     help="ResNet models: the stem (conv 7x7, BatchNorm2d, ReLU, max pool) on the HIP kernels as well "
                          "(implies --hip-train)")
+    ap.add_argument("--fused-optim", action="store_true",
+                    help="the reference's optimizer (get_optimizer: Adam, weight decay on all but biases and norm "
+                         "layers) and loss scaler on the HIP kernels: unscale, clip, step and scale update without a "
+                         "host read (hcir.optim)")
+    ap.add_argument("--weight-decay", type=float, default=1e-4, help="with --fused-optim (reference default)")
+    ap.add_argument("--beta1", type=float, default=0.9, help="with --fused-optim (reference default)")
+    ap.add_argument("--beta2", type=float, default=0.999, help="with --fused-optim (reference default)")
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
@@ -82,8 +89,12 @@ def main():
     model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
     model.hip_train_norm = a.hip_train_norm
     model.hip_train_stem = a.hip_train_stem
-    opt = torch.optim.Adam(model.parameters(), lr=a.lr)
-    step = SHAMTrainStep(model, opt, torch.amp.GradScaler("cuda"), warm_up_epochs=a.warm_up_epochs)
+    if a.fused_optim:
+        from hcir import optim
+        opt, scaler = optim.get_optimizer(model, a.lr, a.weight_decay, a.beta1, a.beta2), optim.GradScaler()
+    else:
+        opt, scaler = torch.optim.Adam(model.parameters(), lr=a.lr), torch.amp.GradScaler("cuda")
+    step = SHAMTrainStep(model, opt, scaler, warm_up_epochs=a.warm_up_epochs)
 
     class Stop(Exception):
         pass
