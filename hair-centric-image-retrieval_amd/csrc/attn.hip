@@ -22,8 +22,6 @@
 
 namespace {
 
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
 struct AttnArgs {
   const _Float16* qkv;  // [B][T][3][H][64]
   _Float16* out;        // [B][NQ][H*64]
@@ -162,10 +160,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
           for (int half = 0; half < 2; ++half) {
             const int key = kb + 8 * half;
             const int col = c0 ^ (((key >> 1) & 1) << 5);
-            const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (fp16x4_t __attribute__((address_space(3)))*)(vsl + key * 128 + col * 2));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vf[s][hdt][4 * half + e] = (_Float16)v4[e];
+            tr_read_half(vf[s][hdt], half, vsl + key * 128 + col * 2);
           }
         }
       }
@@ -360,10 +355,7 @@ __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, i
             for (int half = 0; half < 2; ++half) {
               const int key = kb + 8 * half;
               const int col = c0 ^ (((key >> 1) & 1) << 5);
-              const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                  (fp16x4_t __attribute__((address_space(3)))*)(vsl + key * 128 + col * 2));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) vf[s][hdt][4 * half + e] = (_Float16)v4[e];
+              tr_read_half(vf[s][hdt], half, vsl + key * 128 + col * 2);
             }
           }
         }
@@ -515,10 +507,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_generic_kernel(AttnArgs a) {
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
             const int key = kb + 8 * half;
-            const fp16x4_t v4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (fp16x4_t __attribute__((address_space(3)))*)(vs + key * VPB + c0 * 2));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vf[4 * half + e] = (_Float16)v4[e];
+            tr_read_half(vf, half, vs + key * VPB + c0 * 2);
           }
           oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[hdt], 0, 0, 0);
         }

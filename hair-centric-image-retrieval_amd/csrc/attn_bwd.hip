@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef __fp16 ab_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
 struct AttnBwdArgs {
   const _Float16* qkv;   // [B][T][3][H][64]
   const _Float16* out;   // [B][T][H*64]   forward output O
@@ -188,15 +186,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(AttnBwdArgs a) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           const int row = qb + 8 * half;
-          const ab_fp16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (ab_fp16x4 __attribute__((address_space(3)))*)(dos + img_off_e(row, c0)));
-          const ab_fp16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (ab_fp16x4 __attribute__((address_space(3)))*)(qs + img_off_e(row, c0)));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            dot[4 * half + e] = (_Float16)v1[e];
-            qtf[4 * half + e] = (_Float16)v2[e];
-          }
+          tr_read_half(dot, half, dos + img_off_e(row, c0));
+          tr_read_half(qtf, half, qs + img_off_e(row, c0));
         }
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
@@ -222,10 +213,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_kernel(AttnBwdArgs a) {
         f16x8 ktf;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          const ab_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (ab_fp16x4 __attribute__((address_space(3)))*)(ks + img_off_e(kb + 4 * half, c0)));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ktf[4 * half + e] = (_Float16)v[e];
+          tr_read_half(ktf, half, ks + img_off_e(kb + 4 * half, c0));
         }
         dqa[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ktf, dsb, dqa[dt], 0, 0, 0);
       }
@@ -530,15 +518,8 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
           const int qrow = q0 + 16 * s + 4 * (grp >> 1) + (li >> 2);
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
-            const ab_fp16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (ab_fp16x4 __attribute__((address_space(3)))*)(dos + img2_off_e(qrow + 8 * half, c0)));
-            const ab_fp16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (ab_fp16x4 __attribute__((address_space(3)))*)(qs + img2_off_e(qrow + 8 * half, c0)));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              dotf[s][dt][4 * half + e] = (_Float16)v1[e];
-              qtff[s][dt][4 * half + e] = (_Float16)v2[e];
-            }
+            tr_read_half(dotf[s][dt], half, dos + img2_off_e(qrow + 8 * half, c0));
+            tr_read_half(qtff[s][dt], half, qs + img2_off_e(qrow + 8 * half, c0));
           }
         }
       }
@@ -642,10 +623,7 @@ __global__ __launch_bounds__(64 * kNW2, 1) void attn_bwd2_kernel(AttnBwdArgs a, 
           const int krow = k0 + 16 * s + 4 * (grp >> 1) + (li >> 2);
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
-            const ab_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (ab_fp16x4 __attribute__((address_space(3)))*)(ks + img2_off_e(krow + 8 * half, c0)));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ktf[s][dt][4 * half + e] = (_Float16)v[e];
+            tr_read_half(ktf[s][dt], half, ks + img2_off_e(krow + 8 * half, c0));
           }
         }
       }

@@ -49,6 +49,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// One transposed LDS read (ds_read_b64_tr_b16, EXEC must be full) into half `hf` of an f16x8 MFMA operand: two of them
+// are one operand.  The builtin speaks __fp16, the MFMAs _Float16.
+typedef __fp16 tr_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+__device__ __forceinline__ void tr_read_half(f16x8& f, int hf, const void* lds_ptr) {
+  const tr_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((tr_fp16x4 __attribute__((address_space(3)))*)lds_ptr);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) f[4 * hf + e] = (_Float16)v[e];
+}
+
 // LDS-DMA (global_load_lds_dwordx4: 16 B per lane to wave-uniform base + lane * 16) issued OUTSIDE the compiler's
 // view.  With the builtin, hipcc's waitcnt pass treats every ds_read_b64_tr_b16 (a builtin without a memory operand
 // it could disambiguate) as possibly aliasing the pending transfer and puts `s_waitcnt vmcnt(0)` in front of it: a

@@ -3,6 +3,8 @@
 // plans).  Geometry and split choice: conv_plan.h.  Decisions and measurements: DESIGN.md §3.4.
 #include "common.h"
 #include "conv_plan.h"
+#include "split_sum.h"
+#include "tr_layout.h"
 
 namespace {
 
@@ -10,17 +12,12 @@ namespace {
 // dw[n][r][s][c] = sum_m dy[m][n] * x[pixel(m) + tap(r, s)][c], m = (b, ho, wo) linear, padding taps zero.
 // The contraction index m is the SLOW index of both operands (gemm_tn.hip's situation), so the tiles are staged as
 // they are stored - [64 m][TN n] of dy and [64 m][TC c] of the tap's input pixels, the gather with zeros in the padding
-// being the A fill of conv2d_f16_kernel - and the fragments are read TRANSPOSED with ds_read_b64_tr_b16: lane
-// 16 g + 4 q + p supplies row 8 g + q (+ 4), bytes 8 p .. 8 p + 7 of a 16-column block; two reads are one 16x16x32
-// operand (cdna_hip_programming.md T10).  32-B chunks of a row are XOR-swizzled so that the eight rows a half-wave
-// touches per read ({0..3, 8..11} + 4 hf) fall on the eight 32-B bank groups: with 256-B rows the key is gemm_tn's
-// (row & 3) | ((row >> 3) & 1) << 2; with 128-B rows the row's parity already picks the upper or lower four groups
-// and the key is ((row >> 1) & 1) | ((row >> 3) & 1) << 1.
+// being the A fill of conv2d_f16_kernel - and the fragments are read TRANSPOSED with ds_read_b64_tr_b16, two reads
+// per 16x16x32 operand.  The swizzle of the 256-B and 128-B rows and the lanes' rows: tr_layout.h.
 // Workgroup: 4 waves (2 along n x 2 along c) on a TN x TC tile of ONE tap, TN / TC = 128 where the channel count
 // allows, else 64; fill through registers one step ahead (two LDS buffers, one barrier per step) as in conv.hip.
-// M is split over workgroups; each (tile, split) writes its fp32 partial tile to the workspace and a second kernel adds
-// the splits in split order: no float atomics, two runs are bit-identical (cdna_hip_programming.md Guideline 12).
-typedef __fp16 wg_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+// M is split over workgroups; each (tile, split) writes its fp32 partial tile to the workspace and a second kernel
+// (split_sum.h) adds the splits in split order: no float atomics, two runs are bit-identical.
 
 struct WgradArgs {
   const _Float16* x;
@@ -30,16 +27,6 @@ struct WgradArgs {
   int64_t m, rows_per_split;
   int32_t h, w_px, cin, cout, s, stride, pad, ho, wo, k, tiles_c, taps, tiles;
 };
-
-template <int TW>
-__device__ __forceinline__ int wg_key(int row) {
-  return TW == 128 ? ((row & 3) | (((row >> 3) & 1) << 2)) : (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
-}
-// byte offset of 16-B chunk `ch16` of row `row` in a [64][TW] fp16 tile
-template <int TW>
-__device__ __forceinline__ int wg_off(int row, int ch16) {
-  return row * (TW * 2) + ((((ch16 >> 1) ^ wg_key<TW>(row)) << 5) | ((ch16 & 1) << 4));
-}
 
 template <int TN, int TC>
 __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const WgradArgs a) {
@@ -104,9 +91,9 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const WgradArgs a) {
   };
   auto stash = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < PN; ++i) *(u32x4*)(&Ys[buf][wg_off<TN>(yr + RP_N * i, yc)]) = yreg[i];
+    for (int i = 0; i < PN; ++i) *(u32x4*)(&Ys[buf][tr_fill_off<2 * TN>(yr + RP_N * i, yc)]) = yreg[i];
 #pragma unroll
-    for (int i = 0; i < PC; ++i) *(u32x4*)(&Xs[buf][wg_off<TC>(xr + RP_C * i, xc)]) = xreg[i];
+    for (int i = 0; i < PC; ++i) *(u32x4*)(&Xs[buf][tr_fill_off<2 * TC>(xr + RP_C * i, xc)]) = xreg[i];
   };
 
   f32x4 acc[FN][FC];
@@ -115,7 +102,7 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
     for (int j = 0; j < FC; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int g16 = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
+  const TrLane ln = tr_lane(lane);
   load(0);
   stash(0);
   __syncthreads();
@@ -130,24 +117,16 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const WgradArgs a) {
       f16x8 af[FN], bf[FC];
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
-        const int row = 32 * ks + 8 * g16 + 4 * hf + q4;
+        const int row = tr_lane_row(ln, ks, hf);
 #pragma unroll
         for (int i = 0; i < FN; ++i) {
           const int c32 = wave_n * FN + i;   // 16 columns = 32 B = one chunk
-          const wg_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (wg_fp16x4 __attribute__((address_space(3)))*)(yt + row * (TN * 2) + ((c32 ^ wg_key<TN>(row)) << 5) +
-                                                             8 * p4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) af[i][4 * hf + e] = (_Float16)v[e];
+          tr_read_half(af[i], hf, yt + tr_read_off<2 * TN>(row, c32, ln.p4));
         }
 #pragma unroll
         for (int j = 0; j < FC; ++j) {
           const int c32 = wave_c * FC + j;
-          const wg_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (wg_fp16x4 __attribute__((address_space(3)))*)(xt + row * (TC * 2) + ((c32 ^ wg_key<TC>(row)) << 5) +
-                                                             8 * p4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bf[j][4 * hf + e] = (_Float16)v[e];
+          tr_read_half(bf[j], hf, xt + tr_read_off<2 * TC>(row, c32, ln.p4));
         }
       }
 #pragma unroll
@@ -165,25 +144,11 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const WgradArgs a) {
   for (int i = 0; i < FN; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int n = n0 + wave_n * (TN / 2) + i * 16 + g16 * 4 + e;
+      const int n = n0 + wave_n * (TN / 2) + i * 16 + ln.g16 * 4 + e;
 #pragma unroll
       for (int j = 0; j < FC; ++j)
         out[(int64_t)n * a.k + tap * a.cin + c0 + wave_c * (TC / 2) + j * 16 + (lane & 15)] = acc[i][j][e];
     }
-}
-
-// dw[i] = sum_s part[s][i], s in order; 4 elements per thread (Cout * K is a multiple of 4096)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int splits, int64_t nk,
-                                                           float* __restrict__ dw) {
-  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i >= nk) return;
-  f32x4 s = *reinterpret_cast<const f32x4*>(part + i);
-  for (int sp = 1; sp < splits; ++sp) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(part + (int64_t)sp * nk + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] += v[e];
-  }
-  *reinterpret_cast<f32x4*>(dw + i) = s;
 }
 
 // ------------------------------------------------------------------ hcir_spread2_nhwc_f16
@@ -254,8 +219,7 @@ extern "C" int hcir_conv2d_wgrad_f16(const void* x, const void* dy, int64_t b, i
   else wgrad_launch<64, 64>(a, (unsigned)blocks, hs);
   HCIR_LAUNCH_CHECK();
   if (p.splits > 1) {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)hcir_cdiv(nk, 1024)), dim3(256), 0, hs,
-                       (const float*)workspace, p.splits, nk, dw);
+    split_sum((const float*)workspace, p.splits, nk, dw, hs);   // Cout * K is a multiple of 4096
     HCIR_LAUNCH_CHECK();
   }
   return HCIR_OK;

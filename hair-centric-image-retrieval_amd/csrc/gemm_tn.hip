@@ -7,19 +7,17 @@
 // transposing M x N activations through HBM, the tiles are staged as they are stored ([64 m][256 n|k] fp16, whole
 // 512-B row segments by LDS-DMA) and the fragments are read TRANSPOSED: ds_read_b64_tr_b16 hands lane i of a
 // 16-lane group column i of a 4-row x 16-column block, i.e. 4 consecutive m for one n - two such reads are one
-// 16x16x32 operand (cdna_hip_programming.md T10).  32-B chunks of a row are XOR-swizzled with
-// key(row) = (row & 3) | ((row >> 3) & 1) << 2 so that the eight rows one half-wave touches per read
-// ({0..3, 8..11} + 4 s) land on eight different 32-B bank groups: conflict-free.
+// 16x16x32 operand.  The swizzle of the 512-B rows and the lanes' rows: tr_layout.h.
 //
 // Workgroup: 8 waves (2 along n x 4 along k), tile 256(n) x 256(k), wave tile 128 x 64 = 8 x 4 MFMA tiles (128
 // accumulators), two 64 KB LDS slots.  M is split over workgroups (tiles x splits ~ 2 per CU... one resident per CU);
-// every (tile, split) writes its fp32 partial tile to the workspace and a second kernel adds the splits in order:
-// deterministic, no float atomics (cdna_hip_programming.md Guideline 12).
+// every (tile, split) writes its fp32 partial tile to the workspace and a second kernel (split_sum.h) adds the splits
+// in order: deterministic, no float atomics (cdna_hip_programming.md Guideline 12).
 #include "common.h"
+#include "split_sum.h"
+#include "tr_layout.h"
 
 namespace {
-
-typedef __fp16 tn_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct TnArgs {
   const _Float16* a;  // [M][lda]  (dY: n along the row)
@@ -30,8 +28,6 @@ struct TnArgs {
   int tiles_n, tiles_k, splits;
   int64_t rows_per_split;  // multiple of 64
 };
-
-__device__ __forceinline__ int tn_key(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 
 __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
   constexpr int SLOT = 64 * 512 * 2;  // A tile 32 KB then B tile 32 KB
@@ -47,15 +43,16 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
   const int nsteps = m_end > m_begin ? (int)((m_end - m_begin) / 64) : 0;
 
   // DMA sources: piece P = tid + 512 i, i < 4: operand tile row P >> 5 (64 rows), physical 16-B slot P & 31 holding
-  // logical slot ((c32 ^ key(row)) << 1) | half;  32-bit byte offsets from the step's first row of each operand
+  // the logical chunk at tr_fill_off's in-row byte (the XOR is an involution: tr_layout.h);  32-bit byte offsets from
+  // the step's first row of each operand
   uint32_t aoff[4], boff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int P = tid + 512 * i;
     const int row = P >> 5, pc16 = P & 31;
-    const int lc16 = (((pc16 >> 1) ^ tn_key(row)) << 1) | (pc16 & 1);
-    aoff[i] = (uint32_t)(((int64_t)row * g.lda + n0) * 2 + lc16 * 16);
-    boff[i] = (uint32_t)(((int64_t)row * g.ldb + k0) * 2 + lc16 * 16);
+    const int lbyte = tr_fill_off<512>(row, pc16) - row * 512;
+    aoff[i] = (uint32_t)(((int64_t)row * g.lda + n0) * 2 + lbyte);
+    boff[i] = (uint32_t)(((int64_t)row * g.ldb + k0) * 2 + lbyte);
   }
   const char* abase = reinterpret_cast<const char*>(g.a) + m_begin * g.lda * 2;
   const char* bbase = reinterpret_cast<const char*>(g.b) + m_begin * g.ldb * 2;
@@ -79,9 +76,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
     for (int i = 0; i < 8; ++i) issue(0, i);
   }
 
-  // transposed-read addresses: lane = 16 g + 4 q + p supplies row (8 g + q [+ 4]) of the 32-row substep, byte column
-  // 32 * (16-col block) + 8 p inside the tile row
-  const int g16 = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
+  const TrLane ln = tr_lane(lane);
   for (int step = 0; step < nsteps; ++step) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -95,12 +90,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
       for (int kt = 0; kt < 4; ++kt) {
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-          const int row = 32 * ks + 8 * g16 + 4 * hf + q4;
           const int c32 = wave_k * 4 + kt;  // 16 columns = 32 B = one chunk
-          const tn_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (tn_fp16x4 __attribute__((address_space(3)))*)(bt + row * 512 + ((c32 ^ tn_key(row)) << 5) + 8 * p4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bf[kt][4 * hf + e] = (_Float16)v[e];
+          tr_read_half(bf[kt], hf, bt + tr_read_off<512>(tr_lane_row(ln, ks, hf), c32, ln.p4));
         }
       }
 #pragma unroll
@@ -110,12 +101,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
-            const int row = 32 * ks + 8 * g16 + 4 * hf + q4;
             const int c32 = wave_n * 8 + 4 * half + q;
-            const tn_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                (tn_fp16x4 __attribute__((address_space(3)))*)(at + row * 512 + ((c32 ^ tn_key(row)) << 5) + 8 * p4));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) af[q][4 * hf + e] = (_Float16)v[e];
+            tr_read_half(af[q], hf, at + tr_read_off<512>(tr_lane_row(ln, ks, hf), c32, ln.p4));
           }
         }
         if (more && ks == 0) {  // the eight DMA pieces of the next stage, in the first 32-row substep
@@ -139,31 +126,10 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_tn_kernel(TnArgs g) {
   for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int n = n0 + wave_n * 128 + nt * 16 + g16 * 4 + r;
+      const int n = n0 + wave_n * 128 + nt * 16 + ln.g16 * 4 + r;
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) out[(int64_t)n * g.k + k0 + wave_k * 64 + kt * 16 + (lane & 15)] = acc[nt][kt][r];
     }
-}
-
-// dw[n][k] (+)= sum_s part[s][n][k], s in order; 4 elements per thread
-__global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict__ part, int splits, int64_t nk,
-                                                        int k, float* __restrict__ dw, int64_t lddw,
-                                                        int accumulate) {
-  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i >= nk) return;
-  f32x4 s = *reinterpret_cast<const f32x4*>(part + i);
-  for (int sp = 1; sp < splits; ++sp) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(part + (int64_t)sp * nk + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] += v[e];
-  }
-  float* o = dw + (i / k) * lddw + (i % k);
-  if (accumulate) {
-    const f32x4 old = *reinterpret_cast<const f32x4*>(o);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] += old[e];
-  }
-  *reinterpret_cast<f32x4*>(o) = s;
 }
 
 struct TnPlan {
@@ -212,9 +178,8 @@ int hcir_gemm_f16_tn(const void* a, int64_t lda, const void* b, int64_t ldb, int
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(gemm_f16_tn_kernel, dim3((unsigned)(p.tiles_n * p.tiles_k * p.splits)), dim3(512), 0, st, g);
   HCIR_LAUNCH_CHECK();
-  const int64_t nk = (int64_t)n * k;
-  hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)hcir_cdiv(nk, 1024)), dim3(256), 0, st,
-                     static_cast<const float*>(workspace), p.splits, nk, k, dw, lddw, accumulate);
+  // dw[n][k] (+)= sum_s part[s][n][k], s in order
+  split_sum<true>(static_cast<const float*>(workspace), p.splits, (int64_t)n * k, dw, st, k, lddw, accumulate);
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

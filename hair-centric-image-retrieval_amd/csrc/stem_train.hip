@@ -4,7 +4,9 @@
 // statistics and the BatchNorm backward between them are bn2d.hip's; the image needs no gradient, so there is no data
 // gradient.  Geometry: stem_plan.h.  No atomics, no allocation, no synchronisation; two calls give the same bits.
 #include "common.h"
+#include "split_sum.h"
 #include "stem_plan.h"
+#include "tr_layout.h"
 
 namespace {
 
@@ -262,14 +264,13 @@ __global__ __launch_bounds__(256) void stem_pool_relu_bwd_kernel(
 // ------------------------------------------------------------------ hcir_stem_wgrad_f16
 // dw[n][k] = sum_m dc[m][n] * patch(m)[k]: the contraction index m = (b, i, j) is the slow index of both operands, as
 // in conv_bwd.hip.  Per 16 x 16 tile of conv pixels the dc tile is staged as stored, [256 m][64 n] fp16 (zeros for
-// pixels outside the map), with conv_bwd.hip's swizzle of the 32-B chunks of a 128-B row, and read TRANSPOSED with
+// pixels outside the map), swizzled as tr_layout.h lays out 128-B rows, and read TRANSPOSED with
 // ds_read_b64_tr_b16 (two reads = one 16x16x32 A operand); the B operand is gathered from the fp16 input patch through
 // the forward's tap offsets: lane 16 g + l holds pixels 8 g .. 8 g + 7 of the step's 32 (one tile row: consecutive
 // pixels are 2 halves apart) at tap k = 16 kt + l.  A wave owns three 16-wide k tiles (K = 147 padded to 4 x 48) and
 // all 64 channels: 12 accumulator fragments.  The workgroups are persistent: part p loops over conv tiles
 // [p, p + 1) * tiles_per_part with the accumulators in registers and writes one [64][147] partial, in torch's layout,
-// to the workspace; stem_wgrad_reduce_kernel adds the partials in part order.
-typedef __fp16 st_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+// to the workspace; a second kernel (split_sum.h) adds the partials in part order.
 
 struct StemWgradArgs {
   const float* img;
@@ -279,14 +280,13 @@ struct StemWgradArgs {
   int32_t h, w, hc, wc, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ int st_key(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
-
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) {
   __shared__ __attribute__((aligned(16))) _Float16 patch[STEMT_PATCH + 5];
   __shared__ __attribute__((aligned(16))) char dcs[STEMT_TC * STEMT_TC * 128];
 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int g16 = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3, l16 = lane & 15;
+  const TrLane ln = tr_lane(lane);
+  const int g16 = ln.g16, l16 = lane & 15;
   int toff[3];
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt) toff[kt] = stem_tap_offset(16 * (3 * wv + kt) + l16);
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int row = fr + 32 * i;
-      *(u32x4*)(dcs + row * 128 + ((((fc >> 1) ^ st_key(row)) << 5) | ((fc & 1) << 4))) = dv[i];
+      *(u32x4*)(dcs + tr_fill_off<128>(row, fc)) = dv[i];
     }
     __syncthreads();
 #pragma unroll 2
@@ -328,14 +328,9 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
       f16x8 af[4], bf[3];
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
-        const int row = 32 * ks + 8 * g16 + 4 * hf + q4;
+        const int row = tr_lane_row(ln, ks, hf);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const st_fp16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-              (st_fp16x4 __attribute__((address_space(3)))*)(dcs + row * 128 + ((i ^ st_key(row)) << 5) + 8 * p4));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) af[i][4 * hf + e] = (_Float16)v[e];
-        }
+        for (int i = 0; i < 4; ++i) tr_read_half(af[i], hf, dcs + tr_read_off<128>(row, i, ln.p4));
       }
       const int pix = pbase + 4 * STEMT_TI * ks;   // two tile rows per step
 #pragma unroll
@@ -362,15 +357,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
         for (int e = 0; e < 4; ++e) out[(16 * i + 4 * g16 + e) * STEM_K + k] = acc[i][kt][e];
     }
   }
-}
-
-__global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __restrict__ part, int parts,
-                                                                float* __restrict__ dw) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= STEM_DW) return;
-  float s = part[i];
-  for (int p = 1; p < parts; ++p) s += part[(int64_t)p * STEM_DW + i];
-  dw[i] = s;
 }
 
 }  // namespace
@@ -464,8 +450,7 @@ extern "C" int hcir_stem_wgrad_f16(const float* img, const void* dc, int64_t b, 
   hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)p.parts), dim3(256), 0, hs, a);
   HCIR_LAUNCH_CHECK();
   if (p.parts > 1) {
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((unsigned)hcir_cdiv(STEM_DW, 256)), dim3(256), 0, hs,
-                       (const float*)workspace, p.parts, dw);
+    split_sum((const float*)workspace, p.parts, STEM_DW, dw, hs);   // STEM_DW = 64 * 147 is a multiple of 4
     HCIR_LAUNCH_CHECK();
   }
   return HCIR_OK;
