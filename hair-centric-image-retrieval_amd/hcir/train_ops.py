@@ -1,6 +1,7 @@
 """hcir.train_ops — torch-tensor wrappers over the training half of the C ABI (include/hcir.h, "Training side").
 
-Backward building blocks of the ViT and the two small losses of the HSimCLR step
+The op surface of the ViT's training walk (hcir.vit_train: every launch of its forward and backward is one of these
+functions, so a test can run the walk over stand-ins) and the two small losses of the HSimCLR step
 (HP/src/pretrain_engine.py:681-751).  Every wrapper takes HIP-device tensors and raises otherwise: no CPU path.
 """
 from __future__ import annotations
@@ -11,21 +12,70 @@ import torch
 
 from . import _lib
 from ._lib import HcirError, check
-from .ops import _dev, _stream, _ws
+from .ops import _dev, _ptr, _stream, _ws
 
 _XDT = {torch.float32: _lib.F32, torch.float16: _lib.F16}
+# what a walk over these ops (hcir.vit_train) allocates: where, GEMM-operand dtype, accumulator / gradient dtype
+DEVICE_TYPE, ACT, ACC = "cuda", torch.float16, torch.float32
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+def patch_embed(x: torch.Tensor, ps: int, w16: torch.Tensor, bias, cls, pos, pos_mult: float, tok) -> None:
+    """tok[b][0] = cls + pos_mult pos[0];  tok[b][1 + p] = w16 . patch(b, p) + bias + pos_mult pos[1 + p]."""
+    _dev(x, "x")
+    b, c, hh, ww = x.shape
+    check(_lib.lib().hcir_patch_embed(x.data_ptr(), b, c, hh, ww, ps, w16.data_ptr(), w16.shape[1], bias.data_ptr(),
+                                      cls.data_ptr(), pos.data_ptr(), float(pos_mult), w16.shape[0], tok.data_ptr(),
+                                      _XDT[tok.dtype], _stream(x)), "hcir_patch_embed")
 
 
-def gelu_fwd(u: torch.Tensor) -> torch.Tensor:
+def layernorm(x: torch.Tensor, rows: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, y: torch.Tensor) -> None:
+    """y[:rows] = fp16(LayerNorm(x[:rows])) over contiguous rows of gamma.numel() elements."""
+    _dev(x, "x")
+    d = gamma.numel()
+    check(_lib.lib().hcir_layernorm_f16(x.data_ptr(), _XDT[x.dtype], rows, d, d, gamma.data_ptr(), beta.data_ptr(),
+                                        float(eps), y.data_ptr(), d, _stream(x)), "hcir_layernorm_f16")
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], rows: int, out: torch.Tensor,
+         resid: Optional[torch.Tensor] = None) -> None:
+    """out[:rows] = fp16(a[:rows] @ w^T + bias (+ resid[:rows]));  w fp16 [N, K] as stored, contiguous rows."""
+    _dev(a, "a")
+    n, k = w.shape
+    epi = _lib.EPI_BIAS_F16 if resid is None else _lib.EPI_BIAS_RESID_F16
+    check(_lib.lib().hcir_gemm_f16_resid(a.data_ptr(), k, w.data_ptr(), k, _ptr(bias), None, rows, n, k, epi,
+                                         _ptr(resid), out.data_ptr(), n, _stream(a)), f"hcir_gemm_f16_resid({n}x{k})")
+
+
+def fc1_gelu(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, rows: int, u: torch.Tensor, h: torch.Tensor) -> None:
+    """u = fp16(x @ w^T + bias) (kept for the GELU backward) and h = fp16(gelu(.)): from one pass over the accumulators
+    where the persistent kernel takes the shape, else a GEMM and a GELU pass over u."""
+    n, k = w.shape
+    L = _lib.lib()
+    if L.hcir_gemm_fused_supported(rows, n, k):
+        _dev(x, "x")
+        check(L.hcir_gemm_f16_gelu_dual(x.data_ptr(), k, w.data_ptr(), k, _ptr(bias), rows, n, k, u.data_ptr(),
+                                        h.data_ptr(), n, _stream(x)), "hcir_gemm_f16_gelu_dual")
+    else:
+        gemm(x, w, bias, rows, u)
+        gelu_fwd(u, rows, h)
+
+
+def cls_head(tok: torch.Tensor, b: int, t: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+             out: torch.Tensor) -> None:
+    """out[b] = LayerNorm(tok[b][0]) for tok [b][t][d] (fp32 out)."""
+    _dev(tok, "tok")
+    check(_lib.lib().hcir_cls_head(tok.data_ptr(), _XDT[tok.dtype], b, t, gamma.numel(), gamma.data_ptr(),
+                                   beta.data_ptr(), float(eps), 0, out.data_ptr(), None, _stream(tok)), "hcir_cls_head")
+
+
+def gelu_fwd(u: torch.Tensor, rows: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gelu(u), or of the first `rows` rows of the matrix u, into `out` (allocated when None)."""
     _dev(u, "u")
     if u.dtype != torch.float16 or u.numel() % 8:
         raise HcirError("gelu_fwd expects a contiguous fp16 tensor with numel % 8 == 0")
-    h = torch.empty_like(u)
-    check(_lib.lib().hcir_gelu_fwd_f16(u.data_ptr(), u.numel(), h.data_ptr(), _stream(u)), "hcir_gelu_fwd_f16")
+    h = torch.empty_like(u) if out is None else out
+    n = u.numel() if rows is None else rows * u.shape[1]
+    check(_lib.lib().hcir_gelu_fwd_f16(u.data_ptr(), n, h.data_ptr(), _stream(u)), "hcir_gelu_fwd_f16")
     return h
 
 
@@ -40,13 +90,15 @@ def gelu_bwd(u: torch.Tensor, dh: torch.Tensor, out: Optional[torch.Tensor] = No
     return du
 
 
-def add_to_f16(a: torch.Tensor, b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp16(a + b) of fp32 tensors (b optional)."""
+def add_to_f16(a: torch.Tensor, b: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               rows: Optional[int] = None) -> torch.Tensor:
+    """fp16(a + b) of fp32 tensors (b optional), or of the first `rows` rows of the matrices."""
     _dev(a, "a")
     if a.dtype != torch.float32 or a.numel() % 4:
         raise HcirError("add_to_f16 expects contiguous fp32, numel % 4 == 0")
     y = torch.empty(a.shape, dtype=torch.float16, device=a.device) if out is None else out
-    check(_lib.lib().hcir_add_f32_f16(a.data_ptr(), _p(b), a.numel(), y.data_ptr(), _stream(a)), "hcir_add_f32_f16")
+    n = a.numel() if rows is None else rows * a.shape[1]
+    check(_lib.lib().hcir_add_f32_f16(a.data_ptr(), _ptr(b), n, y.data_ptr(), _stream(a)), "hcir_add_f32_f16")
     return y
 
 
@@ -72,9 +124,9 @@ def layernorm_bwd(x: torch.Tensor, dy16: torch.Tensor, gamma: torch.Tensor, eps:
         if dres16.dtype != torch.float16 or dres16.stride(0) != d:
             raise HcirError("dres16: fp16 [rows, d], contiguous rows")
     check(L.hcir_layernorm_bwd_fused(x.data_ptr(), _XDT[x.dtype], rows, d, ldx, dy16.data_ptr(), d, gamma.data_ptr(),
-                                     float(eps), _p(dres_in), dres_out.data_ptr(), ldr, dgamma.data_ptr(),
-                                     dbeta.data_ptr(), int(accumulate), _p(dres16), d, _p(dres_colsum), ws.data_ptr(),
-                                     ws.numel(), _stream(x)), "hcir_layernorm_bwd_fused")
+                                     float(eps), _ptr(dres_in), dres_out.data_ptr(), ldr, dgamma.data_ptr(),
+                                     dbeta.data_ptr(), int(accumulate), _ptr(dres16), d, _ptr(dres_colsum),
+                                     ws.data_ptr(), ws.numel(), _stream(x)), "hcir_layernorm_bwd_fused")
 
 
 def gelu_bwd_colsum(u: torch.Tensor, dh: torch.Tensor, du: torch.Tensor, colsum_out: torch.Tensor,
@@ -136,6 +188,20 @@ def attn_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, lse: tor
              scale: float, d_qkv: torch.Tensor) -> None:
     check(_lib.lib().hcir_attn_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), b, t, heads, 64,
                                    float(scale), d_qkv.data_ptr(), _stream(qkv)), "hcir_attn_bwd")
+
+
+def attn_cls_fwd_lse(qkv: torch.Tensor, b: int, t: int, heads: int, scale: float, out: torch.Tensor,
+                     lse: torch.Tensor) -> None:
+    """attn_fwd_lse for the class-token query of every image: out [b, heads*64], lse [b, heads]."""
+    check(_lib.lib().hcir_attn_cls_fwd_lse(qkv.data_ptr(), b, t, heads, 64, float(scale), out.data_ptr(),
+                                           lse.data_ptr(), _stream(qkv)), "hcir_attn_cls_fwd_lse")
+
+
+def attn_cls_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, lse: torch.Tensor, b: int, t: int,
+                 heads: int, scale: float, d_qkv: torch.Tensor) -> None:
+    """Its backward: d_qkv gets dK, dV of every token, dQ of token 0 and zero for the other tokens' dQ."""
+    check(_lib.lib().hcir_attn_cls_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), b, t, heads,
+                                       64, float(scale), d_qkv.data_ptr(), _stream(qkv)), "hcir_attn_cls_bwd")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -206,8 +272,8 @@ class _MseFn(torch.autograd.Function):
         dy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
         if dx is None and dy is None:
             return None, None
-        check(_lib.lib().hcir_mse_bwd(x.data_ptr(), y.data_ptr(), x.numel(), g.data_ptr(), _p(dx), _p(dy), _stream(x)),
-              "hcir_mse_bwd")
+        check(_lib.lib().hcir_mse_bwd(x.data_ptr(), y.data_ptr(), x.numel(), g.data_ptr(), _ptr(dx), _ptr(dy),
+                                      _stream(x)), "hcir_mse_bwd")
         return dx, dy
 
 

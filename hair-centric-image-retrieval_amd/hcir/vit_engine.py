@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import HcirError, check
+from .ops import _ptr
 
 
 # Residual-stream storage of engines built without an explicit choice.  fp32 is the conservative
@@ -64,12 +65,17 @@ class VitSpec:
     final_ln_b: Optional[torch.Tensor] = None
 
 
+def _to(t: torch.Tensor, dev, dtype) -> torch.Tensor:
+    """A parameter as the kernels read it: detached, on the device, in the operand dtype, contiguous."""
+    return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+
 def _f32(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return _to(t, dev, torch.float32)
 
 
 def _f16(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.float16).contiguous()
+    return _to(t, dev, torch.float16)
 
 
 class _DevLayer:
@@ -98,10 +104,6 @@ class _DevLayer:
         if bias is not None:
             c2 = c2 + bias.detach().to(device=dev, dtype=torch.float64)
         return wg, c1, c2.to(torch.float32).contiguous()
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class VitEngine:
@@ -211,19 +213,19 @@ class VitEngine:
         nsl = d // 64
         have_stats = False  # `stats` holds (mean, rstd) of the current residual rows
 
-        def resid_gemm(a, k, wt, bias, ls, want_stats, what):
+        def resid_gemm(a, k, wt, bias, ls, rows, pitch, want_stats, what):
+            """tok rows (pitch apart) += ls o (a . wt^T + bias); want_stats (every row only): and their statistics."""
             if want_stats:
-                check(L.hcir_gemm_f16_fused(a.data_ptr(), k, wt.data_ptr(), k, bias.data_ptr(), _p(ls), m, d, k,
+                check(L.hcir_gemm_f16_fused(a.data_ptr(), k, wt.data_ptr(), k, bias.data_ptr(), _ptr(ls), m, d, k,
                                             _lib.EPI_BIAS_RESID_F16, tok.data_ptr(), d, None, None, sp.data_ptr(),
                                             st), what)
                 check(L.hcir_ln_stats_finalize(sp.data_ptr(), nsl, m, d, self.eps, stats.data_ptr(), st),
                       "hcir_ln_stats_finalize")
             else:
-                check(L.hcir_gemm_f16(a.data_ptr(), k, wt.data_ptr(), k, bias.data_ptr(), _p(ls), m, d, k,
-                                      self._resid_epi, tok.data_ptr(), d, st), what)
+                check(L.hcir_gemm_f16(a.data_ptr(), k, wt.data_ptr(), k, bias.data_ptr(), _ptr(ls), rows, d, k,
+                                      self._resid_epi, tok.data_ptr(), pitch, st), what)
 
         for li, l in enumerate(self.layers):
-            cls_only = cls_only_last and li == last
             if fuse and have_stats:
                 check(L.hcir_gemm_f16_fused(tok.data_ptr(), d, l.qkv_wg.data_ptr(), d, l.qkv_c2.data_ptr(), None,
                                             m, 3 * d, d, _lib.EPI_BIAS_F16, qkv.data_ptr(), 3 * d,
@@ -233,55 +235,37 @@ class VitEngine:
                 check(L.hcir_layernorm_f16(tok.data_ptr(), self._rt, m, d, d, l.ln1_w.data_ptr(),
                                            l.ln1_b.data_ptr(), self.eps, ln.data_ptr(), d, st), "hcir_layernorm_f16")
                 self._mark("layernorm")
-                check(L.hcir_gemm_f16(ln.data_ptr(), d, l.qkv_w.data_ptr(), d, _p(l.qkv_b), None, m, 3 * d, d,
+                check(L.hcir_gemm_f16(ln.data_ptr(), d, l.qkv_w.data_ptr(), d, _ptr(l.qkv_b), None, m, 3 * d, d,
                                       _lib.EPI_BIAS_F16, qkv.data_ptr(), 3 * d, st), "hcir_gemm_f16(qkv)")
-            have_stats = False
             self._mark("gemm_qkv")
-            if not cls_only:
-                check(L.hcir_attn_fwd(qkv.data_ptr(), b, t, self.heads, d // self.heads, scale, t,
-                                      att.data_ptr(), st), "hcir_attn_fwd")
-                self._mark("attn")
-                resid_gemm(att, d, l.proj_w, l.proj_b, l.ls1, fuse, "hcir_gemm_f16(proj)")
-                self._mark("gemm_proj")
-                if fuse:
-                    check(L.hcir_gemm_f16_fused(tok.data_ptr(), d, l.fc1_wg.data_ptr(), d, l.fc1_c2.data_ptr(), None,
-                                                m, self.mlp, d, _lib.EPI_BIAS_GELU_F16, hid.data_ptr(), self.mlp,
-                                                stats.data_ptr(), l.fc1_c1.data_ptr(), None, st),
-                          "hcir_gemm_f16_fused(ln2+fc1)")
-                else:
-                    check(L.hcir_layernorm_f16(tok.data_ptr(), self._rt, m, d, d, l.ln2_w.data_ptr(),
-                                               l.ln2_b.data_ptr(), self.eps, ln.data_ptr(), d, st),
-                          "hcir_layernorm_f16")
-                    self._mark("layernorm")
-                    check(L.hcir_gemm_f16(ln.data_ptr(), d, l.fc1_w.data_ptr(), d, l.fc1_b.data_ptr(), None, m,
-                                          self.mlp, d, _lib.EPI_BIAS_GELU_F16, hid.data_ptr(), self.mlp, st),
-                          "hcir_gemm_f16(fc1)")
-                self._mark("gemm_fc1")
-                # the row statistics after fc2 feed the NEXT block's ln_1 (none after the last block)
-                have_stats = fuse and li < last
-                resid_gemm(hid, self.mlp, l.fc2_w, l.fc2_b, l.ls2, have_stats, "hcir_gemm_f16(fc2)")
-                self._mark("gemm_fc2")
+            # behind the qkv GEMM: every row of tok, or - cls_only_last, last block - the class-token rows only: row b
+            # of the compact buffers <-> tok[b][0] (row pitch t*d).  The LayerNorm fold stays off for those
+            if cls_only_last and li == last:
+                rows, pitch, nq, att_r, ln_r, hid_r, fz = b, t * d, 1, w["att_c"], w["ln_c"], w["hid_c"], False
             else:
-                # class-token rows only: row b of the compact buffers <-> tok[b][0] (row stride t*d)
-                att_c, ln_c, hid_c = w["att_c"], w["ln_c"], w["hid_c"]
-                check(L.hcir_attn_fwd(qkv.data_ptr(), b, t, self.heads, d // self.heads, scale, 1,
-                                      att_c.data_ptr(), st), "hcir_attn_fwd(cls)")
-                self._mark("attn")
-                check(L.hcir_gemm_f16(att_c.data_ptr(), d, l.proj_w.data_ptr(), d, l.proj_b.data_ptr(), _p(l.ls1),
-                                      b, d, d, self._resid_epi, tok.data_ptr(), t * d, st), "hcir_gemm_f16(proj,cls)")
-                self._mark("gemm_proj")
-                check(L.hcir_layernorm_f16(tok.data_ptr(), self._rt, b, d, t * d, l.ln2_w.data_ptr(),
-                                           l.ln2_b.data_ptr(), self.eps, ln_c.data_ptr(), d, st),
-                      "hcir_layernorm_f16(cls)")
+                rows, pitch, nq, att_r, ln_r, hid_r, fz = m, d, t, att, ln, hid, fuse
+            check(L.hcir_attn_fwd(qkv.data_ptr(), b, t, self.heads, d // self.heads, scale, nq, att_r.data_ptr(), st),
+                  "hcir_attn_fwd")
+            self._mark("attn")
+            resid_gemm(att_r, d, l.proj_w, l.proj_b, l.ls1, rows, pitch, fz, "hcir_gemm_f16(proj)")
+            self._mark("gemm_proj")
+            if fz:
+                check(L.hcir_gemm_f16_fused(tok.data_ptr(), d, l.fc1_wg.data_ptr(), d, l.fc1_c2.data_ptr(), None,
+                                            m, self.mlp, d, _lib.EPI_BIAS_GELU_F16, hid.data_ptr(), self.mlp,
+                                            stats.data_ptr(), l.fc1_c1.data_ptr(), None, st),
+                      "hcir_gemm_f16_fused(ln2+fc1)")
+            else:
+                check(L.hcir_layernorm_f16(tok.data_ptr(), self._rt, rows, d, pitch, l.ln2_w.data_ptr(),
+                                           l.ln2_b.data_ptr(), self.eps, ln_r.data_ptr(), d, st), "hcir_layernorm_f16")
                 self._mark("layernorm")
-                check(L.hcir_gemm_f16(ln_c.data_ptr(), d, l.fc1_w.data_ptr(), d, l.fc1_b.data_ptr(), None, b,
-                                      self.mlp, d, _lib.EPI_BIAS_GELU_F16, hid_c.data_ptr(), self.mlp, st),
-                      "hcir_gemm_f16(fc1,cls)")
-                self._mark("gemm_fc1")
-                check(L.hcir_gemm_f16(hid_c.data_ptr(), self.mlp, l.fc2_w.data_ptr(), self.mlp, l.fc2_b.data_ptr(),
-                                      _p(l.ls2), b, d, self.mlp, self._resid_epi, tok.data_ptr(), t * d, st),
-                      "hcir_gemm_f16(fc2,cls)")
-                self._mark("gemm_fc2")
+                check(L.hcir_gemm_f16(ln_r.data_ptr(), d, l.fc1_w.data_ptr(), d, l.fc1_b.data_ptr(), None, rows,
+                                      self.mlp, d, _lib.EPI_BIAS_GELU_F16, hid_r.data_ptr(), self.mlp, st),
+                      "hcir_gemm_f16(fc1)")
+            self._mark("gemm_fc1")
+            # the row statistics after fc2 feed the NEXT block's ln_1 (none after the last block)
+            have_stats = fz and li < last
+            resid_gemm(hid_r, self.mlp, l.fc2_w, l.fc2_b, l.ls2, rows, pitch, have_stats, "hcir_gemm_f16(fc2)")
+            self._mark("gemm_fc2")
         return tok
 
     def cls_embedding(self, tok: torch.Tensor, final_norm: bool, l2_normalize: bool,
@@ -296,8 +280,8 @@ class VitEngine:
         bb = self.fln_b if final_norm else None
         if final_norm and g is None:
             raise HcirError("model has no final LayerNorm")
-        check(self.L.hcir_cls_head(tok.data_ptr(), self._rt, b, t, d, _p(g), _p(bb), self.eps, int(l2_normalize),
-                                   e32.data_ptr(), _p(e16), st), "hcir_cls_head")
+        check(self.L.hcir_cls_head(tok.data_ptr(), self._rt, b, t, d, _ptr(g), _ptr(bb), self.eps, int(l2_normalize),
+                                   e32.data_ptr(), _ptr(e16), st), "hcir_cls_head")
         return (e32, e16) if want_f16 else e32
 
     def patch_mean(self, tok: torch.Tensor, final_norm: bool) -> torch.Tensor:
@@ -306,8 +290,8 @@ class VitEngine:
         out = torch.empty((b, d), dtype=torch.float32, device=tok.device)
         g = self.fln_w if final_norm else None
         bb = self.fln_b if final_norm else None
-        check(self.L.hcir_patch_mean(tok.data_ptr(), self._rt, b, t, d, _p(g), _p(bb), self.eps, out.data_ptr(), st),
-              "hcir_patch_mean")
+        check(self.L.hcir_patch_mean(tok.data_ptr(), self._rt, b, t, d, _ptr(g), _ptr(bb), self.eps, out.data_ptr(),
+                                     st), "hcir_patch_mean")
         return out
 
 

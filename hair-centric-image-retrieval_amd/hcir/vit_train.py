@@ -2,68 +2,83 @@
 (the backbone half of `self.model(x)` + `.backward()` in
 HP/src/pretrain_engine.py:682-745).
 
-`VitTrainer.forward(x)` runs
-    patch_embed -> depth x [ LN1 -> qkv GEMM -> attention (+ log-sum-exp) -> proj GEMM + residual ->
-                             LN2 -> fc1 GEMM -> GELU -> fc2 GEMM + residual ] -> final LN of the class token
-keeping, per block, what the backward needs (fp16: block input, qkv, attention output, the residual after the
-attention, the fc1 pre-activation, and — by default, `keep_recomputable=True` — both LayerNorm outputs and the GELU
-output, which are the A operands of the weight-gradient GEMMs; fp32: the attention's row log-sum-exp): 15.4 KB per
-token and block, ~165 GB for config C3's three 1024-image forwards of the 288 GB.  `keep_recomputable=False`
-recomputes the LayerNorm / GELU outputs in the backward instead (three HBM-bound launches per block, 11.8 KB per
-token and block).  `VitTrainer.backward(saved, d_cls)` walks the blocks in reverse:
-    dgrad    dX = dY . W          hcir_gemm_f16 against a transposed fp16 copy of the weight
-    wgrad    dW = dY^T . X        hcir_gemm_f16_tn (operands as stored, transposed LDS reads, split-M, deterministic)
-    bias     db = colsum(dY)      hcir_colsum_f16
-    GELU', LayerNorm', attention' hcir_gelu_bwd_f16, hcir_layernorm_bwd, hcir_attn_bwd
+The network is patch_embed -> depth x block -> final LayerNorm of the class token, and the block is written once in
+each direction (`_block_forward`, `_block_backward`):
+    LN1 -> qkv GEMM                                                         on every token row (K and V need them all)
+    attention (+ log-sum-exp) -> proj GEMM + residual -> LN2 -> fc1 GEMM -> GELU -> fc2 GEMM + residual   on a ROW SET
+A row set (`_RowSet`) is the rows the second line runs on, the attention pair that serves them and the height of their
+buffers: all b*t tokens, or - the last block under `cls_only_last`, whose other rows never reach the loss - the b
+class tokens in compact [pad64(b), .] buffers.  The compact block is the same body between a gather of the class-token
+rows (forward) and a scatter of their residual gradient into the stream (backward).
+The forward keeps, per block (`_Block`), what the backward needs (fp16: block input, qkv, attention output, the
+residual after the attention, the fc1 pre-activation, and - by default, `keep_recomputable=True` - both LayerNorm
+outputs and the GELU output, which are the A operands of the weight-gradient GEMMs; fp32: the attention's row
+log-sum-exp): 15.4 KB per token and block, ~165 GB for config C3's three 1024-image forwards of the 288 GB.
+`keep_recomputable=False` recomputes the LayerNorm / GELU outputs in the backward instead (three HBM-bound launches per
+block, 11.8 KB per token and block).  The backward walks the blocks in reverse:
+    dgrad    dX = dY . W          ops.gemm against a transposed fp16 copy of the weight
+    wgrad    dW = dY^T . X        ops.gemm_tn (operands as stored, transposed LDS reads, split-M, deterministic)
+    bias     db = colsum(dY)      ops.colsum, or the column sums the LayerNorm / GELU backward leaves on its way
+    GELU', LayerNorm', attention' ops.gelu_bwd_colsum, ops.layernorm_bwd, the row set's attention backward
 The residual gradient travels in fp32, GEMM operands in fp16 (a GradScaler's loss scale passes through linearly,
 as under the reference's fp16 autocast).  `vit_cls_with_grad` wraps both in a torch.autograd.Function so that
 SHAM2.forward composes with torch's optimizer, GradScaler and clip_grad_norm_ exactly as in the reference loop.
-There is no CPU path.
+Every launch goes through `ops` (hcir.train_ops: no CPU path); tests/test_vit_walk_host.py runs the same walk over
+float64 stand-ins on the CPU against torch's autograd.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from collections import namedtuple
+from types import SimpleNamespace
+from typing import List
 
 import torch
 
-from . import _lib, train_ops as T
-from ._lib import HcirError, check
-from .vit_engine import VitSpec
+from . import train_ops
+from ._lib import HcirError
+from .vit_engine import VitSpec, _to
 
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+_GRADS = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+# rows behind the qkv GEMM, queries per image (the row pitch of those rows in the stream is nq * d), attention pair
+_RowSet = namedtuple("_RowSet", "rows nq attn_fwd attn_bwd")
 
 
 def _pad64(m: int) -> int:
     return (m + 63) // 64 * 64
 
 
+class _Block:
+    """What one block's forward leaves for its backward; x_mid .. h have the height of the block's row set.  ln1, ln2
+    and h are None where the backward recomputes them."""
+    __slots__ = ("x_in", "ln1", "qkv", "att", "lse", "x_mid", "ln2", "u", "h")
+
+
 class _Saved:
     """Activations of one training forward (device buffers; rows padded to a multiple of 64 with zeros)."""
-    __slots__ = ("b", "t", "m", "x_in", "qkv", "att", "lse", "x_mid", "u", "ln1", "ln2", "h", "x_out", "patches", "last")
+    __slots__ = ("b", "t", "m", "patches", "blocks", "last", "x_out")
 
 
 class VitTrainer:
     """fp16 operand copies of a ViT's weights (as stored and transposed) + the training forward / backward."""
 
     def __init__(self, spec: VitSpec, device: torch.device, keep_recomputable: bool = True,
-                 cls_only_last: bool = True):
+                 cls_only_last: bool = True, ops=train_ops):
         self.keep_recomputable = bool(keep_recomputable)
-        # forward() returns the class token only, so the last block's other rows are dead work (see forward)
+        # forward() returns the class token only, so the last block's other rows are dead work (see _row_set)
         self.cls_only_last = bool(cls_only_last)
-        if device.type != "cuda":
+        if device.type != ops.DEVICE_TYPE:
             raise HcirError(f"VitTrainer needs a HIP device, got {device} (no CPU fallback)")
         if spec.dim % spec.heads or spec.dim // spec.heads != 64:
             raise HcirError("hcir attention kernels support head_dim 64")
         if any(l.ls1 is not None or l.ls2 is not None for l in spec.layers):
             raise NotImplementedError("LayerScale is not on the training path")
-        self.L = _lib.lib()
+        self.ops = ops
         self.device = device
         self.spec = spec
         self.dim, self.heads, self.eps, self.pos_mult = spec.dim, spec.heads, float(spec.eps), float(spec.pos_mult)
         self.patch = int(spec.patch)
         self.mlp = spec.layers[0].fc1_w.shape[0]
+        self.scale = (self.dim // self.heads) ** -0.5
         if self.dim % 256 or self.mlp % 256 or (3 * spec.conv_w.shape[2] * spec.conv_w.shape[3]) % 256:
             raise HcirError("training path needs dim, mlp and C*P*P to be multiples of 256 (hcir_gemm_f16_tn)")
         self._key = None
@@ -86,9 +101,9 @@ class VitTrainer:
         if key == self._key:
             return
         dev, s = self.device, self.spec
-        f16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()
-        f16t = lambda t: t.detach().to(device=dev, dtype=torch.float16).t().contiguous()
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        f16 = lambda t: _to(t, dev, self.ops.ACT)
+        f16t = lambda t: _to(t.t(), dev, self.ops.ACT)
+        f32 = lambda t: _to(t, dev, self.ops.ACC)
         self.conv_w = f16(s.conv_w.reshape(self.dim, -1))
         self.conv_b, self.cls, self.pos = f32(s.conv_b), f32(s.cls.reshape(-1)), f32(s.pos.reshape(-1, self.dim))
         self.lw = []
@@ -104,23 +119,43 @@ class VitTrainer:
         self.fln_w, self.fln_b = f32(s.final_ln_w), f32(s.final_ln_b)
         self._key = key
 
-    # -- small helpers over the C ABI ---------------------------------------------------------------------------
-    def _gemm(self, a, k, w, bias, m, n, epi, out, st, what, resid=None):
-        check(self.L.hcir_gemm_f16_resid(a.data_ptr(), k, w.data_ptr(), k, _p(bias), None, m, n, k, epi, _p(resid),
-                                         out.data_ptr(), n, st), what)
+    # -- buffers: their dtypes and device come from ops.ACT / ops.ACC and self.device alone ------------------------
+    def _act(self, rows: int, cols: int) -> torch.Tensor:
+        """[pad64(rows), cols] GEMM operand whose pad rows are zero: kernels only ever write rows < `rows`, and every
+        one of those is written before it is read (the weight-gradient GEMM contracts over the pad rows as well)."""
+        buf = torch.empty((_pad64(rows), cols), dtype=self.ops.ACT, device=self.device)
+        if buf.shape[0] > rows:
+            buf[rows:].zero_()
+        return buf
 
-    def _ln(self, x, rows, d, ldx, g, b, y, st):
-        check(self.L.hcir_layernorm_f16(x.data_ptr(), _lib.F16, rows, d, ldx, g.data_ptr(), b.data_ptr(), self.eps,
-                                        y.data_ptr(), d, st), "hcir_layernorm_f16")
+    def _acc(self, *shape, zero: bool = False) -> torch.Tensor:
+        return (torch.zeros if zero else torch.empty)(shape, dtype=self.ops.ACC, device=self.device)
+
+    def _row_set(self, b: int, t: int, cls_rows: bool) -> _RowSet:
+        """Only the class token feeds the loss (HP/src/main_backbone.py:625-627): in the LAST block the other queries,
+        and proj / LN2 / MLP of their rows, are dead in the forward and in the backward.  K and V of every token are
+        still needed (LN1 and the qkv GEMM); everything behind runs on the b class-token rows."""
+        ops = self.ops
+        return _RowSet(b, 1, ops.attn_cls_fwd_lse, ops.attn_cls_bwd) if cls_rows else \
+            _RowSet(b * t, t, ops.attn_fwd_lse, ops.attn_bwd)
+
+    @staticmethod
+    def _kept(kept, scratch, recompute, *args):
+        """A tensor the forward kept, or (keep_recomputable=False) recomputed into the backward's scratch buffer."""
+        if kept is not None:
+            return kept
+        recompute(*args, scratch)
+        return scratch
 
     # -- forward ------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
-        if not x.is_cuda:
+        ops = self.ops
+        if x.device.type != ops.DEVICE_TYPE:
             raise HcirError(f"input is on {x.device}; the hcir ViT runs on a HIP device only")
         self.refresh()
-        x = x.float().contiguous()
+        x = x.to(ops.ACC).contiguous()
         b, c, hh, ww = x.shape
-        ps, d, L, dev = self.patch, self.dim, self.L, self.device
+        ps, d = self.patch, self.dim
         if hh % ps or ww % ps:
             raise HcirError("image sides must be multiples of the patch size")
         t = (hh // ps) * (ww // ps) + 1
@@ -128,256 +163,146 @@ class VitTrainer:
             raise HcirError("hcir_attn_bwd supports up to 256 tokens")
         if t != self.pos.shape[0]:
             raise HcirError(f"image gives {t} tokens but pos_embedding has {self.pos.shape[0]}")
-        m, mp = b * t, _pad64(b * t)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        def z16(cols):
-            """[mp, cols] fp16 whose pad rows (>= m) are zero: kernels only ever write rows < m."""
-            buf = torch.empty((mp, cols), dtype=torch.float16, device=dev)
-            if mp > m:
-                buf[m:].zero_()
-            return buf
-
+        if self.conv_w.shape[1] % 64:
+            raise HcirError("C*P*P must be a multiple of 64")
+        m = b * t
         sv = _Saved()
-        sv.b, sv.t, sv.m = b, t, m
-        sv.x_in, sv.qkv, sv.att, sv.lse, sv.x_mid, sv.u, sv.ln1, sv.ln2, sv.h = ([] for _ in range(9))
+        sv.b, sv.t, sv.m, sv.blocks = b, t, m, []
         # im2col of the patches in (c, ky, kx) order: the weight gradient of conv_proj needs it (data movement only)
         gh, gw = hh // ps, ww // ps
-        pm = _pad64(b * gh * gw)
-        sv.patches = torch.zeros((pm, c * ps * ps), dtype=torch.float16, device=dev)
+        sv.patches = self._act(b * gh * gw, c * ps * ps)
         sv.patches[: b * gh * gw] = x.reshape(b, c, gh, ps, gw, ps).permute(0, 2, 4, 1, 3, 5).reshape(b * gh * gw, -1)
-        tok = z16(d)
-        kpad = self.conv_w.shape[1]
-        if kpad % 64:
-            raise HcirError("C*P*P must be a multiple of 64")
-        check(L.hcir_patch_embed(x.data_ptr(), b, c, hh, ww, ps, self.conv_w.data_ptr(), kpad, self.conv_b.data_ptr(),
-                                 self.cls.data_ptr(), self.pos.data_ptr(), self.pos_mult, d, tok.data_ptr(), _lib.F16,
-                                 st), "hcir_patch_embed")
-        scale = (d // self.heads) ** -0.5
-        cur = tok
+        cur = self._act(m, d)
+        ops.patch_embed(x, ps, self.conv_w, self.conv_b, self.cls, self.pos, self.pos_mult, cur)
         # The LayerNorm outputs and gelu(u) are KEPT as well (they are the A operands of the weight-gradient GEMMs):
         # 3.6 KB more per token and layer - 65 GB for config C3's three 1024-image forwards, of 288 - instead of two
-        # LayerNorm and one GELU launch per layer in the backward (keep_recomputable=False restores the recompute).
-        keep = self.keep_recomputable
-        ln, h = (None, None) if keep else (z16(d), z16(self.mlp))
-        sv.last = None
+        # LayerNorm and one GELU launch per layer in the backward (keep_recomputable=False restores the recompute:
+        # the forward then writes them to two scratch buffers that every full-height block shares).
+        scratch = None if self.keep_recomputable else (self._act(m, d), self._act(m, self.mlp))
+        full, sv.last = self._row_set(b, t, False), self._row_set(b, t, self.cls_only_last)
         for li, w in enumerate(self.lw):
-            qkv = z16(3 * d)
-            if keep:
-                ln = z16(d)
-            self._ln(cur, m, d, d, w["ln1_w"], w["ln1_b"], ln, st)
-            if keep:
-                sv.ln1.append(ln)
-            self._gemm(ln, d, w["qkv_w"], w["qkv_b"], m, 3 * d, _lib.EPI_BIAS_F16, qkv, st, "hcir_gemm_f16(qkv)")
-            if self.cls_only_last and li == len(self.lw) - 1:
-                # Only the class token feeds the loss (HP/src/main_backbone.py:625-627): in the LAST block the other
-                # queries, and proj / LN2 / MLP of their rows, are dead in the forward and in the backward.  K and V
-                # of every token are still needed (the qkv GEMM above); everything behind runs on the b class-token
-                # rows, compact buffers [pad64(b), .] (as the inference engine has done since round 1).
-                bp = _pad64(b)
-
-                def c16(cols):
-                    buf = torch.empty((bp, cols), dtype=torch.float16, device=dev)
-                    if bp > b:
-                        buf[b:].zero_()
-                    return buf
-                att_c, xin_c, x_mid_c, ln2_c, u_c, h_c, x_out_c = (c16(d), c16(d), c16(d), c16(d), c16(self.mlp),
-                                                                   c16(self.mlp), c16(d))
-                lse_c = torch.empty((b, self.heads), dtype=torch.float32, device=dev)
-                check(L.hcir_attn_cls_fwd_lse(qkv.data_ptr(), b, t, self.heads, d // self.heads, scale, att_c.data_ptr(),
-                                              lse_c.data_ptr(), st), "hcir_attn_cls_fwd_lse")
-                xin_c[:b] = cur[:m].view(b, t, d)[:, 0]
-                self._gemm(att_c, d, w["proj_w"], w["proj_b"], b, d, _lib.EPI_BIAS_RESID_F16, x_mid_c, st,
-                           "hcir_gemm_f16(proj, cls rows)", resid=xin_c)
-                self._ln(x_mid_c, b, d, d, w["ln2_w"], w["ln2_b"], ln2_c, st)
-                if L.hcir_gemm_fused_supported(b, self.mlp, d):
-                    check(L.hcir_gemm_f16_gelu_dual(ln2_c.data_ptr(), d, w["fc1_w"].data_ptr(), d, _p(w["fc1_b"]), b,
-                                                    self.mlp, d, u_c.data_ptr(), h_c.data_ptr(), self.mlp, st),
-                          "hcir_gemm_f16_gelu_dual(cls rows)")
-                else:
-                    self._gemm(ln2_c, d, w["fc1_w"], w["fc1_b"], b, self.mlp, _lib.EPI_BIAS_F16, u_c, st,
-                               "hcir_gemm_f16(fc1, cls rows)")
-                    check(L.hcir_gelu_fwd_f16(u_c.data_ptr(), b * self.mlp, h_c.data_ptr(), st), "hcir_gelu_fwd_f16")
-                self._gemm(h_c, self.mlp, w["fc2_w"], w["fc2_b"], b, d, _lib.EPI_BIAS_RESID_F16, x_out_c, st,
-                           "hcir_gemm_f16(fc2, cls rows)", resid=x_mid_c)
-                sv.last = dict(att=att_c, lse=lse_c, x_mid=x_mid_c, ln2=ln2_c, u=u_c, h=h_c, x_out=x_out_c)
-                sv.x_in.append(cur)
-                sv.qkv.append(qkv)
-                sv.x_out = None
-                cls = torch.empty((b, d), dtype=torch.float32, device=dev)
-                check(L.hcir_cls_head(x_out_c.data_ptr(), _lib.F16, b, 1, d, self.fln_w.data_ptr(), self.fln_b.data_ptr(),
-                                      self.eps, 0, cls.data_ptr(), None, st), "hcir_cls_head")
-                return cls, sv
-            att = z16(d)
-            lse = torch.empty((b, self.heads, t), dtype=torch.float32, device=dev)
-            T.attn_fwd_lse(qkv, b, t, self.heads, scale, att, lse)
-            x_mid = z16(d)       # out of place: `cur` is this block's saved input
-            self._gemm(att, d, w["proj_w"], w["proj_b"], m, d, _lib.EPI_BIAS_RESID_F16, x_mid, st, "hcir_gemm_f16(proj)",
-                       resid=cur)
-            u = z16(self.mlp)
-            if keep:
-                ln, h = z16(d), z16(self.mlp)
-                sv.ln2.append(ln)
-                sv.h.append(h)
-            self._ln(x_mid, m, d, d, w["ln2_w"], w["ln2_b"], ln, st)
-            if L.hcir_gemm_fused_supported(m, self.mlp, d):
-                # pre-activation (kept for the GELU backward) and activation from one pass over the accumulators
-                check(L.hcir_gemm_f16_gelu_dual(ln.data_ptr(), d, w["fc1_w"].data_ptr(), d, _p(w["fc1_b"]), m, self.mlp,
-                                                d, u.data_ptr(), h.data_ptr(), self.mlp, st), "hcir_gemm_f16_gelu_dual")
-            else:
-                self._gemm(ln, d, w["fc1_w"], w["fc1_b"], m, self.mlp, _lib.EPI_BIAS_F16, u, st, "hcir_gemm_f16(fc1)")
-                check(L.hcir_gelu_fwd_f16(u.data_ptr(), m * self.mlp, h.data_ptr(), st), "hcir_gelu_fwd_f16")
-            x_out = z16(d)
-            self._gemm(h, self.mlp, w["fc2_w"], w["fc2_b"], m, d, _lib.EPI_BIAS_RESID_F16, x_out, st,
-                       "hcir_gemm_f16(fc2)", resid=x_mid)
-            for lst, v in ((sv.x_in, cur), (sv.qkv, qkv), (sv.att, att), (sv.lse, lse), (sv.x_mid, x_mid), (sv.u, u)):
-                lst.append(v)
-            cur = x_out
-        sv.x_out = cur
-        cls = torch.empty((b, d), dtype=torch.float32, device=dev)
-        check(L.hcir_cls_head(cur.data_ptr(), _lib.F16, b, t, d, self.fln_w.data_ptr(), self.fln_b.data_ptr(), self.eps,
-                              0, cls.data_ptr(), None, st), "hcir_cls_head")
+            rs = sv.last if li == len(self.lw) - 1 else full
+            x_res = cur                                   # the row set's residual input
+            if rs.rows != m:                              # the gather: row i of the compact buffers <-> token (i, 0)
+                x_res = self._act(b, d)
+                x_res[:b] = cur[:m].view(b, t, d)[:, 0]
+            blk, cur = self._block_forward(w, cur, x_res, b, t, rs, scratch)
+            sv.blocks.append(blk)
+        sv.x_out = cur                                    # [b][rs.nq][d]: the class token is row 0 of each image
+        cls = self._acc(b, d)
+        ops.cls_head(cur, b, sv.last.nq, self.fln_w, self.fln_b, self.eps, cls)
         return cls, sv
 
+    def _block_forward(self, w, x, x_res, b, t, rs, scratch):
+        """One block from the stream `x` (all b*t rows) to its output on the rows of `rs`, whose residual input is
+        `x_res`.  `scratch` (ln, h): shared [pad64(b*t), .] buffers for what the backward recomputes; None: all kept."""
+        ops, d, m, rows = self.ops, self.dim, b * t, rs.rows
+        blk = _Block()
+        blk.x_in, blk.qkv = x, self._act(m, 3 * d)
+        ln1 = scratch[0] if scratch else self._act(m, d)
+        blk.ln1 = None if scratch else ln1
+        ops.layernorm(x, m, w["ln1_w"], w["ln1_b"], self.eps, ln1)
+        ops.gemm(ln1, w["qkv_w"], w["qkv_b"], m, blk.qkv)
+        blk.att, blk.lse = self._act(rows, d), self._acc(b, self.heads, rs.nq)
+        rs.attn_fwd(blk.qkv, b, t, self.heads, self.scale, blk.att, blk.lse)
+        blk.x_mid = self._act(rows, d)                    # out of place: `x_res` is (part of) this block's saved input
+        ops.gemm(blk.att, w["proj_w"], w["proj_b"], rows, blk.x_mid, resid=x_res)
+        blk.u = self._act(rows, self.mlp)
+        own = scratch is None or rows != m                # compact buffers are always the block's own
+        ln2, h = (self._act(rows, d), self._act(rows, self.mlp)) if own else scratch
+        blk.ln2, blk.h = (ln2, h) if own else (None, None)
+        ops.layernorm(blk.x_mid, rows, w["ln2_w"], w["ln2_b"], self.eps, ln2)
+        # pre-activation (kept for the GELU backward) and activation
+        ops.fc1_gelu(ln2, w["fc1_w"], w["fc1_b"], rows, blk.u, h)
+        x_out = self._act(rows, d)
+        ops.gemm(h, w["fc2_w"], w["fc2_b"], rows, x_out, resid=blk.x_mid)
+        return blk, x_out
+
     # -- backward -----------------------------------------------------------------------------------------------
+    def _work(self, rows: int) -> SimpleNamespace:
+        """Work buffers of the backward over one row set: the fp32 residual gradient and the fp16 GEMM operands."""
+        d = self.dim
+        return SimpleNamespace(dres=self._acc(_pad64(rows), d, zero=True), dy16=self._act(rows, d),
+                               big16=self._act(rows, self.mlp), dln=self._act(rows, d), datt=self._act(rows, d))
+
     def backward(self, sv: _Saved, d_cls: torch.Tensor) -> List[torch.Tensor]:
         """Gradients (fp32, shapes of `params()`) of sum(cls * d_cls)."""
-        b, t, m, d, dev, L = sv.b, sv.t, sv.m, self.dim, self.device, self.L
-        mp = _pad64(m)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        f32z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        ops, b, t, m, d = self.ops, sv.b, sv.t, sv.m, self.dim
         # every gradient buffer is WRITTEN (accumulate=False) by the kernel that produces it: no zero fill (12 fills
-        # per block); the [mp, *] fp16 work buffers only need their pad rows m.. zero (operands of the TN GEMM)
-        f32e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-
-        def pad16(cols):
-            buf = torch.empty((mp, cols), dtype=torch.float16, device=dev)
-            buf[m:].zero_()
-            return buf
-        grads = {}
-        dres = f32z(mp, d)                                    # dL / d(residual stream), fp32
-        dy16 = pad16(d)
-        g_flw, g_flb = f32e(d), f32e(d)
-        dcls16 = d_cls.detach().to(device=dev, dtype=torch.float16).contiguous()
-        lastc = sv.last          # class-token-only last block: its residual gradient lives in a compact [pad64(b), d] buffer
-        if lastc is None:
-            T.layernorm_bwd(sv.x_out, dcls16, self.fln_w, self.eps, None, dres, g_flw, g_flb, accumulate=False, rows=b,
-                            ldx=t * d, ldr=t * d)
-        else:
-            bp = _pad64(b)
-            dres_c = f32z(bp, d)
-            T.layernorm_bwd(lastc["x_out"], dcls16, self.fln_w, self.eps, None, dres_c, g_flw, g_flb, accumulate=False,
-                            rows=b, ldx=d, ldr=d)
-        big16 = pad16(self.mlp)                                                   # d_h / d_u
+        # per block); the fp16 work buffers only need their pad rows zero (operands of the TN GEMM)
+        fw = self._work(m)                                # the stream: dres is dL / d(residual stream)
+        fw.dqkv = self._act(m, 3 * d)
         # gelu(u) / LayerNorm output: recomputed per block only when the forward did not keep them
-        hbuf = None if sv.h else pad16(self.mlp)
-        lnbuf = None if sv.ln1 else pad16(d)
-        dqkv = pad16(3 * d)
-        datt = pad16(d)
-        dln = pad16(d)
-        layer_grads = []
-        scale = (d // self.heads) ** -0.5
-        nelem = m * d
+        fw.hbuf, fw.lnbuf = (None, None) if self.keep_recomputable else (self._act(m, self.mlp), self._act(m, d))
+        full, last = self._row_set(b, t, False), sv.last
+        lw = fw if last.rows == m else self._work(b)      # the last block's row set has its own residual gradient
+        g_flw, g_flb = self._acc(d), self._acc(d)
+        dcls16 = _to(d_cls, self.device, ops.ACT)
+        ops.layernorm_bwd(sv.x_out, dcls16, self.fln_w, self.eps, None, lw.dres, g_flw, g_flb, accumulate=False, rows=b,
+                          ldx=last.nq * d, ldr=last.nq * d)
         # dy16 = fp16(dres) and its column sums (the bias gradient of the Linear in front) come out of the LayerNorm
-        # backward that produced dres (hcir_layernorm_bwd_fused) - except for the last block, whose dres is the
-        # gradient of the final LayerNorm (class-token rows only)
-        fc2_b_next = None
+        # backward that produced dres - except for the last block, whose dres is the gradient of the final LayerNorm
+        # (class-token rows only)
+        layer_grads, fc2_b = [], None
         for li in range(len(self.lw) - 1, -1, -1):
-            w = self.lw[li]
-            g = {k: f32e(*shape) for k, shape in (
-                ("ln1_w", (d,)), ("ln1_b", (d,)), ("qkv_w", (3 * d, d)), ("qkv_b", (3 * d,)), ("proj_w", (d, d)),
-                ("proj_b", (d,)), ("ln2_w", (d,)), ("ln2_b", (d,)), ("fc1_w", (self.mlp, d)), ("fc1_b", (self.mlp,)),
-                ("fc2_w", (d, self.mlp)), ("fc2_b", (d,)))}
-            if lastc is not None and li == len(self.lw) - 1:
-                # ---- last block on the b class-token rows (compact buffers); K / V gradients for every token
-                z16c = lambda cols: torch.zeros((bp, cols), dtype=torch.float16, device=dev)
-                dy16_c, big16_c, dln_c, datt_c = z16c(d), z16c(self.mlp), z16c(d), z16c(d)
-                check(L.hcir_add_f32_f16(dres_c.data_ptr(), None, b * d, dy16_c.data_ptr(), st), "hcir_add_f32_f16")
-                T.colsum(dy16_c, g["fc2_b"], accumulate=False, rows=b)
-                self._gemm(dy16_c, d, w["fc2_wt"], None, b, self.mlp, _lib.EPI_BIAS_F16, big16_c, st, "dgrad(fc2, cls)")
-                T.gemm_tn(dy16_c, lastc["h"], g["fc2_w"], accumulate=False)
-                T.gelu_bwd_colsum(lastc["u"], big16_c, big16_c, g["fc1_b"], rows=b)
-                self._gemm(big16_c, self.mlp, w["fc1_wt"], None, b, d, _lib.EPI_BIAS_F16, dln_c, st, "dgrad(fc1, cls)")
-                T.gemm_tn(big16_c, lastc["ln2"], g["fc1_w"], accumulate=False)
-                T.layernorm_bwd(lastc["x_mid"], dln_c, w["ln2_w"], self.eps, dres_c, dres_c, g["ln2_w"], g["ln2_b"],
-                                accumulate=False, rows=b, dres16=dy16_c, dres_colsum=g["proj_b"])
-                self._gemm(dy16_c, d, w["proj_wt"], None, b, d, _lib.EPI_BIAS_F16, datt_c, st, "dgrad(proj, cls)")
-                T.gemm_tn(dy16_c, lastc["att"], g["proj_w"], accumulate=False)
-                check(L.hcir_attn_cls_bwd(sv.qkv[li].data_ptr(), lastc["att"].data_ptr(), datt_c.data_ptr(),
-                                          lastc["lse"].data_ptr(), b, t, self.heads, d // self.heads, scale,
-                                          dqkv.data_ptr(), st), "hcir_attn_cls_bwd")
-                # the block's residual gradient: the class-token rows carry dres_c, every other row nothing (yet)
-                dres[:m].view(b, t, d)[:, 0] = dres_c[:b]
-                self._gemm(dqkv, 3 * d, w["qkv_wt"], None, m, d, _lib.EPI_BIAS_F16, dln, st, "dgrad(qkv)")
-                if sv.ln1:
-                    lncur = sv.ln1[li]
-                else:
-                    lncur = lnbuf
-                    self._ln(sv.x_in[li], m, d, d, w["ln1_w"], w["ln1_b"], lnbuf, st)
-                T.gemm_tn(dqkv, lncur, g["qkv_w"], accumulate=False)
-                T.colsum(dqkv, g["qkv_b"], accumulate=False, rows=m)
-                fc2_b_next = f32e(d) if li > 0 else None
-                T.layernorm_bwd(sv.x_in[li], dln, w["ln1_w"], self.eps, dres, dres, g["ln1_w"], g["ln1_b"],
-                                accumulate=False, rows=m, dres16=dy16 if li > 0 else None, dres_colsum=fc2_b_next)
-                layer_grads.append(g)
-                continue
-            # ---- MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
-            if fc2_b_next is None:
-                check(L.hcir_add_f32_f16(dres.data_ptr(), None, nelem, dy16.data_ptr(), st), "hcir_add_f32_f16")
-                T.colsum(dy16, g["fc2_b"], accumulate=False, rows=m)
-            else:
-                g["fc2_b"] = fc2_b_next
-            self._gemm(dy16, d, w["fc2_wt"], None, m, self.mlp, _lib.EPI_BIAS_F16, big16, st, "dgrad(fc2)")
-            if sv.h:
-                hcur = sv.h[li]
-            else:
-                hcur = hbuf
-                check(L.hcir_gelu_fwd_f16(sv.u[li].data_ptr(), m * self.mlp, hbuf.data_ptr(), st), "hcir_gelu_fwd_f16")
-            T.gemm_tn(dy16, hcur, g["fc2_w"], accumulate=False)
-            T.gelu_bwd_colsum(sv.u[li], big16, big16, g["fc1_b"], rows=m)     # d_u in place, + the fc1 bias gradient
-            self._gemm(big16, self.mlp, w["fc1_wt"], None, m, d, _lib.EPI_BIAS_F16, dln, st, "dgrad(fc1)")
-            if sv.ln2:
-                lncur = sv.ln2[li]
-            else:
-                lncur = lnbuf
-                self._ln(sv.x_mid[li], m, d, d, w["ln2_w"], w["ln2_b"], lnbuf, st)
-            T.gemm_tn(big16, lncur, g["fc1_w"], accumulate=False)
-            T.layernorm_bwd(sv.x_mid[li], dln, w["ln2_w"], self.eps, dres, dres, g["ln2_w"], g["ln2_b"],
-                            accumulate=False, rows=m, dres16=dy16, dres_colsum=g["proj_b"])
-            # ---- attention: x_mid = x_in + proj(attn(qkv(LN1(x_in))))
-            self._gemm(dy16, d, w["proj_wt"], None, m, d, _lib.EPI_BIAS_F16, datt, st, "dgrad(proj)")
-            T.gemm_tn(dy16, sv.att[li], g["proj_w"], accumulate=False)
-            T.attn_bwd(sv.qkv[li], sv.att[li], datt, sv.lse[li], b, t, self.heads, scale, dqkv)
-            self._gemm(dqkv, 3 * d, w["qkv_wt"], None, m, d, _lib.EPI_BIAS_F16, dln, st, "dgrad(qkv)")
-            if sv.ln1:
-                lncur = sv.ln1[li]
-            else:
-                lncur = lnbuf
-                self._ln(sv.x_in[li], m, d, d, w["ln1_w"], w["ln1_b"], lnbuf, st)
-            T.gemm_tn(dqkv, lncur, g["qkv_w"], accumulate=False)
-            T.colsum(dqkv, g["qkv_b"], accumulate=False, rows=m)
-            fc2_b_next = f32e(d) if li > 0 else None
-            T.layernorm_bwd(sv.x_in[li], dln, w["ln1_w"], self.eps, dres, dres, g["ln1_w"], g["ln1_b"],
-                            accumulate=False, rows=m, dres16=dy16 if li > 0 else None, dres_colsum=fc2_b_next)
+            rs, k = (last, lw) if li == len(self.lw) - 1 else (full, fw)
+            g, fc2_b = self._block_backward(self.lw[li], sv.blocks[li], b, t, rs, k, fw, fc2_b, li == 0)
             layer_grads.append(g)
         layer_grads.reverse()
         # ---- patch embedding: tok[b][0] = cls + pos_mult pos[0]; tok[b][1+p] = W patch + bias + pos_mult pos[1+p]
-        dtok = dres[:m].view(b, t, d)
+        dtok = fw.dres[:m].view(b, t, d)
         g_cls = dtok[:, 0].sum(0)
         g_pos = dtok.sum(0) * self.pos_mult
         npat = b * (t - 1)
-        dpatch = torch.zeros((_pad64(npat), d), dtype=torch.float16, device=dev)
+        dpatch = self._act(npat, d)
         dpatch[:npat] = dtok[:, 1:].reshape(npat, d)
-        g_cw = f32e(d, sv.patches.shape[1])
-        g_cb = f32e(d)
-        T.gemm_tn(dpatch, sv.patches, g_cw, accumulate=False)
-        T.colsum(dpatch, g_cb, accumulate=False, rows=npat)
+        g_cw, g_cb = self._acc(d, sv.patches.shape[1]), self._acc(d)
+        ops.gemm_tn(dpatch, sv.patches, g_cw, accumulate=False)
+        ops.colsum(dpatch, g_cb, accumulate=False, rows=npat)
         s = self.spec
         out = [g_cw.view(s.conv_w.shape), g_cb, g_cls.view(s.cls.shape), g_pos.view(s.pos.shape)]
         for g in layer_grads:
-            out += [g["ln1_w"], g["ln1_b"], g["qkv_w"], g["qkv_b"], g["proj_w"], g["proj_b"], g["ln2_w"], g["ln2_b"],
-                    g["fc1_w"], g["fc1_b"], g["fc2_w"], g["fc2_b"]]
+            out += [g[n] for n in _GRADS]
         out += [g_flw, g_flb]
         return out
+
+    def _block_backward(self, w, blk, b, t, rs, k, fw, fc2_b, first):
+        """The block's 12 gradients.  `k`: work buffers of the row set `rs`, whose k.dres arrives as dL / d(block
+        output) and is updated in place down to the attention; `fw`: those of the stream, whose fw.dres leaves as
+        dL / d(block input).  `fc2_b`: the fc2 bias gradient where the block behind already produced it together
+        with k.dy16 = fp16(k.dres).  Returns the gradients and that handoff for the block in front (None: `first`)."""
+        ops, d, m, rows = self.ops, self.dim, b * t, rs.rows
+        g = {n: self._acc(*w[n].shape) for n in _GRADS}
+        # ---- MLP: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
+        if fc2_b is None:
+            ops.add_to_f16(k.dres, None, k.dy16, rows)
+            ops.colsum(k.dy16, g["fc2_b"], accumulate=False, rows=rows)
+        else:
+            g["fc2_b"] = fc2_b
+        ops.gemm(k.dy16, w["fc2_wt"], None, rows, k.big16)                                     # dgrad(fc2): d_h
+        ops.gemm_tn(k.dy16, self._kept(blk.h, fw.hbuf, ops.gelu_fwd, blk.u, rows), g["fc2_w"], accumulate=False)
+        ops.gelu_bwd_colsum(blk.u, k.big16, k.big16, g["fc1_b"], rows=rows)   # d_u in place, + the fc1 bias gradient
+        ops.gemm(k.big16, w["fc1_wt"], None, rows, k.dln)                                      # dgrad(fc1)
+        ln2 = self._kept(blk.ln2, fw.lnbuf, ops.layernorm, blk.x_mid, rows, w["ln2_w"], w["ln2_b"], self.eps)
+        ops.gemm_tn(k.big16, ln2, g["fc1_w"], accumulate=False)
+        ops.layernorm_bwd(blk.x_mid, k.dln, w["ln2_w"], self.eps, k.dres, k.dres, g["ln2_w"], g["ln2_b"],
+                          accumulate=False, rows=rows, dres16=k.dy16, dres_colsum=g["proj_b"])
+        # ---- attention: x_mid = x_in + proj(attn(qkv(LN1(x_in)))); K / V gradients for every token
+        ops.gemm(k.dy16, w["proj_wt"], None, rows, k.datt)                                     # dgrad(proj)
+        ops.gemm_tn(k.dy16, blk.att, g["proj_w"], accumulate=False)
+        rs.attn_bwd(blk.qkv, blk.att, k.datt, blk.lse, b, t, self.heads, self.scale, fw.dqkv)
+        if k is not fw:
+            # the scatter: the class-token rows of the stream carry k.dres, every other row nothing (yet).  It has to
+            # stand here, before the LayerNorm backward that adds to fw.dres and hands fp16(fw.dres) on
+            fw.dres[:m].view(b, t, d)[:, 0] = k.dres[:b]
+        ops.gemm(fw.dqkv, w["qkv_wt"], None, m, fw.dln)                                        # dgrad(qkv)
+        ln1 = self._kept(blk.ln1, fw.lnbuf, ops.layernorm, blk.x_in, m, w["ln1_w"], w["ln1_b"], self.eps)
+        ops.gemm_tn(fw.dqkv, ln1, g["qkv_w"], accumulate=False)
+        ops.colsum(fw.dqkv, g["qkv_b"], accumulate=False, rows=m)
+        fc2_b_next = None if first else self._acc(d)
+        ops.layernorm_bwd(blk.x_in, fw.dln, w["ln1_w"], self.eps, fw.dres, fw.dres, g["ln1_w"], g["ln1_b"],
+                          accumulate=False, rows=m, dres16=None if first else fw.dy16, dres_colsum=fc2_b_next)
+        return g, fc2_b_next
 
 
 class _VitClsFn(torch.autograd.Function):
