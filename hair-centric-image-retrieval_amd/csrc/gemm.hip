@@ -19,6 +19,7 @@
 // issuer (GemmStages<G>) and ONE LDS-transposing epilogue (gemm_epilogue_lds).
 #include "sim_core.h"
 #include "act.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -26,8 +27,8 @@ namespace {
 using GemmCfg = SimCfg<_Float16, 2, 2, 2>;  // GM = 128 W rows, QB = 128 A rows
 
 // Internal epilogue codes of hcir_gemm_f16_fused (persistent kernel only), beyond hcir_epilogue:
-//   EPI_RESID_F16_STATS: BIAS_RESID_F16 that also writes per-row partial (sum, sum of squares) of the stored
-//                        fp16 rows, one slice per 64 output features, for the LayerNorm that reads them next;
+//   EPI_RESID_F16_STATS: BIAS_RESID_F16 that also writes per-row partial (mean, M2 = sum of squared deviations
+//                        from it) of the stored fp16 rows, one slice per 64 output features, for the LayerNorm that reads them next;
 //   EPI_LN_BIAS_F16 / EPI_LN_BIAS_GELU_F16: the A rows are the RAW residual rows x and W carries the
 //                        LayerNorm gamma (W' = gamma o W): out = act(rstd[m] (acc - mean[m] c1[n]) + bias[n])
 //                        with c1[n] = sum_k W'[n][k], bias[n] = sum_k beta[k] W[n][k] + b[n]  (LayerNorm folded
@@ -47,7 +48,7 @@ struct GemmArgs {
   int n, k;
   const float* ln_stats;  // [m][2] (mean, rstd) of the A rows           (EPI_LN_*)
   const float* ln_c1;     // [n]                                           (EPI_LN_*)
-  float* stats_part;      // [n/64][m][2] partial (sum, sumsq) of out rows (EPI_RESID_F16_STATS)
+  float* stats_part;      // [n/64][m][2] partial (mean, M2) of out rows  (EPI_RESID_F16_STATS)
   const void* resid;      // residual rows of the *_RESID_* epilogues (same type and row pitch as out); == out: in place
   void* out2;             // second fp16 output of EPI_BIAS_F16_DUAL_GELU (row pitch ldo)
   int64_t stats_ld = 0;   // rows per slice of stats_part (0: m) - a launch over a row range of a larger matrix
@@ -1037,10 +1038,7 @@ __global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int par
   *reinterpret_cast<f32x2*>(stats + 2 * row) = (f32x2){mean, 1.0f / sqrtf(var + eps)};
 }
 
-// Which kernel a launch takes, callee first: launch_gemm -> launch_gemm_big -> launch_big_tiles / launch_gemm_mid.
-inline bool gemm_takes_big(int64_t m, int n, int k) { return k % 64 == 0 && m >= 1024 && n % 256 == 0; }
-inline bool gemm_takes_mid(int64_t m, int n, int k) { return k % 64 == 0 && m >= 1024 && n % 128 == 0; }
-
+// Which kernel a launch takes: gemm_plan.h.
 template <int EPI>
 void launch_gemm_mid(const GemmArgs& g, hipStream_t st) {
   const int tn = g.n / GMid::TN, tm = (int)hcir_cdiv(g.m, GMid::TM);
@@ -1056,19 +1054,12 @@ void launch_big_tiles(const GemmArgs& g, int tn, int tm, hipStream_t st) {
 }
 
 template <int EPI>
-void launch_gemm_big(const GemmArgs& g, hipStream_t st) {
-  const int tn = (int)hcir_cdiv(g.n, 256), tm = (int)hcir_cdiv(g.m, 256);
+void launch_gemm_big(const GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+  // (the dual-output epilogue exists on the 256 x 256 kernel only: gemm_plan never sends it elsewhere)
   if constexpr (EPI != EPI_BIAS_F16_DUAL_GELU) {
-    // Tail split: when the last round of 256 x 256 tiles would be less than half full (64 images: fc1 = 600 tiles = 2.34
-    // rounds; ViT-L/14 at 128 images: 516 / 1548 / 2064 tiles = 2.02 / 6.05 / 8.06 rounds - a whole round for a sliver),
-    // the m-tiles that fill whole rounds run on the 256 x 256 kernel and the remaining ROWS go to the 128 x 192 kernel
-    // as a second launch (pointers advanced to the row range; the per-row statistics keep the full matrix's slice pitch).
-    const int ntiles = tn * tm;
-    const int tm1 = (ntiles / 256) * 256 / tn;          // m-tiles of the whole rounds
-    const int tail_tiles = ntiles - tm1 * tn;
-    const int64_t m1 = (int64_t)tm1 * 256;
-    if (ntiles > 256 && tm1 > 0 && tm1 < tm && tail_tiles < 128 && g.n % GMid::TN == 0 &&
-        (g.n / GMid::TN) * hcir_cdiv(g.m - m1, GMid::TM) <= 512) {
+    if (p.route == HCIR_GEMM_ROUTE_SPLIT) {
+      // pointers advanced to the row range; the per-row statistics keep the full matrix's slice pitch
+      const int64_t m1 = p.m1;
       GemmArgs g1 = g, g2 = g;
       g1.m = m1;
       g1.stats_ld = g.stats_ld ? g.stats_ld : g.m;
@@ -1081,34 +1072,29 @@ void launch_gemm_big(const GemmArgs& g, hipStream_t st) {
       if (g.resid) g2.resid = static_cast<const char*>(g.resid) + obytes;
       if (g.ln_stats) g2.ln_stats = g.ln_stats + 2 * m1;
       if (g.stats_part) g2.stats_part = g.stats_part + 2 * m1;
-      launch_big_tiles<EPI>(g1, tn, tm1, st);
+      launch_big_tiles<EPI>(g1, p.tn, p.tm1, st);
       launch_gemm_mid<EPI>(g2, st);
       return;
     }
-    // Small M: a launch whose 256 x 256 tiles fill less than 0.7 of ONE round of the 256 CUs (64 images: proj / fc2
-    // give 150 tiles) runs on the 128 x 192 kernel at two workgroups per CU instead - 2.7 x the tiles, every CU busy;
-    // its results are bit-identical (same k order).  12 % slower per flop on full rounds, which is why only these take it.
-    if (tn * tm * 10 < 256 * 7 && g.n % GMid::TN == 0 && (g.n / GMid::TN) * hcir_cdiv(g.m, GMid::TM) <= 512) {
+    if (p.route == HCIR_GEMM_ROUTE_MID) {
       launch_gemm_mid<EPI>(g, st);
       return;
     }
   }
-  launch_big_tiles<EPI>(g, tn, tm, st);
+  launch_big_tiles<EPI>(g, p.tn, p.tm, st);
 }
 
 template <int EPI>
 void launch_gemm(const GemmArgs& g, hipStream_t st) {
-  if (gemm_takes_big(g.m, g.n, g.k)) {
-    launch_gemm_big<EPI>(g, st);
+  const GemmPlan p = gemm_plan(g.m, g.n, g.k, EPI == EPI_BIAS_F16_DUAL_GELU);
+  if (p.route != HCIR_GEMM_ROUTE_SMALL) {
+    launch_gemm_big<EPI>(g, p, st);
     return;
   }
-  const int tiles_n = (int)hcir_cdiv(g.n, 128), tiles_m = (int)hcir_cdiv(g.m, 128);
   if (g.k % 64 == 0)
-    hipLaunchKernelGGL((gemm_f16_kernel<EPI, true>), dim3(tiles_n * tiles_m), dim3(256), 0, st, g,
-                       tiles_n, tiles_m);
+    hipLaunchKernelGGL((gemm_f16_kernel<EPI, true>), dim3(p.tn * p.tm), dim3(256), 0, st, g, p.tn, p.tm);
   else
-    hipLaunchKernelGGL((gemm_f16_kernel<EPI, false>), dim3(tiles_n * tiles_m), dim3(256), 0, st, g,
-                       tiles_n, tiles_m);
+    hipLaunchKernelGGL((gemm_f16_kernel<EPI, false>), dim3(p.tn * p.tm), dim3(256), 0, st, g, p.tn, p.tm);
 }
 
 }  // namespace
@@ -1129,6 +1115,10 @@ int hcir_gemm_f16_resid(const void* a, int64_t lda, const void* w, int64_t ldw, 
   if (!a || !w || !out || m <= 0 || n <= 0 || k <= 0) return HCIR_ERR_INVALID;
   if ((k & 7) || (n & 7) || lda < k || ldw < k || (lda & 7) || (ldw & 7) || ldo < n || (ldo & 3))
     return HCIR_ERR_INVALID;
+  // fp16 outputs of the persistent kernels are stored as 16-byte pieces of a row
+  const bool f16out = epilogue == HCIR_EPI_BIAS_F16 || epilogue == HCIR_EPI_BIAS_GELU_F16 ||
+                      epilogue == HCIR_EPI_AFFINE_RELU_F16 || epilogue == HCIR_EPI_BIAS_RESID_F16;
+  if (f16out && gemm_takes_big(m, n, k) && (ldo & 7)) return HCIR_ERR_INVALID;
   // row pitches other than k: only the 256x256 persistent kernel carries separate pitches
   if ((lda != k || ldw != k) && !gemm_takes_big(m, n, k)) return HCIR_ERR_UNSUPPORTED;
   if ((epilogue == HCIR_EPI_AFFINE_RELU_F16 || epilogue == HCIR_EPI_AFFINE_F32) && !scale)
@@ -1159,7 +1149,7 @@ int hcir_gemm_f16_gelu_dual(const void* a, int64_t lda, const void* w, int64_t l
   if (!gemm_takes_big(m, n, k)) return HCIR_ERR_UNSUPPORTED;
   GemmArgs g{static_cast<const _Float16*>(a), static_cast<const _Float16*>(w), bias, nullptr, out_pre, m,
              lda, ldw, ldo, n, k, nullptr, nullptr, nullptr, out_pre, out_act};
-  launch_gemm_big<EPI_BIAS_F16_DUAL_GELU>(g, static_cast<hipStream_t>(stream));
+  launch_gemm_big<EPI_BIAS_F16_DUAL_GELU>(g, gemm_plan(m, n, k, true), static_cast<hipStream_t>(stream));
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }
@@ -1173,6 +1163,15 @@ int hcir_debug_gemm_stamps(unsigned long long* host_dst) {
 int hcir_gemm_fused_supported(int64_t m, int32_t n, int32_t k) { return gemm_takes_big(m, n, k) ? 1 : 0; }
 
 int32_t hcir_gemm_stats_slices(int32_t n) { return n / 64; }
+
+int hcir_gemm_route(int64_t m, int32_t n, int32_t k, int epilogue, int64_t* rows_on_big) {
+  if (m <= 0 || n <= 0 || k <= 0 || (k & 7) || (n & 7)) return HCIR_ERR_INVALID;
+  if (epilogue < HCIR_EPI_BIAS_F16 || (epilogue > HCIR_EPI_BIAS_RESID_F16 && epilogue != HCIR_GEMM_ROUTE_EPI_DUAL))
+    return HCIR_ERR_INVALID;
+  const GemmPlan p = gemm_plan(m, n, k, epilogue == HCIR_GEMM_ROUTE_EPI_DUAL);
+  if (rows_on_big) *rows_on_big = p.m1;
+  return p.route;
+}
 
 int hcir_gemm_f16_fused(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
                         const float* scale, int64_t m, int32_t n, int32_t k, int epilogue, void* out,
@@ -1192,9 +1191,10 @@ int hcir_gemm_f16_fused(const void* a, int64_t lda, const void* w, int64_t ldw, 
   GemmArgs g{static_cast<const _Float16*>(a), static_cast<const _Float16*>(w), bias, scale, out, m,
              lda, ldw, ldo, n, k, ln_stats, ln_c1, stats_part, out, nullptr};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_part) launch_gemm_big<EPI_RESID_F16_STATS>(g, st);
-  else if (epilogue == HCIR_EPI_BIAS_F16) launch_gemm_big<EPI_LN_BIAS_F16>(g, st);
-  else launch_gemm_big<EPI_LN_BIAS_GELU_F16>(g, st);
+  const GemmPlan p = gemm_plan(m, n, k, false);
+  if (stats_part) launch_gemm_big<EPI_RESID_F16_STATS>(g, p, st);
+  else if (epilogue == HCIR_EPI_BIAS_F16) launch_gemm_big<EPI_LN_BIAS_F16>(g, p, st);
+  else launch_gemm_big<EPI_LN_BIAS_GELU_F16>(g, p, st);
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

@@ -23,6 +23,8 @@ LIB_PATH = os.environ.get("HCIR_LIB_PATH") or os.path.join(CSRC_DIR, "libhcir.so
 F32, F16, BF16 = 0, 1, 2
 EPI_BIAS_F16, EPI_BIAS_GELU_F16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_AFFINE_RELU_F16, EPI_AFFINE_F32, \
     EPI_BIAS_RESID_F16 = range(7)
+GEMM_ROUTE_SMALL, GEMM_ROUTE_MID, GEMM_ROUTE_BIG, GEMM_ROUTE_SPLIT = range(4)   # hcir_gemm_route
+GEMM_ROUTE_EPI_DUAL = 10
 
 _lib = None
 
@@ -55,6 +57,7 @@ SIGNATURES = {
     "hcir_gemm_f16_gelu_dual": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "hcir_gemm_fused_supported": (c_int, [c_i64, c_i32, c_i32]),
     "hcir_gemm_stats_slices": (c_i32, [c_i32]),
+    "hcir_gemm_route": (c_int, [c_i64, c_i32, c_i32, c_int, c_vp]),
     "hcir_gemm_f16_fused": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_int,
                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "hcir_ln_stats_finalize": (c_int, [c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),

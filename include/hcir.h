@@ -173,7 +173,8 @@ typedef enum {
  * nn.Linear weight as stored).  Replaces nn.Linear / MultiheadAttention
  * in_proj / out_proj / MLPBlock / timm Mlp  (HP/src/models_vit.py:63,66,70,79;
  * HP/src/main_backbone.py:554 -> torchvision EncoderBlock).
- * Requirements: K % 8 == 0, N % 8 == 0; bias may be NULL.  lda / ldw are row pitches in
+ * Requirements: K % 8 == 0, N % 8 == 0; ldo >= N and a multiple of 4, of 8 for an fp16 output on the persistent
+ * kernels (M >= 1024, N % 256 == 0, K % 64 == 0: rows are stored in 16-byte pieces); bias may be NULL.  lda / ldw are row pitches in
  * elements (>= K, multiples of 8); pitches other than K are carried by the persistent
  * 256 x 256 kernel only (M >= 1024, N % 256 == 0, K % 64 == 0), else HCIR_ERR_UNSUPPORTED. */
 int hcir_gemm_f16(const void* a, int64_t lda, const void* w, int64_t ldw,
@@ -214,6 +215,22 @@ int hcir_gemm_f16_gelu_dual(const void* a, int64_t lda, const void* w, int64_t l
  * Exactly one of {ln_stats + ln_c1, stats_part} must be given.  scale as in hcir_gemm_f16. */
 int hcir_gemm_fused_supported(int64_t m, int32_t n, int32_t k);
 int32_t hcir_gemm_stats_slices(int32_t n);
+/* Which kernel hcir_gemm_f16 / _resid / _fused (epilogue: an hcir_epilogue value) or hcir_gemm_f16_gelu_dual
+ * (epilogue: HCIR_GEMM_ROUTE_EPI_DUAL) takes for an M x N x K problem; host arithmetic only, nothing is launched:
+ *   SMALL  the 128 x 128 kernel (also every shape the fused and dual calls refuse);
+ *   MID    the whole launch on the persistent 128 x 192 kernel;
+ *   BIG    the whole launch on the persistent 256 x 256 kernel (256 workgroups; more tiles: several per workgroup);
+ *   SPLIT  rows [0, *rows_on_big) on the 256 x 256 kernel, the rest as a second launch on the 128 x 192 kernel.
+ * *rows_on_big (may be NULL) receives the rows the 256 x 256 kernel computes: M on BIG, 0 on SMALL and MID.
+ * Returns the route, or HCIR_ERR_INVALID (m, n, k < 1, n or k no multiple of 8, unknown epilogue). */
+typedef enum {
+  HCIR_GEMM_ROUTE_SMALL = 0,
+  HCIR_GEMM_ROUTE_MID = 1,
+  HCIR_GEMM_ROUTE_BIG = 2,
+  HCIR_GEMM_ROUTE_SPLIT = 3
+} hcir_gemm_route_kind;
+#define HCIR_GEMM_ROUTE_EPI_DUAL 10
+int hcir_gemm_route(int64_t m, int32_t n, int32_t k, int epilogue, int64_t* rows_on_big);
 int hcir_gemm_f16_fused(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
                         const float* scale, int64_t m, int32_t n, int32_t k, int epilogue,
                         void* out, int64_t ldo, const float* ln_stats, const float* ln_c1,

@@ -308,7 +308,7 @@ def test_gemm_big_and_mid_kernels_same_bits(L, same_bits_problem, case):
 
 @pytest.mark.parametrize("m,d,mlp", [(1500, 256, 512), (197 * 6, 768, 3072), (197 * 64, 768, 3072)])
 def test_gemm_fused_layernorm(L, m, d, mlp):
-    """hcir_gemm_f16_fused: (1) the fp16-residual epilogue also emits per-row (sum, sumsq) slices ->
+    """hcir_gemm_f16_fused: (1) the fp16-residual epilogue also emits per-row (mean, M2) slices ->
     hcir_ln_stats_finalize -> (mean, rstd) of the STORED rows; (2) the consumer GEMM reads the raw rows and
     applies LayerNorm algebraically.  Checked against torch LayerNorm + Linear (+ GELU) in fp32."""
     g = torch.Generator().manual_seed(m + d)
