@@ -460,6 +460,7 @@ int hcir_layernorm_bwd_fused(const void* x, int x_dtype, int64_t rows, int32_t d
   if (!x || !dy_f16 || !gamma || !dres_out || !dgamma || !dbeta || !workspace) return HCIR_ERR_INVALID;
   if (rows <= 0 || d <= 0 || (d & 3) || d > 4 * 64 * kLnMaxJ || ldx < d || lddy < d || ldr < d || (ldr & 3))
     return HCIR_ERR_INVALID;
+  if ((ldx & 3) || (lddy & 3)) return HCIR_ERR_INVALID;  // rows are loaded four elements at a time
   if (dres_colsum && !dres_f16) return HCIR_ERR_INVALID;
   if (dres_f16 && (ldh < d || (ldh & 3))) return HCIR_ERR_INVALID;
   if (x_dtype != HCIR_F32 && x_dtype != HCIR_F16) return HCIR_ERR_UNSUPPORTED;

@@ -453,6 +453,8 @@ int hcir_add_f32_f16(const float* a, const float* b, int64_t n, void* y, void* s
  *   dres_out[row] = (dres_in ? dres_in[row] : 0) + dx            fp32, row pitch ldr (dres_out may alias dres_in)
  *   dgamma (+)= sum_rows dy o xhat,  dbeta (+)= sum_rows dy       (accumulate != 0: added to the existing values)
  * x is the layer's INPUT (residual stream, HCIR_F32 or HCIR_F16; statistics are recomputed), dy fp16.
+ * Requirements: d % 4 == 0, d <= 4096; ldx, lddy, ldr >= d and each a multiple of 4 (rows are read and written
+ * four elements at a time), else HCIR_ERR_INVALID.
  * workspace: 2 * hcir_layernorm_bwd_blocks(rows) * d floats (two-stage, fixed-order column sums). */
 int32_t hcir_layernorm_bwd_blocks(int64_t rows);
 int hcir_layernorm_bwd(const void* x, int x_dtype, int64_t rows, int32_t d, int64_t ldx, const void* dy_f16,
@@ -462,7 +464,8 @@ int hcir_layernorm_bwd(const void* x, int x_dtype, int64_t rows, int32_t d, int6
 /* hcir_layernorm_bwd that also writes dres_f16[row] = fp16(dres_out[row]) (row pitch ldh) - the operand of the next
  * dgrad / wgrad GEMM, otherwise one hcir_add_f32_f16 pass - and, if dres_colsum != NULL, dres_colsum[c] = sum_rows of
  * that fp16 copy - the bias gradient of the Linear layer whose output gradient it is, otherwise one hcir_colsum_f16
- * pass.  dres_f16 NULL: exactly hcir_layernorm_bwd.  workspace: 3 * hcir_layernorm_bwd_blocks(rows) * d floats. */
+ * pass.  dres_f16 NULL: exactly hcir_layernorm_bwd.  ldh >= d, ldh % 4 == 0; dres_colsum needs dres_f16 and is
+ * assigned whatever `accumulate` says.  workspace: 3 * hcir_layernorm_bwd_blocks(rows) * d floats. */
 int hcir_layernorm_bwd_fused(const void* x, int x_dtype, int64_t rows, int32_t d, int64_t ldx, const void* dy_f16,
                              int64_t lddy, const float* gamma, float eps, const float* dres_in, float* dres_out,
                              int64_t ldr, float* dgamma, float* dbeta, int accumulate, void* dres_f16, int64_t ldh,

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle import rowops as ro
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,6 +35,8 @@ def test_gelu_fwd_bwd():
     assert (h.double() - ref.detach()).abs().max() <= 2e-3 * 8 and _rel(h, ref.detach()) <= 1e-3
     assert (du.double() - ud.grad).abs().max() <= 4e-3          # |dh| <= ~5, fp16 output rounding
     assert torch.isfinite(h).all() and torch.isfinite(du).all()
+    # every element inside oracle.rowops's derived bounds
+    assert ro.ratio(h, *ro.gelu_fwd_f64(u)) <= 1.0 and ro.ratio(du, *ro.gelu_bwd_f64(u, dh)) <= 1.0
 
 
 @pytest.mark.parametrize("xdt", [torch.float16, torch.float32])
@@ -56,6 +60,10 @@ def test_layernorm_bwd(xdt, rows, d):
     assert _rel(out.cpu(), xd.grad + dres.double()) <= 2e-5
     assert _rel(dgam.cpu() - 0.5, gd.grad) <= 2e-5
     assert _rel(dbet.cpu() + 0.25, bd.grad) <= 2e-5
+    old = (torch.full((d,), 0.5), torch.full((d,), -0.25))
+    ref = ro.layernorm_bwd_f64(x, dy, gamma, 1e-6, dres, old, 1)           # every element, oracle.rowops's bounds
+    for got, key in ((out, "dres"), (dgam, "dgamma"), (dbet, "dbeta")):
+        assert ro.ratio(got.cpu(), *ref[key]) <= 1.0, key
     out2 = torch.empty(rows, d, device="cuda")
     T.layernorm_bwd(x.cuda(), dy.cuda(), gamma.cuda(), 1e-6, None, out2, dgam, dbet, accumulate=False)
     assert _rel(out2.cpu(), xd.grad) <= 2e-5 and _rel(dgam.cpu(), gd.grad) <= 2e-5
@@ -100,6 +108,7 @@ def test_layernorm_bwd_fused_copy_and_colsum(rows, d):
     assert torch.equal(o0, o1) and torch.equal(ga0, ga1) and torch.equal(be0, be1)
     assert torch.equal(h16, T.add_to_f16(o0))
     assert (cs.cpu().double() - h16.cpu().double().sum(0)).abs().max() <= 1e-4 * np.sqrt(rows)
+    assert ro.ratio(cs, *ro.dres_colsum_f64(h16)) <= 1.0
     # the copy alone (no column sums)
     h2 = torch.zeros_like(h16)
     T.layernorm_bwd(x, dy, gamma, 1e-6, dres, o1, ga1, be1, accumulate=False, dres16=h2)
@@ -119,6 +128,7 @@ def test_gelu_bwd_colsum_equals_the_two_kernels(m, n):
     cs = torch.full((n,), 5.0, device="cuda")
     T.gelu_bwd_colsum(u, dh, du, cs)
     assert torch.equal(du, du_ref) and torch.equal(cs, cs_ref)
+    assert ro.ratio(du, *ro.gelu_bwd_f64(u, dh)) <= 1.0 and ro.ratio(cs, *ro.colsum_f64(du)) <= 1.0
     dh2 = dh.clone()
     T.gelu_bwd_colsum(u, dh2, dh2, cs, accumulate=True)            # in place, accumulating
     assert torch.equal(dh2, du_ref) and torch.allclose(cs, 2 * cs_ref, rtol=1e-6, atol=1e-6)
@@ -132,8 +142,10 @@ def test_colsum(m, n):
     T.colsum(x.cuda(), out, accumulate=True)
     ref = x.double().sum(0) + 2.0
     assert (out.cpu().double() - ref).abs().max() <= 1e-4 * np.sqrt(m)
+    assert ro.ratio(out.cpu(), *ro.colsum_f64(x, torch.full((n,), 2.0), 1)) <= 1.0
     T.colsum(x.cuda(), out, accumulate=False)
     assert (out.cpu().double() - (ref - 2.0)).abs().max() <= 1e-4 * np.sqrt(m)
+    assert ro.ratio(out.cpu(), *ro.colsum_f64(x)) <= 1.0
 
 
 @pytest.mark.parametrize("m,n,k", [(64, 256, 256), (1984, 768, 768), (12608, 2304, 768), (6400, 768, 3072),

@@ -397,6 +397,9 @@ def test_layernorm(L, rows, d, xdt):
                                 bd.data_ptr(), 1e-6, y.data_ptr(), d, _st()) == 0
     # fp16 output rounding: 2^-11 relative
     np.testing.assert_allclose(y.float().cpu().numpy(), ref.numpy(), atol=2e-3 * ref.abs().max().item(), rtol=0)
+    from oracle import rowops as ro
+    from oracle.attention import f32
+    assert ro.ratio(y.cpu(), *ro.layernorm_f64(x, w, b, f32(1e-6))) <= 1.0       # every element, the derived bound
 
 
 @pytest.mark.parametrize("b,t,h", [(2, 197, 12), (1, 17, 2), (3, 64, 4), (2, 257, 16), (1, 33, 1), (1, 288, 2)])
