@@ -9,7 +9,11 @@ the same fp16 channels_last tensors with fp32 parameters; e_hip = ours.  The pro
 
 with floors that are derived, not measured: 2^-11 for tensors stored in fp16 (y, dx, dresid: one fp16 rounding) and
 2^-20 for fp32 vectors (save_mean, save_rstd, running statistics, dgamma, dbeta: 16 fp32 ulps over a vector norm).
-Every pair is printed; the recorded values are in profiles/bn2d_errors.txt and DESIGN.md §3.4."""
+Every pair is printed; the recorded values are in profiles/bn2d_errors.txt and DESIGN.md §3.4.
+
+G1 to G5 run small maps (at most 4 passes per chunk, one apply trip, one chunk per finalize lane); G6 keeps this
+end-to-end comparison at the plans a training batch runs.  A norm over 10^5 to 10^7 elements does not see a wrong or
+unwritten row: tests/test_bn2d_elements_gpu.py holds every element and channel."""
 import os
 import sys
 
@@ -133,6 +137,30 @@ G1_SHAPES = [(2, 1, 1, 64),        # M = 2: the smallest legal
              (4, 7, 7, 2048),      # the widest C: a row is four wavefronts' work
              (4, 14, 14, 256),
              (3, 28, 28, 128)]
+G3_SHAPE = (4, 14, 14, 64)
+G4_SAME_BITS_SHAPES = [(1, 56, 56, 64), (4, 7, 7, 2048)]
+G4_MASK_SHAPES = [(3, 5, 5, 64), (4, 14, 14, 256)]
+G4_BUFFERS_SHAPE = (4, 14, 14, 256)
+G4_RUNNING_SHAPE = (3, 5, 5, 64)
+G5_SHAPE = (4, 14, 14, 256)
+G5_SHORTCUT_SHAPE = (4, 14, 14, 64)
+G6_SHAPES = [(61, 13, 13, 2048), (3, 67, 67, 320)]
+
+
+def _g2_pick():
+    """the smallest B x 56 x 56 x 64 map with at least 3 chunks and a ragged last one: (B, M, chunks, rows per chunk)"""
+    for b in range(1, 9):
+        m = b * 56 * 56
+        chunks, rows = _plan_c64(m)
+        if chunks >= 3 and m % rows != 0:
+            return b, m, chunks, rows
+    return None
+
+
+def small_map_shapes():
+    """every shape G1 to G5 run (tests/test_bn2d_host.py asserts that they all take the small-map branch of the plan)"""
+    return (G1_SHAPES + [(_g2_pick()[0], 56, 56, 64), G3_SHAPE, G4_BUFFERS_SHAPE, G4_RUNNING_SHAPE, G5_SHAPE,
+                         G5_SHORTCUT_SHAPE] + G4_SAME_BITS_SHAPES + G4_MASK_SHAPES)
 
 
 @pytest.mark.parametrize("resid", [False, True])
@@ -144,13 +172,7 @@ def test_g1_shapes_vs_float64(shape, relu, resid):
 
 def test_g2_several_chunks_with_a_ragged_last_one():
     from hcir import ops
-    pick = None
-    for b in range(1, 9):
-        m = b * 56 * 56
-        chunks, rows = _plan_c64(m)
-        if chunks >= 3 and m % rows != 0:
-            pick = (b, m, chunks, rows)
-            break
+    pick = _g2_pick()
     assert pick is not None
     b, m, chunks, rows = pick
     assert ops.bn2d_chunks(m, 64) == chunks >= 3 and m - (chunks - 1) * rows < rows     # the plan the kernel ran
@@ -162,7 +184,7 @@ def test_g2_several_chunks_with_a_ragged_last_one():
 def test_g3_large_mean():
     """x = 100 + 0.25 randn: sum x^2 - (sum x)^2 / n in fp32 loses mean^2 / var = 1.6e5 of its 1.7e7, the variance
     would be off by percents; save_rstd and running_var are held to the same criterion as everything else."""
-    shape = (4, 14, 14, 64)
+    shape = G3_SHAPE
     G, REF, HIP = _case(shape, False, False, seed=13, large_mean=True)
     assert abs(G["save_mean"].mean().item() - 100.0) < 0.1 and abs(G["save_rstd"].mean().item() - 4.0) < 0.5
     _hold(f"G3 {shape} mean=100", G, REF, HIP)
@@ -170,7 +192,7 @@ def test_g3_large_mean():
 
 def test_g4_two_calls_same_bits():
     from hcir import ops
-    for shape in [(1, 56, 56, 64), (4, 7, 7, 2048)]:
+    for shape in G4_SAME_BITS_SHAPES:
         inp = {k: v.cuda() for k, v in _inputs(shape, seed=14).items()}
         outs = []
         for _ in range(2):
@@ -184,7 +206,7 @@ def test_g4_two_calls_same_bits():
 
 def test_g4_relu_mask_and_residual_gradient_exact():
     from hcir import ops
-    for shape in [(3, 5, 5, 64), (4, 14, 14, 256)]:
+    for shape in G4_MASK_SHAPES:
         inp = {k: v.cuda() for k, v in _inputs(shape, seed=15).items()}
         y, mean, rstd = ops.bn2d_fwd(inp["x"], inp["gamma"], inp["beta"], EPS, MOMENTUM, inp["resid"], True)
         assert (y >= 0).all() and (y == 0).any() and (y > 0).any()
@@ -199,7 +221,7 @@ def test_g4_relu_mask_and_residual_gradient_exact():
 
 def test_g4_without_running_buffers():
     from hcir import ops
-    inp = {k: v.cuda() for k, v in _inputs((4, 14, 14, 256), seed=16).items()}
+    inp = {k: v.cuda() for k, v in _inputs(G4_BUFFERS_SHAPE, seed=16).items()}
     rm, rv = inp["rm"].clone(), inp["rv"].clone()
     y0, mean0, rstd0 = ops.bn2d_fwd(inp["x"], inp["gamma"], inp["beta"], EPS, MOMENTUM, None, False, rm, rv)
     y1, mean1, rstd1 = ops.bn2d_fwd(inp["x"], inp["gamma"], inp["beta"], EPS, MOMENTUM, None, False, None, None)
@@ -209,7 +231,7 @@ def test_g4_without_running_buffers():
 
 @pytest.mark.parametrize("random_buffers", [False, True])
 def test_g4_running_statistics_move_toward_the_unbiased_variance(random_buffers):
-    shape = (3, 5, 5, 64)       # M = 75: M / (M - 1) = 1.0135, far outside the criterion if the biased variance is used
+    shape = G4_RUNNING_SHAPE    # M = 75: M / (M - 1) = 1.0135, far outside the criterion if the biased variance is used
     inp = _inputs(shape, seed=17, random_buffers=random_buffers)
     G, REF, HIP = (_torch_run(inp, False, False, "cpu", torch.float64),
                    _torch_run(inp, False, False, "cuda", torch.float16), _hip_run(inp, False, False))
@@ -233,7 +255,7 @@ def _bn(c, inp):
 
 def test_g5_bn_act_autograd():
     from hcir.conv_train import bn_act_nhwc
-    shape = (4, 14, 14, 256)
+    shape = G5_SHAPE
     inp = _inputs(shape, seed=18)
     G, REF = _torch_run(inp, True, True, "cpu", torch.float64), _torch_run(inp, True, True, "cuda", torch.float16)
     bn = _bn(shape[3], inp)
@@ -254,7 +276,7 @@ def test_g5_identity_shortcut_sums_both_gradients():
     """relu(bn(conv(a)) + a): `a` feeds the convolution and is the residual, the wiring of a BasicBlock without a
     downsample branch; autograd adds the convolution's data gradient and the residual branch's."""
     from hcir.conv_train import bn_act_nhwc, conv2d_nhwc
-    shape = (4, 14, 14, 64)
+    shape = G5_SHORTCUT_SHAPE
     inp = _inputs(shape, seed=19)
     w = (torch.randn(64, 64, 3, 3, generator=torch.Generator().manual_seed(20)) / 24.0).half().float()
 
@@ -284,3 +306,17 @@ def test_g5_identity_shortcut_sums_both_gradients():
     alone = torch.where(HIP["y"] > 0, inp["dy"].double(), torch.zeros(()).double())
     assert rel(HIP["input"], alone) > 0.1
     _hold(f"G5 shortcut {shape}", G, REF, HIP)
+
+
+@pytest.mark.parametrize("shape", G6_SHAPES, ids=str)
+def test_g6_capped_and_strided_plans(shape):
+    """The same end-to-end criterion against torch's kernels at the plans a training batch runs: the chunk count
+    clamped by the grid cap with 6 passes per chunk and 6 apply trips, and 2 apply trips over 5 channel slabs; both
+    with several chunks per finalize lane (tests/test_bn2d_elements_gpu.py holds every element of these shapes)."""
+    from hcir import ops
+    from oracle import bn2d as ob
+    m, c = ob.rows_of(shape), shape[3]
+    p = ob.plan(m, c)
+    assert ops.bn2d_chunks(m, c) == p.chunks and p.per >= 2 and p.trips >= 2
+    assert (p.clamped, p.chunk_passes, p.trips, p.slabs) == ((True, 6, 6, 4) if c == 2048 else (False, 4, 2, 5))
+    _hold(f"G6 {shape} relu=1 resid=1", *_case(shape, True, True, seed=21))
