@@ -2,12 +2,10 @@
 //
 // Replaces Attention.forward (HP/src/models_vit.py:69-78) and the
 // nn.MultiheadAttention inside torchvision's EncoderBlock (HP/src/main_backbone.py:554):
-//   out = softmax((q * scale) k^T) v   per (batch, head), head_dim 64.
+//   out = softmax((q * scale) k^T) v   per (batch, head).
 //
-// One 4-wave workgroup per (b, head); wave w owns query tiles w, w+4, ... (32 rows each);
-// K and V of the head (T x 64 fp16 each) are staged ONCE into LDS and shared by all waves.
-// Four waves (not one per query tile) keep two workgroups resident per CU, so one workgroup's
-// K/V staging latency hides under the other's MFMAs.
+// The arithmetic of one 32-row query tile is written ONCE (the attn_* helpers below) and is shared by the three
+// kernels, so that their results agree by construction:
 //   S^T = K . Q^T   : MFMA 32x32x16 f16, keys on the MFMA row, queries on the column
 //                     -> a lane owns ONE query and holds its scores in registers:
 //                     row max / exp2 / row sum need one cross-half shuffle only.
@@ -15,24 +13,212 @@
 //                     B operand of the second MFMA (cdna_hip_programming.md §3, "An
 //                     accumulator tile as the next MFMA's operand"); the A operand V^T is
 //                     read from the row-major V image with ds_read_b64_tr_b16 (T10).
-// LDS images: K rows are 128 B, 16-B slots XOR-swizzled with (key>>1)&7 (ds_read_b128
-// conflict-free); V rows are 128 B with the two 64-B halves swapped when key bit 1 is
-// set (the 4-row x 32-col transposed reads of a half-wave then cover all 64 banks).
+// The kernels keep what differs between them: how K, V and Q reach LDS and registers, which tiles a wave walks, the
+// barriers and the waits.
+//   attn_fwd_kernel<NKT>              head_dim 64: one 4-wave workgroup per (b, head), wave w owns query tiles w,
+//                                     w+4, ...; K and V of the head are staged ONCE into LDS by LDS-DMA and shared by
+//                                     all waves.  Four waves (not one per query tile) keep two workgroups resident
+//                                     per CU, so one workgroup's K/V staging latency hides under the other's MFMAs.
+//   attn_fwd2_kernel                  head_dim 64, T in (192, 224], all query rows: persistent, double-buffered.
+//   attn_fwd_generic_kernel<HD, NKT>  any other head_dim: register-staged, plain images.
+// LDS images (KVImage): with head_dim 64, K rows are 128 B, 16-B slots XOR-swizzled with (key>>1)&7 (ds_read_b128
+// conflict-free); V rows are 128 B with the two 64-B halves swapped when key bit 1 is set (the 4-row x 32-col
+// transposed reads of a half-wave then cover all 64 banks).  The generic kernel's images are plain.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
 struct AttnArgs {
-  const _Float16* qkv;  // [B][T][3][H][64]
-  _Float16* out;        // [B][NQ][H*64]
+  const _Float16* qkv;  // [B][T][3][H][HD]
+  _Float16* out;        // [B][NQ][H*HD]
   int t, h;
   int nq;               // query rows computed per (b, head): T, or fewer (CLS-only last layer: 1)
   float scale_log2e;
   float* lse;           // optional [B][H][T]: log2 of the softmax denominator incl. the row maximum (training)
 };
 
+// Where the K and V images of one head keep their data: the fill asks for the place of a 16-B chunk, the tile code
+// for the place it reads.  Both swizzles are XORs, so the same function answers "where does chunk c of this row go"
+// and "which chunk does slot c of this row hold" (LDS-DMA lands linearly and swizzles its source instead).
+template <int HD, bool Swizzled>
+struct KVImage {
+  static_assert(HD % 16 == 0 && HD <= 128 && (!Swizzled || HD == 64), "head_dim");
+  static constexpr int HDP = (HD + 31) / 32 * 32;      // V / output dims padded to whole 32-row MFMA tiles
+  static constexpr int NS = HD / 16, NDT = HDP / 32;   // 16-dim steps of S^T, 32-dim tiles of O^T
+  static constexpr int KPB = HD * 2, VPB = HDP * 2;    // row pitches in bytes
+  // byte offset inside key's K row of 16-B chunk c16; inside key's V row of column col
+  static __device__ __forceinline__ int k_in_row(int key, int c16) {
+    return (Swizzled ? c16 ^ ((key >> 1) & 7) : c16) << 4;
+  }
+  static __device__ __forceinline__ int v_in_row(int key, int col) {
+    return (Swizzled ? col ^ (((key >> 1) & 1) << 5) : col) * 2;
+  }
+  static __device__ __forceinline__ int k_off(int key, int c16) { return key * KPB + k_in_row(key, c16); }
+  static __device__ __forceinline__ int v_off(int key, int col) { return key * VPB + v_in_row(key, col); }
+};
+
+// ---- the query tile: a lane is (r = lane & 31, h = lane >> 5), and (grp = lane >> 4, li = lane & 15) for the
+//      transposed reads.  sc[], sum and oacc[] live in the kernel and the indices come by value: one helper for the
+//      whole tile that derives them from `lane` and declares sc[] itself compiled to 25-50 instructions more per tile.
+
+// S^T = K . Q^T: lane (q = r, half h) holds Q[q][16s + 8h .. +7] in qf[s]
+template <int NKT, class Img>
+__device__ __forceinline__ void attn_scores(const char* ks, const f16x8 (&qf)[Img::NS], int r, int h,
+                                            f32x16 (&sc)[NKT]) {
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
+    const int key = kt * 32 + r;
+#pragma unroll
+    for (int s = 0; s < Img::NS; ++s) {
+      const f16x8 kf = *reinterpret_cast<const f16x8*>(ks + Img::k_off(key, 2 * s + h));
+      sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[kt], 0, 0, 0);
+    }
+  }
+}
+
+// row maximum over the keys < t (registers + one cross-half exchange); only the LAST key tile can hold keys >= T
+// (32 NKT - T < 32), so only it is masked.  Keys past T are staged as the last real key: finite data whose scores
+// become -inf here, so that their probabilities are exactly 0.
+template <int NKT>
+__device__ __forceinline__ float attn_masked_max(f32x16 (&sc)[NKT], int t, int h) {
+  const float ninf = -__builtin_huge_valf();
+  float mx = ninf;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int key = (NKT - 1) * 32 + acc_row(i, h);
+    sc[NKT - 1][i] = key < t ? sc[NKT - 1][i] : ninf;
+  }
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sc[kt][i]);
+  return fmaxf(mx, __shfl_xor(mx, 32));
+}
+
+// P = exp2(S scale log2e - max) and its row sum for one key tile
+__device__ __forceinline__ void attn_exp_tile(f32x16& sc, float scale_log2e, float mxs, float& sum) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[i], scale_log2e, -mxs));
+    sc[i] = p;
+    sum += p;
+  }
+}
+
+// P, its row sum (this lane's half of it) and O^T = V^T . P, software-pipelined over the key tiles: the exponentials
+// of key tile kt + 1 stand between the transposed V reads and the MFMAs of key tile kt IN ONE BASIC BLOCK (the lse
+// store, a branch, stays behind the loop), so the 16 x (fma, v_exp_f32, add) chains issue in the shadow of the matrix
+// pipe.  As one block of 112 v_exp_f32 in front of the PV MFMAs (what hipcc emitted for the plain loop nest) the
+// wave's matrix pipe idled for ~1800 cycles per query tile.
+template <int NKT, class Img>
+__device__ __forceinline__ void attn_exp_pv(const char* vs, f32x16 (&sc)[NKT], float scale_log2e, float mxs, int grp,
+                                            int li, float& sum, f32x16 (&oacc)[Img::NDT]) {
+  constexpr int NDT = Img::NDT;
+#pragma unroll
+  for (int t2 = 0; t2 < NDT; ++t2)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) oacc[t2][i] = 0.f;
+  attn_exp_tile(sc[0], scale_log2e, mxs, sum);
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    f16x8 pf[2], vf[2][NDT];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[s][j] = (_Float16)sc[kt][8 * s + j];
+#pragma unroll
+      for (int hdt = 0; hdt < NDT; ++hdt) {
+        // transposed read: this lane supplies row (kb + li>>2), columns c0 + 4*(li&3) .. +3
+        const int c0 = 32 * hdt + 16 * (grp & 1) + 4 * (li & 3);
+        const int kb = 32 * kt + 16 * s + 4 * (grp >> 1) + (li >> 2);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) tr_read_half(vf[s][hdt], half, vs + Img::v_off(kb + 8 * half, c0));
+      }
+    }
+    if (kt + 1 < NKT) attn_exp_tile(sc[kt + 1], scale_log2e, mxs, sum);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int hdt = 0; hdt < NDT; ++hdt)
+        oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s][hdt], pf[s], oacc[hdt], 0, 0, 0);
+  }
+}
+
+// the lane's four normalised outputs g4 of one O^T tile: query r, dims 8 g4 + 4 h .. + 3 of the tile's 32
+__device__ __forceinline__ f16x4 attn_out4(const f32x16& oacc, int g4, float inv) {
+  f16x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = (_Float16)(oacc[4 * g4 + e] * inv);
+  return o;
+}
+
+// Where the rows of the query tile at q0 go: row q0's place in `out`, the elements between rows, and how many of the
+// tile's 32 rows are to be stored.  Wave-uniform, so that a row's address is one multiply-add away.
+struct AttnOutTile {
+  _Float16* row0;
+  int64_t pitch;
+  int rows;
+};
+template <int HD>
+__device__ __forceinline__ AttnOutTile attn_out_tile(const AttnArgs& a, int64_t b, int head, int q0) {
+  const int64_t pitch = (int64_t)a.h * HD;
+  return AttnOutTile{a.out + (b * a.nq + q0) * pitch + head * HD, pitch, a.nq - q0};
+}
+
+// Row store, head_dim 64: the lane owns query row q0 + r and 4-dim pieces of it; a direct store would write 16 B of
+// 32 different rows per instruction (partial lines).  The wave transposes its 32 x 64 tile through 4 KB of LDS `ot`
+// (16-B chunks XOR-swizzled with row & 7) and stores whole 128-B rows: 8 lanes x 16 B.
+__device__ __forceinline__ void attn_store_rows_lds(const AttnOutTile& o, char* ot, const f32x16 (&oacc)[2], float inv,
+                                                    int lane, int r, int h) {
+#pragma unroll
+  for (int hdt = 0; hdt < 2; ++hdt) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const int chunk = 4 * hdt + g4;  // 16-B chunk = 8 head dims; h picks its 8-B half
+      *reinterpret_cast<f16x4*>(ot + r * 128 + ((chunk ^ (r & 7)) << 4) + 8 * h) = attn_out4(oacc[hdt], g4, inv);
+    }
+  }
+  const int rr = lane >> 3, cc = lane & 7;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row = it * 8 + rr;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(ot + row * 128 + ((cc ^ (row & 7)) << 4));
+    if (row < o.rows) *reinterpret_cast<u32x4*>(o.row0 + row * o.pitch + cc * 8) = v;
+  }
+}
+
+// Row store without the LDS tile: 8 bytes per lane and piece; the dims a padded last O^T tile computed past HD stay
+// unstored
+template <int HD, int NDT>
+__device__ __forceinline__ void attn_store_rows_direct(const AttnOutTile& o, const f32x16 (&oacc)[NDT], float inv,
+                                                       int r, int h) {
+  if (r < o.rows) {
+    _Float16* orow = o.row0 + r * o.pitch;
+#pragma unroll
+    for (int hdt = 0; hdt < NDT; ++hdt) {
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int dim = 32 * hdt + 8 * g4 + 4 * h;
+        if (HD % 32 == 0 || dim < HD) *reinterpret_cast<f16x4*>(orow + dim) = attn_out4(oacc[hdt], g4, inv);
+      }
+    }
+  }
+}
+
+// p = exp2(s * scale_log2e - lse): what hcir_attn_bwd recomputes P from.  `sum` is the whole row's.
+__device__ __forceinline__ void attn_store_lse(const AttnArgs& a, int64_t b, int head, int q0, int r, int h, float mxs,
+                                               float sum) {
+  if (a.lse && h == 0 && q0 + r < a.nq)
+    a.lse[(b * a.h + head) * (int64_t)a.t + q0 + r] = mxs + __builtin_amdgcn_logf(sum);
+}
+
 template <int NKT>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
+  using Img = KVImage<64, true>;
   constexpr int TP = 32 * NKT;
   // K and V images, then a 4 KB output-transposition tile per wave
   constexpr bool kTrans = NKT <= 7;  // with 8-9 key tiles the extra 16 KB would cost the second workgroup per CU
@@ -53,24 +239,21 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 
   // ---- stage K and V by LDS-DMA: every piece of the head in flight at once, no VGPR round trip.
   // The LDS destination of a wave instruction is linear (base + lane*16), so both swizzles are
-  // applied to the per-lane SOURCE chunk.  Keys past T are clamped to the last real key: finite
-  // data whose scores are masked to -inf (K) / whose probabilities are exactly 0 (V).
+  // applied to the per-lane SOURCE chunk (k_in_row / v_in_row are bytes, the pointers fp16).  Keys past T are
+  // clamped to the last real key.
   for (int slot0 = (tid & ~63); slot0 < TP * 8; slot0 += nthreads) {
     const int slot = slot0 + lane;
     const int key = slot >> 3, pc = slot & 7;
     const int src_key = key < a.t ? key : a.t - 1;
-    const int kc = pc ^ ((key >> 1) & 7);
-    const int vc = pc ^ (((key >> 1) & 1) << 2);
     __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(kg + src_key * row_stride + kc * 8),
+        (const __attribute__((address_space(1))) void*)(kg + src_key * row_stride + Img::k_in_row(key, pc) / 2),
         (__attribute__((address_space(3))) void*)(ks + slot0 * 16), 16, 0, 0);
     __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(vg + src_key * row_stride + vc * 8),
+        (const __attribute__((address_space(1))) void*)(vg + src_key * row_stride + Img::v_in_row(key, 8 * pc) / 2),
         (__attribute__((address_space(3))) void*)(vs + slot0 * 16), 16, 0, 0);
   }
-  // Q fragments come straight from global: lane (q = r, half h) holds Q[q][16s + 8h .. +7].
-  // The first tile's fragments are requested together with the K/V DMA, the next tile's at the
-  // top of the current tile, so their latency is never exposed.
+  // Q fragments come straight from global.  The first tile's fragments are requested together with the K/V DMA,
+  // the next tile's at the top of the current tile, so their latency is never exposed.
   auto load_q = [&](int qt, f16x8 (&dst)[4]) {
     int qrow = qt * 32 + r;
     qrow = qrow < a.t ? qrow : a.t - 1;
@@ -83,7 +266,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: see sim_glds_retire_and_sync()
   __syncthreads();
   const int nqt = (a.nq + 31) >> 5;
-  const float ninf = -__builtin_huge_valf();
   const int grp = lane >> 4, li = lane & 15;
 
   for (int qt = wave; qt < nqt; qt += 4) {
@@ -91,136 +273,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
     // out of the loop (that cost 256 VGPRs + scratch spills); they are re-derived from `lane` here
     int opaque = 0;
     asm volatile("" : "+v"(opaque));
-    const char* ksl = ks + opaque;
-    const char* vsl = vs + opaque;
     const int q0 = qt * 32;
     if (qt + 4 < nqt) load_q(qt + 4, qn);
 
-    // ---- S^T = K . Q^T ----
-    f32x16 sc[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
-      const int key = kt * 32 + r;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int c = 2 * s + h;
-        const f16x8 kf =
-            *reinterpret_cast<const f16x8*>(ksl + key * 128 + ((c ^ ((key >> 1) & 7)) << 4));
-        sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[kt], 0, 0, 0);
-      }
-    }
-
-    // ---- softmax over keys (registers + one cross-half exchange); only the LAST key tile can
-    //      hold keys >= T (TP - T < 32), so only it is masked
-    float mx = ninf;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int key = (NKT - 1) * 32 + acc_row(i, h);
-      sc[NKT - 1][i] = key < a.t ? sc[NKT - 1][i] : ninf;
-    }
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sc[kt][i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mxs = mx * a.scale_log2e;
+    f32x16 sc[NKT], oacc[2];
+    attn_scores<NKT, Img>(ks + opaque, qf, r, h, sc);
+    const float mxs = attn_masked_max(sc, a.t, h) * a.scale_log2e;
     float sum = 0.f;
-    // ---- P = exp2(S scale log2e - max), O^T = V^T . P, software-pipelined over the key tiles: the exponentials of
-    //      key tile kt + 1 stand between the transposed V reads and the MFMAs of key tile kt IN ONE BASIC BLOCK (the
-    //      lse store, a branch, moved behind the loop), so the 16 x (fma, v_exp_f32, add) chains issue in the shadow
-    //      of the matrix pipe.  As one block of 112 v_exp_f32 in front of the PV MFMAs (what hipcc emitted for the
-    //      plain loop nest) the wave's matrix pipe idled for ~1800 cycles per query tile.
-#define HCIR_EXP_TILE(KT)                                                                            \
-  _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                                    \
-    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[KT][i], a.scale_log2e, -mxs));           \
-    sc[KT][i] = p;                                                                                    \
-    sum += p;                                                                                         \
-  }
-    f32x16 oacc[2];
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) oacc[t2][i] = 0.f;
-    HCIR_EXP_TILE(0)
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      f16x8 pf[2], vf[2][2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[s][j] = (_Float16)sc[kt][8 * s + j];
-#pragma unroll
-        for (int hdt = 0; hdt < 2; ++hdt) {
-          // transposed read: this lane supplies row (kb + li>>2), columns c0 + 4*(li&3) .. +3
-          const int c0 = 32 * hdt + 16 * (grp & 1) + 4 * (li & 3);
-          const int kb = 32 * kt + 16 * s + 4 * (grp >> 1) + (li >> 2);
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int key = kb + 8 * half;
-            const int col = c0 ^ (((key >> 1) & 1) << 5);
-            tr_read_half(vf[s][hdt], half, vsl + key * 128 + col * 2);
-          }
-        }
-      }
-      if (kt + 1 < NKT) {
-        HCIR_EXP_TILE(kt + 1)
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int hdt = 0; hdt < 2; ++hdt)
-          oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s][hdt], pf[s], oacc[hdt], 0, 0, 0);
-    }
-#undef HCIR_EXP_TILE
+    attn_exp_pv<NKT, Img>(vs + opaque, sc, a.scale_log2e, mxs, grp, li, sum, oacc);
     sum += __shfl_xor(sum, 32);
     const float inv = 1.0f / sum;
-    if (a.lse && h == 0 && q0 + r < a.nq)   // p = exp2(s * scale_log2e - lse): what hcir_attn_bwd recomputes P from
-      a.lse[(b * a.h + head) * (int64_t)a.t + q0 + r] = mxs + __builtin_amdgcn_logf(sum);
-
-    // ---- store: the lane owns query row q0 + r and 4-dim pieces of it; a direct store would write 16 B of 32
-    //      different rows per instruction (partial lines).  The wave transposes its 32 x 64 tile through 4 KB of
-    //      LDS (16-B chunks XOR-swizzled with row & 7) and stores whole 128-B rows: 8 lanes x 16 B.
-    if constexpr (kTrans) {
-      char* ot = lds + 2 * TP * 128 + wave * 4096 + opaque;
-#pragma unroll
-      for (int hdt = 0; hdt < 2; ++hdt) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          f16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)(oacc[hdt][4 * g4 + e] * inv);
-          const int chunk = 4 * hdt + g4;  // 16-B chunk = 8 head dims; h picks its 8-B half
-          *reinterpret_cast<f16x4*>(ot + r * 128 + ((chunk ^ (r & 7)) << 4) + 8 * h) = o;
-        }
-      }
-      const int rr = lane >> 3, cc = lane & 7;
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + rr;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ot + row * 128 + ((cc ^ (row & 7)) << 4));
-        const int q = q0 + row;
-        if (q < a.nq)
-          *reinterpret_cast<u32x4*>(a.out + (b * a.nq + q) * ((int64_t)a.h * 64) + head * 64 + cc * 8) = v;
-      }
-    }
-    if constexpr (!kTrans) {
-      const int q = q0 + r;
-      if (q < a.nq) {
-        _Float16* orow = a.out + (b * a.nq + q) * ((int64_t)a.h * 64) + head * 64;
-#pragma unroll
-        for (int hdt = 0; hdt < 2; ++hdt) {
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            f16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (_Float16)(oacc[hdt][4 * g4 + e] * inv);
-            *reinterpret_cast<f16x4*>(orow + 32 * hdt + 8 * g4 + 4 * h) = o;
-          }
-        }
-      }
-    }
+    attn_store_lse(a, b, head, q0, r, h, mxs, sum);
+    const AttnOutTile o = attn_out_tile<64>(a, b, head, q0);
+    if constexpr (kTrans)
+      attn_store_rows_lds(o, lds + 2 * TP * 128 + wave * 4096 + opaque, oacc, inv, lane, r, h);
+    else
+      attn_store_rows_direct<64>(o, oacc, inv, r, h);
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = qn[s];
   }
@@ -234,11 +302,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
 // its second co-resident workgroup for overlap: with one key tile of compute it takes 197 us per launch at 880 images
 // (all bytes moved), with all seven 286 us - 89 us of compute standing outside the memory time.  (Round 2's persistent
 // attempt gained 2.5 %: its pending transfers were retired by the compiler in front of every transposed V read.)
-// Same S / softmax / PV code, same LDS images, same results as attn_fwd_kernel<7>.
+// The tile arithmetic and the LDS images are those of attn_fwd_kernel<7>, the same code.
 // --------------------------------------------------------------------------
 constexpr int kF2NKT = 7, kF2Rows = 32 * kF2NKT, kF2Img = kF2Rows * 128;
 
 __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, int items) {
+  using Img = KVImage<64, true>;
   constexpr int NKT = kF2NKT;
   __shared__ __attribute__((aligned(16))) char lds[4 * kF2Img + kF2NKT * 4096];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -246,7 +315,6 @@ __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, i
   const int grp = lane >> 4, li = lane & 15;
   const int row_stride = 3 * a.h * 64;   // elements between tokens
   const uint32_t lds0 = lds_addr(lds);
-  const float ninf = -__builtin_huge_valf();
   const int q0 = wave * 32;
   const bool active = q0 < a.nq;                 // this wave's query tile exists
   auto item_base = [&](int item) { return ((int64_t)(item / a.h) * a.t) * row_stride + (item % a.h) * 64; };
@@ -261,8 +329,8 @@ __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, i
       const int key = ii * 8 + (lane >> 3), pc = lane & 7;
       const int src = key < a.t ? key : a.t - 1;   // past T: the last real key (finite; masked / P = 0)
       const uint32_t rowoff = (uint32_t)(src * row_stride * 2);
-      lds_dma16(kg, rowoff + ((pc ^ ((key >> 1) & 7)) << 4), lds0 + buf * 2 * kF2Img + ii * 1024);
-      lds_dma16(vg, rowoff + ((pc ^ (((key >> 1) & 1) << 2)) << 4), lds0 + buf * 2 * kF2Img + kF2Img + ii * 1024);
+      lds_dma16(kg, rowoff + Img::k_in_row(key, pc), lds0 + buf * 2 * kF2Img + ii * 1024);
+      lds_dma16(vg, rowoff + Img::v_in_row(key, 8 * pc), lds0 + buf * 2 * kF2Img + kF2Img + ii * 1024);
     }
   };
   f16x8 qf[4], qn[4];
@@ -297,104 +365,17 @@ __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, i
       int opaque = 0;
       asm volatile("" : "+v"(opaque));
       const char* ksl = lds + buf * 2 * kF2Img + opaque;
-      const char* vsl = ksl + kF2Img;
       const int head = item % a.h;
       const int64_t b = item / a.h;
-      // ---- S^T = K . Q^T ----
-      f32x16 sc[NKT];
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
-        const int key = kt * 32 + r;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int c = 2 * s + h;
-          const f16x8 kf = *reinterpret_cast<const f16x8*>(ksl + key * 128 + ((c ^ ((key >> 1) & 7)) << 4));
-          sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[kt], 0, 0, 0);
-        }
-      }
-      // ---- softmax over keys; only the last key tile can hold keys >= T
-      float mx = ninf;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int key = (NKT - 1) * 32 + acc_row(i, h);
-        sc[NKT - 1][i] = key < a.t ? sc[NKT - 1][i] : ninf;
-      }
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sc[kt][i]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mxs = mx * a.scale_log2e;
+      f32x16 sc[NKT], oacc[2];
+      attn_scores<NKT, Img>(ksl, qf, r, h, sc);
+      const float mxs = attn_masked_max(sc, a.t, h) * a.scale_log2e;
       float sum = 0.f;
-#define HCIR_EXP_TILE2(KT)                                                                           \
-  _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                                    \
-    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[KT][i], a.scale_log2e, -mxs));           \
-    sc[KT][i] = p;                                                                                    \
-    sum += p;                                                                                         \
-  }
-      f32x16 oacc[2];
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) oacc[t2][i] = 0.f;
-      HCIR_EXP_TILE2(0)
-#pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        f16x8 pf[2], vf[2][2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) pf[s][j] = (_Float16)sc[kt][8 * s + j];
-#pragma unroll
-          for (int hdt = 0; hdt < 2; ++hdt) {
-            const int c0 = 32 * hdt + 16 * (grp & 1) + 4 * (li & 3);
-            const int kb = 32 * kt + 16 * s + 4 * (grp >> 1) + (li >> 2);
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-              const int key = kb + 8 * half;
-              const int col = c0 ^ (((key >> 1) & 1) << 5);
-              tr_read_half(vf[s][hdt], half, vsl + key * 128 + col * 2);
-            }
-          }
-        }
-        if (kt + 1 < NKT) {
-          HCIR_EXP_TILE2(kt + 1)
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int hdt = 0; hdt < 2; ++hdt)
-            oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s][hdt], pf[s], oacc[hdt], 0, 0, 0);
-      }
-#undef HCIR_EXP_TILE2
+      attn_exp_pv<NKT, Img>(ksl + kF2Img, sc, a.scale_log2e, mxs, grp, li, sum, oacc);
       sum += __shfl_xor(sum, 32);
-      const float inv = 1.0f / sum;
-      // ---- whole 128-B rows through the wave's 4 KB transposition tile, then the lse
-      char* ot = lds + 4 * kF2Img + wave * 4096 + opaque;
-#pragma unroll
-      for (int hdt = 0; hdt < 2; ++hdt) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          f16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (_Float16)(oacc[hdt][4 * g4 + e] * inv);
-          const int chunk = 4 * hdt + g4;
-          *reinterpret_cast<f16x4*>(ot + r * 128 + ((chunk ^ (r & 7)) << 4) + 8 * h) = o;
-        }
-      }
-      const int rr = lane >> 3, cc = lane & 7;
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + rr;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ot + row * 128 + ((cc ^ (row & 7)) << 4));
-        const int q = q0 + row;
-        if (q < a.nq)
-          *reinterpret_cast<u32x4*>(a.out + (b * a.nq + q) * ((int64_t)a.h * 64) + head * 64 + cc * 8) = v;
-      }
-      if (a.lse && h == 0 && q0 + r < a.nq)
-        a.lse[(b * a.h + head) * (int64_t)a.t + q0 + r] = mxs + __builtin_amdgcn_logf(sum);
+      attn_store_rows_lds(attn_out_tile<64>(a, b, head, q0), lds + 4 * kF2Img + wave * 4096 + opaque, oacc,
+                          1.0f / sum, lane, r, h);
+      attn_store_lse(a, b, head, q0, r, h, mxs, sum);
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = qn[s];
@@ -405,21 +386,18 @@ __global__ __launch_bounds__(64 * kF2NKT, 1) void attn_fwd2_kernel(AttnArgs a, i
 
 // --------------------------------------------------------------------------
 // Any head_dim that is a multiple of 16 up to 128 (vit_huge_patch14: 1280 / 16 = 80, HP/src/models_vit.py:266-270).
-// Same algorithm and MFMA operand maps as attn_fwd_kernel; correctness-first staging: K and V go through registers
-// into plain (unswizzled) LDS images, K rows HD * 2 bytes, V rows padded with zeros to a multiple of 32 dims so that
-// the O^T = V^T . P tiles of 32 dims need no edge case (the padded output rows are computed and not stored).
+// The same tile code as attn_fwd_kernel; correctness-first staging: K and V go through registers into plain
+// (unswizzled) LDS images, K rows HD * 2 bytes, V rows padded with zeros to a multiple of 32 dims so that the
+// O^T = V^T . P tiles of 32 dims need no edge case (the padded output rows are computed and not stored).
 // The tuned head_dim-64 kernel above is what every BASELINE config runs.
 // --------------------------------------------------------------------------
 template <int HD, int NKT>
 __global__ __launch_bounds__(256, 1) void attn_fwd_generic_kernel(AttnArgs a) {
-  constexpr int TP = 32 * NKT;
-  constexpr int HDP = (HD + 31) / 32 * 32;     // V / output dims padded to whole 32-row MFMA tiles
-  constexpr int KPB = HD * 2, VPB = HDP * 2;   // row pitches in bytes
-  constexpr int NS = HD / 16, NDT = HDP / 32;
-  static_assert(HD % 16 == 0 && HD <= 128, "head_dim");
-  __shared__ __attribute__((aligned(16))) char lds[TP * (KPB + VPB)];
+  using Img = KVImage<HD, false>;
+  constexpr int TP = 32 * NKT, HDP = Img::HDP, NS = Img::NS, NDT = Img::NDT;
+  __shared__ __attribute__((aligned(16))) char lds[TP * (Img::KPB + Img::VPB)];
   char* ks = lds;
-  char* vs = lds + TP * KPB;
+  char* vs = lds + TP * Img::KPB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int head = blockIdx.x % a.h;
@@ -436,13 +414,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_generic_kernel(AttnArgs a) {
     if (c * 8 < HD) {
       kv = *reinterpret_cast<const u32x4*>(kg + src_key * row_stride + c * 8);
       vv = *reinterpret_cast<const u32x4*>(vg + src_key * row_stride + c * 8);
-      *reinterpret_cast<u32x4*>(ks + key * KPB + c * 16) = kv;
+      *reinterpret_cast<u32x4*>(ks + Img::k_off(key, c)) = kv;
     }
-    *reinterpret_cast<u32x4*>(vs + key * VPB + c * 16) = vv;
+    *reinterpret_cast<u32x4*>(vs + Img::v_off(key, 8 * c)) = vv;
   }
   __syncthreads();
   const int nqt = (a.nq + 31) >> 5;
-  const float ninf = -__builtin_huge_valf();
   const int grp = lane >> 4, li = lane & 15;
   for (int qt = wave; qt < nqt; qt += 4) {
     const int q0 = qt * 32;
@@ -451,104 +428,32 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_generic_kernel(AttnArgs a) {
     f16x8 qf[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) qf[s] = *reinterpret_cast<const f16x8*>(qg + qrow * row_stride + 16 * s + 8 * h);
-    f32x16 sc[NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
-      const int key = kt * 32 + r;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const f16x8 kf = *reinterpret_cast<const f16x8*>(ks + key * KPB + (2 * s + h) * 16);
-        sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], sc[kt], 0, 0, 0);
-      }
-    }
-    float mx = ninf;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int key = (NKT - 1) * 32 + acc_row(i, h);
-      sc[NKT - 1][i] = key < a.t ? sc[NKT - 1][i] : ninf;
-    }
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sc[kt][i]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mxs = mx * a.scale_log2e;
+    f32x16 sc[NKT], oacc[NDT];
+    attn_scores<NKT, Img>(ks, qf, r, h, sc);
+    const float mxs = attn_masked_max(sc, a.t, h) * a.scale_log2e;
     float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kt][i], a.scale_log2e, -mxs));
-        sc[kt][i] = p;
-        sum += p;
-      }
-    }
+    attn_exp_pv<NKT, Img>(vs, sc, a.scale_log2e, mxs, grp, li, sum, oacc);
     sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-    f32x16 oacc[NDT];
-#pragma unroll
-    for (int t2 = 0; t2 < NDT; ++t2)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) oacc[t2][i] = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        f16x8 pf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pf[j] = (_Float16)sc[kt][8 * s + j];
-#pragma unroll
-        for (int hdt = 0; hdt < NDT; ++hdt) {
-          const int c0 = 32 * hdt + 16 * (grp & 1) + 4 * (li & 3);
-          const int kb = 32 * kt + 16 * s + 4 * (grp >> 1) + (li >> 2);
-          f16x8 vf;
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int key = kb + 8 * half;
-            tr_read_half(vf, half, vs + key * VPB + c0 * 2);
-          }
-          oacc[hdt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[hdt], 0, 0, 0);
-        }
-      }
-    }
-    const int q = q0 + r;
-    if (q < a.nq) {
-      _Float16* orow = a.out + (b * a.nq + q) * ((int64_t)a.h * HD) + head * HD;
-#pragma unroll
-      for (int hdt = 0; hdt < NDT; ++hdt) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int dim = 32 * hdt + 8 * g4 + 4 * h;
-          if (dim < HD) {
-            f16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (_Float16)(oacc[hdt][4 * g4 + e] * inv);
-            *reinterpret_cast<f16x4*>(orow + dim) = o;
-          }
-        }
-      }
-    }
+    attn_store_rows_direct<HD>(attn_out_tile<HD>(a, b, head, q0), oacc, 1.0f / sum, r, h);
+  }
+}
+
+// f(std::integral_constant<int, N>) for the kernel instantiation that covers nkt key tiles, N = 1..9 (T <= 288)
+template <int N = 1, class F>
+static void attn_with_key_tiles(int nkt, F&& f) {
+  if constexpr (N == 9) {
+    f(std::integral_constant<int, 9>{});
+  } else {
+    if (nkt == N) f(std::integral_constant<int, N>{});
+    else attn_with_key_tiles<N + 1>(nkt, f);
   }
 }
 
 template <int HD>
-static int attn_generic_launch(const AttnArgs& a, int nqt, dim3 grid, hipStream_t st) {
-#define LAUNCHG(N) hipLaunchKernelGGL((attn_fwd_generic_kernel<HD, N>), grid, dim3(256), 0, st, a)
-  switch (nqt) {
-    case 1: LAUNCHG(1); break;
-    case 2: LAUNCHG(2); break;
-    case 3: LAUNCHG(3); break;
-    case 4: LAUNCHG(4); break;
-    case 5: LAUNCHG(5); break;
-    case 6: LAUNCHG(6); break;
-    case 7: LAUNCHG(7); break;
-    case 8: LAUNCHG(8); break;
-    default: LAUNCHG(9); break;
-  }
-#undef LAUNCHG
-  return 0;
+static void attn_generic_launch(const AttnArgs& a, int nkt, dim3 grid, hipStream_t st) {
+  attn_with_key_tiles(nkt, [&](auto n) {
+    hipLaunchKernelGGL((attn_fwd_generic_kernel<HD, decltype(n)::value>), grid, dim3(256), 0, st, a);
+  });
 }
 
 }  // namespace
@@ -563,37 +468,27 @@ static int attn_fwd_launch(const void* qkv, int64_t b, int32_t t, int32_t h, int
   AttnArgs a{static_cast<const _Float16*>(qkv), static_cast<_Float16*>(out), t, h, nq,
              scale * 1.44269504088896340736f, lse};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nqt = (t + 31) / 32;
+  const int nkt = (t + 31) / 32;   // the kernels are built for a number of key tiles
   const dim3 grid((unsigned)(b * h));
   if (hd != 64) {   // generic (unswizzled, register-staged) kernel
-    if (hd == 32) attn_generic_launch<32>(a, nqt, grid, st);
-    else if (hd == 48) attn_generic_launch<48>(a, nqt, grid, st);
-    else if (hd == 80) attn_generic_launch<80>(a, nqt, grid, st);
-    else if (hd == 96) attn_generic_launch<96>(a, nqt, grid, st);
-    else attn_generic_launch<128>(a, nqt, grid, st);
+    if (hd == 32) attn_generic_launch<32>(a, nkt, grid, st);
+    else if (hd == 48) attn_generic_launch<48>(a, nkt, grid, st);
+    else if (hd == 80) attn_generic_launch<80>(a, nkt, grid, st);
+    else if (hd == 96) attn_generic_launch<96>(a, nkt, grid, st);
+    else attn_generic_launch<128>(a, nkt, grid, st);
     HCIR_LAUNCH_CHECK();
     return HCIR_OK;
   }
-  if (nqt == kF2NKT && nq == t && b * h >= 512) {
+  if (nkt == kF2NKT && nq == t && b * h >= 512) {
     const int items = (int)(b * h);
     hipLaunchKernelGGL(attn_fwd2_kernel, dim3(256), dim3(64 * kF2NKT), 0, st, a, items);
     HCIR_LAUNCH_CHECK();
     return HCIR_OK;
   }
-#define LAUNCH(N) hipLaunchKernelGGL(attn_fwd_kernel<N>, grid, dim3(256), 0, st, a)
-  // the kernel is built for NKT key tiles; 4 waves walk the query tiles
-  switch (nqt) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    case 4: LAUNCH(4); break;
-    case 5: LAUNCH(5); break;
-    case 6: LAUNCH(6); break;
-    case 7: LAUNCH(7); break;
-    case 8: LAUNCH(8); break;
-    default: LAUNCH(9); break;
-  }
-#undef LAUNCH
+  // 4 waves walk the query tiles
+  attn_with_key_tiles(nkt, [&](auto n) {
+    hipLaunchKernelGGL(attn_fwd_kernel<decltype(n)::value>, grid, dim3(256), 0, st, a);
+  });
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

@@ -202,7 +202,9 @@ def test_fwd_lse(L, t):
 def test_fwd_persistent(L, t, b):
     """b * h >= 512 at seven key tiles: the persistent double-buffered kernel.  Every image carries the marker, so the
     images a workgroup reaches as its second and third item (items >= 256: images 16 and up) do too.  Bit-equal to the
-    same images in calls of fewer than 512 items."""
+    same images in calls of fewer than 512 items (attn_fwd_kernel<7>): the two kernels share the code of the query
+    tile, so this checks what they do not share - the double-buffered staging, the item walk, the barrier and the
+    waits."""
     h = 16
     for fam in ("flat", "marker_last"):
         qd = oa.make_qkv(fam, b, t, h, 64).cuda()
