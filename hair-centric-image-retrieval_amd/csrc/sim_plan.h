@@ -65,8 +65,9 @@ inline int sim_grid_x(int64_t tiles, int64_t qblocks, int max_wg) {
 }
 
 // ----- candidate buffers ----------------------------------------------------
-// candidates per query the big-tile scan can hold: one-element lists of the final merge (16 per lane), next
-// to the prefix list
+// candidates per query the big-tile scan can hold: one-element lists of the final merge (with the prefix list 961
+// lists, the four-wave kernel at four lists per lane), or the 16 slots per lane of the one-wave select, the last
+// of which takes the prefix list
 constexpr int kCandLPL = 16;
 constexpr int kCandCap = 64 * kCandLPL - 64;  // 960
 // candidate-append scans of <= 128 queries with 16 < k <= 64: the floor is the minimum of ceil(k/16) group floors
@@ -76,6 +77,33 @@ constexpr int kCandCapBig = 64 * kSelLPLBig - 64;  // 3008
 constexpr int kSelLPLSmall = 8;
 constexpr int kCandCapSmall = 64 * kSelLPLSmall - 64;  // 448: long prefix, k <= 16 (one buffer size for scan AND select)
 constexpr int kMaxFloorGroups = 4;
+
+// ----- merge routing ----------------------------------------------------------
+// Which kernel of topk_merge.h merges `total_lists` sorted lists per query (the optional extra list counted) into
+// `kout` ranks, and how many lists that launch can hold: a launch with fewer slots than lists would silently drop
+// lists and return wrong neighbours, so every launcher checks capacity >= total_lists.
+enum SimMergeKind {
+  SIM_MERGE_NONE = 0,    // no kernel serves the request (capacity 0)
+  SIM_MERGE_FOUR_WAVES,  // topk_merge32q_kernel<lpl>: kout <= 16, lane slot j of wave w = list w + 4 (lane + 64 j)
+  SIM_MERGE_WAVE,        // topk_merge32_kernel<kMergeLPL>: one wave per query, lane slot j = list lane + 64 j
+  SIM_MERGE_SELECT       // topk_merge_sel_kernel<kMergeLPL>: ngroups > 1 interleaved groups of 16-entry lists, kout <= 16
+};
+constexpr int kMergeLPL = 9;       // lists per lane of the one-wave kernels -> 576 lists (per group)
+constexpr int kMergeQuadMaxLPL = 4;  // ... of the four-wave kernel -> up to 1024 lists
+struct SimMergeRoute {
+  int kind;      // SimMergeKind
+  int lpl;       // the kernel's template argument
+  int capacity;  // lists the launch reads (all groups together)
+};
+inline SimMergeRoute sim_merge_route(int total_lists, int kout, int ngroups) {
+  if (ngroups > 1)
+    return kout <= 16 ? SimMergeRoute{SIM_MERGE_SELECT, kMergeLPL, 64 * kMergeLPL * ngroups} : SimMergeRoute{SIM_MERGE_NONE, 0, 0};
+  if (kout <= 16 && total_lists <= 256 * kMergeQuadMaxLPL) {
+    const int lpl = total_lists <= 256 ? 1 : (int)sim_cdiv(total_lists, 256);
+    return SimMergeRoute{SIM_MERGE_FOUR_WAVES, lpl, 256 * lpl};
+  }
+  return SimMergeRoute{SIM_MERGE_WAVE, kMergeLPL, 64 * kMergeLPL};
+}
 
 // ----- the plan ---------------------------------------------------------------
 enum SimFlow {

@@ -10,8 +10,8 @@
 //            of <=128 queries; each lane owns one query column and keeps a sorted
 //            top-KP list in registers; lists of a workgroup are merged through LDS
 //            and written as one partial list per (workgroup, query).
-//   merge  : one wave per query merges the partial lists (k rounds of wave arg-max
-//            over per-lane cached list heads).
+//   merge  : one or four waves per query merge the partial lists (k rounds of wave
+//            arg-max over per-lane cached list heads): topk_merge.h.
 //   prefix : for big galleries the first S rows are scanned and merged first; the
 //            k-th score of that prefix is a per-query floor for the main scan, so
 //            that register-list insertions become rare there (a gallery row with
@@ -25,6 +25,7 @@
 //            list-keeping scan as fallback if a buffer overflows.
 #include "sim_core.h"
 #include "sim_plan.h"
+#include "topk_merge.h"
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -47,8 +48,6 @@ __device__ unsigned long long g_stamps[1024 * 8];
 #endif
 
 namespace {
-
-constexpr float kNegInf = -__builtin_huge_valf();
 
 // Sorted (score desc, arrival order) register list.  Callers feed increasing row
 // indices, so equal scores keep the smaller index first.  Precondition: s > v[KP-1].
@@ -76,21 +75,6 @@ __device__ __forceinline__ float topk_kth(const float (&v)[KP], int k) {
   }
   return t;
 }
-
-// (score, row) as ONE 64-bit key: [orderable(score) : ~row]; "better" (score desc, row asc) is the unsigned
-// maximum, an empty slot is key 0.  Used by the in-workgroup and the final merges.
-__device__ __forceinline__ uint64_t merge_key(float v, int id) {
-  if (id < 0) return 0ull;
-  uint32_t u = __builtin_bit_cast(uint32_t, v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)id);
-}
-__device__ __forceinline__ float merge_key_val(uint64_t k) {
-  uint32_t u = (uint32_t)(k >> 32);
-  u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-  return __builtin_bit_cast(float, u);
-}
-__device__ __forceinline__ int merge_key_idx(uint64_t k) { return (int)(0xFFFFFFFFu - (uint32_t)k); }
 
 // Batch insertion (scan epilogue): when many of a lane's 16 scores of one 32 x 32 MFMA tile are candidates - every
 // one of them while the lists fill from a workgroup's first tile - the slot-by-slot insertion costs ~115 VALU
@@ -720,699 +704,6 @@ __global__ __launch_bounds__(512, 2) void sim_scan_big_kernel(BigScanArgs a) {
   }
 }
 
-// --------------------------------------------------------------------------
-// merge: one wave per query; lists [nlists][nq][kin] sorted (desc, idx asc),
-// empty slots have idx < 0.  Lane l owns lists l, l+64, ... (<= LPL of them) and
-// caches each list's head; k_out rounds of wave arg-max.
-// --------------------------------------------------------------------------
-constexpr int kMergeLPL = 9;  // lists per lane -> 576 lists per pass
-
-template <typename IdxT>
-struct MergeArgs {
-  const float* vals;
-  const IdxT* idx;
-  float* out_val;
-  int64_t* out_idx;      // final output (idx_base added), or
-  int* out_idx32;        // intermediate output
-  float* kth_val;        // optional [nq]: value of rank k_out-1 (floor for the main scan)
-  int* kth_idx;          // optional [nq]
-  int64_t nq, idx_base;
-  int nlists, kin, kout;
-  // optional extra list per query (the prefix result), [nq][kin_extra]
-  const float* extra_val;
-  const int* extra_idx;
-  int kin_extra;
-  const int* nlists_q;   // optional [nq]: lists of this query = min(nlists_q[q], nlists) (candidate buffers)
-  const int* gate;       // optional device flag: run only if (*gate != 0) == (gate_want != 0)
-  int gate_want;
-  int* zero_cnt;         // optional [nq + 1]: cleared here (candidate counters + overflow flag of the big scan)
-  int ngroups;           // > 1: blockIdx.y = group g merges lists g, g + ngroups, ... into out[g][nq][kout],
-                         //      kth_val[g][nq] (group floors of the prefix); 0 / 1: one group
-};
-
-template <typename IdxT, int LPL = kMergeLPL>
-__global__ __launch_bounds__(256) void topk_merge_kernel(MergeArgs<IdxT> a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (qi >= a.nq) return;
-  if (a.gate && ((*a.gate != 0) != (a.gate_want != 0))) return;
-  if (a.zero_cnt && lane == 0) {
-    a.zero_cnt[qi] = 0;
-    if (qi == 0) a.zero_cnt[a.nq] = 0;
-  }
-  const bool has_extra = a.extra_val != nullptr;
-  int nl = a.nlists;
-  if (a.nlists_q) nl = a.nlists_q[qi] < nl ? a.nlists_q[qi] : nl;
-  const int total = a.nlists + (has_extra ? 1 : 0);
-
-  float cv[LPL];
-  int64_t ci[LPL];
-  int hd[LPL];
-  auto fetch = [&](int list, int pos, float& v, int64_t& id) {
-    v = kNegInf;
-    id = -1;
-    if (list < a.nlists) {
-      if (pos < a.kin && list < nl) {
-        const int64_t o = ((int64_t)list * a.nq + qi) * a.kin + pos;
-        v = a.vals[o];
-        id = (int64_t)a.idx[o];
-      }
-    } else if (list < total) {
-      if (pos < a.kin_extra) {
-        v = a.extra_val[qi * a.kin_extra + pos];
-        id = a.extra_idx[qi * a.kin_extra + pos];
-      }
-    }
-    if (id < 0) v = kNegInf;
-  };
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) {
-    hd[j] = 0;
-    fetch(lane + 64 * j, 0, cv[j], ci[j]);
-  }
-  float keep_v = kNegInf;
-  int64_t keep_i = -1;
-  for (int o = 0; o < a.kout; ++o) {
-    float bv = cv[0];
-    int64_t bi = ci[0];
-    int bj = 0;
-#pragma unroll
-    for (int j = 1; j < LPL; ++j) {
-      const bool take = (ci[j] >= 0) && (bi < 0 || better(cv[j], ci[j], bv, bi));
-      bv = take ? cv[j] : bv;
-      bi = take ? ci[j] : bi;
-      bj = take ? j : bj;
-    }
-    // wave arg-max under (score desc, idx asc); empty = idx < 0
-    float wv = bv;
-    int64_t wi = bi;
-    int wl = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(wv, off);
-      const int64_t oi = __shfl_xor(wi, off);
-      const int ol = __shfl_xor(wl, off);
-      const bool take = (oi >= 0) && (wi < 0 || better(ov, oi, wv, wi));
-      wv = take ? ov : wv;
-      wi = take ? oi : wi;
-      wl = take ? ol : wl;
-    }
-    // winner o kept by lane o & 63, stored once per 64 rounds (see topk_merge32_kernel: no store inside the loop)
-    if (lane == (o & 63)) {
-      keep_v = wv;
-      keep_i = wi;
-    }
-    if ((o & 63) == 63 || o == a.kout - 1) {
-      const int oo = (o & ~63) + lane;
-      if (oo <= o) {
-        a.out_val[qi * a.kout + oo] = keep_i < 0 ? kNegInf : keep_v;
-        if (a.out_idx) a.out_idx[qi * a.kout + oo] = keep_i < 0 ? -1 : keep_i + a.idx_base;
-        if (a.out_idx32) a.out_idx32[qi * a.kout + oo] = (int)keep_i;
-        if (oo == a.kout - 1) {
-          if (a.kth_val) a.kth_val[qi] = keep_i < 0 ? kNegInf : keep_v;
-          if (a.kth_idx) a.kth_idx[qi] = (int)keep_i;
-        }
-      }
-    }
-    if (lane == wl && wi >= 0) {
-#pragma unroll
-      for (int j = 0; j < LPL; ++j) {
-        if (j == bj) {
-          hd[j] += 1;
-          fetch(lane + 64 * j, hd[j], cv[j], ci[j]);
-        }
-      }
-    }
-  }
-}
-
-// --------------------------------------------------------------------------
-// merge32: the same merge for 32-bit row indices (every intra-GPU merge), latency-tuned.
-//   * a (score, row) pair is ONE 64-bit key: [orderable(score) : ~row]; "better" (score desc, row asc) is the
-//     unsigned maximum, empty slots are key 0;
-//   * the first FOUR entries of each list are fetched up front as two 16-B loads: the k rounds then run from
-//     registers (the old kernel re-fetched the winner's next entry from memory in every round, ~1.5 us each);
-//     a list whose four are used up is refilled in place (rare);
-//   * the wave arg-max is 4 DPP butterfly steps inside each row of 16 lanes + 4 v_readlane + scalar max,
-//     instead of 18 ds_bpermute per round.
-// --------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp_max_u64(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, true);
-  const uint64_t o = ((uint64_t)hi << 32) | lo;
-  return o > v ? o : v;
-}
-// maximum over the 64 lanes, returned wave-uniform
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  v = dpp_max_u64<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = dpp_max_u64<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = dpp_max_u64<0x141>(v);  // row_half_mirror
-  v = dpp_max_u64<0x140>(v);  // row_mirror: every lane of a 16-lane row now holds the row maximum
-  uint64_t m = 0;
-#pragma unroll
-  for (int row = 0; row < 4; ++row) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 16 * row);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 16 * row);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    m = o > m ? o : m;
-  }
-  return m;
-}
-
-template <int LPL>
-__global__ __launch_bounds__(256) void topk_merge32_kernel(MergeArgs<int> a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (qi >= a.nq) return;
-  if (a.gate && ((*a.gate != 0) != (a.gate_want != 0))) return;
-  const int ng_ = a.ngroups > 1 ? a.ngroups : 1, grp = (int)blockIdx.y;
-  if (a.zero_cnt && lane == 0 && grp == 0) {
-    a.zero_cnt[qi] = 0;
-    if (qi == 0) a.zero_cnt[a.nq] = 0;
-  }
-  const bool has_extra = a.extra_val != nullptr;
-  int nl = (a.nlists - grp + ng_ - 1) / ng_;   // lists of this group
-  if (a.nlists_q) nl = a.nlists_q[qi] < nl ? a.nlists_q[qi] : nl;
-  const int extra_list = nl;  // list index of the optional extra list
-  const int64_t gout = (int64_t)grp * a.nq;   // output row offset of the group
-
-  // entries [pos, pos + 4) of a list as keys (0 where the list has ended)
-  auto fetch4 = [&](int list, int pos, uint64_t (&k4)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) k4[e] = 0ull;
-    const float* pv = nullptr;
-    const int* pi = nullptr;
-    int len = 0;
-    if (list < nl) {
-      pv = a.vals + ((int64_t)(list * ng_ + grp) * a.nq + qi) * a.kin;
-      pi = a.idx + ((int64_t)(list * ng_ + grp) * a.nq + qi) * a.kin;
-      len = a.kin;
-    } else if (has_extra && list == extra_list) {
-      pv = a.extra_val + qi * a.kin_extra;
-      pi = a.extra_idx + qi * a.kin_extra;
-      len = a.kin_extra;
-    }
-    if (pos + 4 <= len && (len & 3) == 0) {  // whole 16-B groups (lists of 16 / 32 / 64 entries)
-      const f32x4 v = *reinterpret_cast<const f32x4*>(pv + pos);
-      const u32x4 id = *reinterpret_cast<const u32x4*>(pi + pos);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) k4[e] = merge_key(v[e], (int)id[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (pos + e < len) k4[e] = merge_key(pv[pos + e], pi[pos + e]);
-    }
-  };
-
-  uint64_t kq[LPL][4];
-  int used[LPL];
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) {
-    used[j] = 0;
-    fetch4(lane + 64 * j, 0, kq[j]);
-  }
-  // Winner o is KEPT by lane o and the whole result leaves after the loop, 64 outputs per store instruction.
-  // (With lane 0 storing inside the loop hipcc put `s_waitcnt vmcnt(0)` in front of every round - the refill
-  // load below shares the counter - so each of the k rounds waited for a store round trip: ~1.1 us per round,
-  // 18-23 us per merge of 16 ranks and 55 us per merge of 50; k <= 64 per pass, so one register holds it.)
-  uint64_t mine = 0ull;
-  for (int o = 0; o < a.kout; ++o) {
-    uint64_t best = kq[0][0];
-    int bj = 0;
-#pragma unroll
-    for (int j = 1; j < LPL; ++j) {
-      const bool take = kq[j][0] > best;
-      best = take ? kq[j][0] : best;
-      bj = take ? j : bj;
-    }
-    const uint64_t wm = wave_max_u64(best);
-    mine = (lane == (o & 63)) ? wm : mine;
-    if ((o & 63) == 63 || o == a.kout - 1) {   // a full wave of results (kout > 64 only from hcir_topk_merge callers)
-      const int oo = (o & ~63) + lane;
-      if (oo <= o) {
-        const bool none = mine == 0ull;
-        const float wv = none ? kNegInf : merge_key_val(mine);
-        const int wi = none ? -1 : merge_key_idx(mine);
-        a.out_val[(gout + qi) * a.kout + oo] = wv;
-        if (a.out_idx) a.out_idx[(gout + qi) * a.kout + oo] = none ? -1 : (int64_t)wi + a.idx_base;
-        if (a.out_idx32) a.out_idx32[(gout + qi) * a.kout + oo] = wi;
-        if (oo == a.kout - 1) {
-          if (a.kth_val) a.kth_val[gout + qi] = wv;
-          if (a.kth_idx) a.kth_idx[gout + qi] = wi;
-        }
-      }
-    }
-    if (wm != 0ull && best == wm) {  // row indices are unique: exactly one lane and one list hold the winner
-#pragma unroll
-      for (int j = 0; j < LPL; ++j) {
-        if (j == bj) {
-          kq[j][0] = kq[j][1];
-          kq[j][1] = kq[j][2];
-          kq[j][2] = kq[j][3];
-          kq[j][3] = 0ull;
-          used[j] += 1;
-          if ((used[j] & 3) == 0) fetch4(lane + 64 * j, used[j], kq[j]);  // its four are used up: refill
-        }
-      }
-    }
-  }
-}
-
-// --------------------------------------------------------------------------
-// merge32q: merge32 with FOUR waves per query (kout <= 16).  The one-wave merge is a serial chain: every one of
-// the k rounds walks all LPL cached list heads of a lane (9 - 13 compare-select steps) before the wave maximum -
-// 17 - 26 us per launch for 512 - 768 lists, whatever the number of queries (<= 128 of them keep 16 - 32 CUs busy).
-// Here wave w of the workgroup takes lists w, w + 4, ... (a quarter of the heads per lane), the four 16-entry
-// results meet in LDS as 64 keys, and wave 0 ranks them by counting (lane i compares its key with the other 63):
-// rank r < kout stores output r.  Keys are all distinct (row indices are unique), so ranks are a permutation.
-// --------------------------------------------------------------------------
-template <int LPL>
-__global__ __launch_bounds__(256) void topk_merge32q_kernel(MergeArgs<int> a) {
-  __shared__ uint64_t part[4][16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t qi = blockIdx.x;
-  if (a.gate && ((*a.gate != 0) != (a.gate_want != 0))) return;
-  if (a.zero_cnt && threadIdx.x == 0) {
-    a.zero_cnt[qi] = 0;
-    if (qi == 0) a.zero_cnt[a.nq] = 0;
-  }
-  const bool has_extra = a.extra_val != nullptr;
-  int nl = a.nlists;
-  if (a.nlists_q) nl = a.nlists_q[qi] < nl ? a.nlists_q[qi] : nl;
-  const int extra_list = nl;
-
-  auto fetch4 = [&](int list, int pos, uint64_t (&k4)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) k4[e] = 0ull;
-    const float* pv = nullptr;
-    const int* pi = nullptr;
-    int len = 0;
-    if (list < nl) {
-      pv = a.vals + ((int64_t)list * a.nq + qi) * a.kin;
-      pi = a.idx + ((int64_t)list * a.nq + qi) * a.kin;
-      len = a.kin;
-    } else if (has_extra && list == extra_list) {
-      pv = a.extra_val + qi * a.kin_extra;
-      pi = a.extra_idx + qi * a.kin_extra;
-      len = a.kin_extra;
-    }
-    if (pos + 4 <= len && (len & 3) == 0) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(pv + pos);
-      const u32x4 id = *reinterpret_cast<const u32x4*>(pi + pos);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) k4[e] = merge_key(v[e], (int)id[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (pos + e < len) k4[e] = merge_key(pv[pos + e], pi[pos + e]);
-    }
-  };
-  // list of (wave, lane, j): wave + 4 (lane + 64 j)
-  uint64_t kq[LPL][4];
-  int used[LPL];
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) {
-    used[j] = 0;
-    fetch4(wave + 4 * (lane + 64 * j), 0, kq[j]);
-  }
-  uint64_t mine = 0ull;
-  for (int o = 0; o < a.kout; ++o) {
-    uint64_t best = kq[0][0];
-    int bj = 0;
-#pragma unroll
-    for (int j = 1; j < LPL; ++j) {
-      const bool take = kq[j][0] > best;
-      best = take ? kq[j][0] : best;
-      bj = take ? j : bj;
-    }
-    const uint64_t wm = wave_max_u64(best);
-    mine = (lane == o) ? wm : mine;
-    if (wm != 0ull && best == wm) {
-#pragma unroll
-      for (int j = 0; j < LPL; ++j) {
-        if (j == bj) {
-          kq[j][0] = kq[j][1];
-          kq[j][1] = kq[j][2];
-          kq[j][2] = kq[j][3];
-          kq[j][3] = 0ull;
-          used[j] += 1;
-          if ((used[j] & 3) == 0) fetch4(wave + 4 * (lane + 64 * j), used[j], kq[j]);
-        }
-      }
-    }
-  }
-  if (lane < 16) part[wave][lane] = lane < a.kout ? mine : 0ull;
-  __syncthreads();
-  if (wave != 0) return;
-  const uint64_t key = part[lane >> 4][lane & 15];
-  int rank = 0;
-#pragma unroll
-  for (int i = 0; i < 64; ++i) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, i);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), i);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    rank += o > key ? 1 : 0;
-  }
-  const int nnz = __builtin_popcountll(__ballot(key != 0ull));
-  if (key != 0ull && rank < a.kout) {
-    const float wv = merge_key_val(key);
-    const int wi = merge_key_idx(key);
-    a.out_val[qi * a.kout + rank] = wv;
-    if (a.out_idx) a.out_idx[qi * a.kout + rank] = (int64_t)wi + a.idx_base;
-    if (a.out_idx32) a.out_idx32[qi * a.kout + rank] = wi;
-    if (rank == a.kout - 1) {
-      if (a.kth_val) a.kth_val[qi] = wv;
-      if (a.kth_idx) a.kth_idx[qi] = wi;
-    }
-  }
-  if (lane >= nnz && lane < a.kout) {   // fewer than kout entries in all lists together
-    a.out_val[qi * a.kout + lane] = kNegInf;
-    if (a.out_idx) a.out_idx[qi * a.kout + lane] = -1;
-    if (a.out_idx32) a.out_idx32[qi * a.kout + lane] = -1;
-    if (lane == a.kout - 1) {
-      if (a.kth_val) a.kth_val[qi] = kNegInf;
-      if (a.kth_idx) a.kth_idx[qi] = -1;
-    }
-  }
-}
-
-// --------------------------------------------------------------------------
-// select: top-k of an UNSORTED candidate buffer (what the candidate-append scans leave: [cap][nq], cnt[nq]) plus an
-// optional sorted list per query (the prefix result).  One wave per query, every entry a 64-bit (score, ~row) key
-// in a register (lane l owns candidates l, l + 64, ...; its last slot takes entry l of the sorted list).
-//   1. the k-th largest SCORE by a bitwise search (32 steps of "how many scores are >= t": one compare-and-count
-//      per slot and a wave sum) - no key ever moves;
-//   2. ties at that score (rare) are cut by the same search on the row half of the key: exactly k keys selected;
-//   3. the selected keys are compacted to one per lane through LDS (ballot / mbcnt positions) and ranked by
-//      counting, lane i comparing with every other lane's key (64 readlane steps); lane i stores at its rank.
-// (k rounds of wave maximum over all slots - the first version - cost 14.6 us at 15 slots and 72-78 us at 47.)
-// cap = 64 (LPL - 1).
-// --------------------------------------------------------------------------
-struct SelectArgs {
-  const float* cand_val;   // [nq][cap] (query-major: a query's candidates are contiguous)
-  const int* cand_idx;
-  const int* cand_cnt;
-  int cap;
-  const float* pre_val;  // optional [nq][kpre], sorted
-  const int* pre_idx;
-  int kpre;
-  float* out_val;
-  int64_t* out_idx;
-  int64_t nq, idx_base;
-  int k;
-  const int* gate;       // run only if (*gate != 0) == (gate_want != 0)
-  int gate_want;
-};
-
-// wave-uniform sum of an int over the 64 lanes: four DPP steps inside each row of 16 lanes, then four v_readlane.
-// (A __shfl_xor butterfly is six dependent ds_bpermute round trips: the 32-step searches below spent 11 us in them.)
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);  // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);  // row_mirror: every lane holds its row's sum
-  return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-         __builtin_amdgcn_readlane(v, 48);
-}
-
-// The k largest of the wave's keys kq[LPL] (0 = empty slot), one per lane (unsorted) plus its rank among them:
-// steps 1-3 of the select comment above.  `compact` is the wave's 64-entry LDS scratch.  Returns the number of keys
-// found (min(k, live keys)); lanes >= that hold key 0.
-template <int LPL>
-__device__ __forceinline__ int select_keys(const uint64_t (&kq)[LPL], int kwant, int lane, uint64_t* compact,
-                                           uint64_t& mine, int& rank) {
-  int live = 0;
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) live += kq[j] != 0ull ? 1 : 0;
-  live = wave_sum_i32(live);
-  const int k = kwant < live ? kwant : live;
-  // 1. T = k-th largest score half
-  uint32_t T = 0u;
-  if (k > 0) {
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-      const uint32_t t = T | (1u << bit);
-      int c = 0;
-#pragma unroll
-      for (int j = 0; j < LPL; ++j) c += (uint32_t)(kq[j] >> 32) >= t ? 1 : 0;
-      if (wave_sum_i32(c) >= k) T = t;
-    }
-  }
-  // 2. keys above T are in; `need` of the keys AT T are in, largest row half (= smallest row) first
-  int cgt = 0, ceq = 0;
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) {
-    const uint32_t u = (uint32_t)(kq[j] >> 32);
-    cgt += u > T ? 1 : 0;
-    ceq += (u == T && kq[j] != 0ull) ? 1 : 0;
-  }
-  cgt = wave_sum_i32(cgt);
-  ceq = wave_sum_i32(ceq);
-  const int need = k - cgt;
-  uint32_t Lo = 0u;  // smallest accepted row half among the ties
-  if (need < ceq) {
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-      const uint32_t t = Lo | (1u << bit);
-      int c = 0;
-#pragma unroll
-      for (int j = 0; j < LPL; ++j) c += ((uint32_t)(kq[j] >> 32) == T && (uint32_t)kq[j] >= t && kq[j] != 0ull) ? 1 : 0;
-      if (wave_sum_i32(c) >= need) Lo = t;
-    }
-  }
-  // 3. compaction: position = keys selected in earlier slots + selected lanes below this one in this slot
-  int base = 0;
-#pragma unroll
-  for (int j = 0; j < LPL; ++j) {
-    const uint32_t u = (uint32_t)(kq[j] >> 32);
-    const bool sel = k > 0 && kq[j] != 0ull && (u > T || (u == T && (uint32_t)kq[j] >= Lo));
-    const uint64_t m = __ballot(sel);
-    if (sel) compact[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = kq[j];
-    base += __builtin_popcountll(m);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same wave wrote and reads: LDS is in order, this pins the compiler
-  mine = lane < k ? compact[lane] : 0ull;
-  rank = 0;
-#pragma unroll 8
-  for (int j = 0; j < 64; ++j) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, j);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), j);
-    rank += ((((uint64_t)hi << 32) | lo) > mine) ? 1 : 0;
-  }
-  return k;
-}
-
-template <int LPL>
-__global__ __launch_bounds__(256) void topk_select_kernel(SelectArgs a) {
-  __shared__ uint64_t compact[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t qi = (int64_t)blockIdx.x * 4 + wave;
-  if (qi >= a.nq) return;
-  if (a.gate && ((*a.gate != 0) != (a.gate_want != 0))) return;
-  int cnt = a.cand_cnt[qi];
-  cnt = cnt < a.cap ? cnt : a.cap;
-  uint64_t kq[LPL];
-#pragma unroll
-  for (int j = 0; j < LPL - 1; ++j) {
-    const int e = lane + 64 * j;
-    kq[j] = 0ull;
-    if (e < cnt) kq[j] = merge_key(a.cand_val[qi * a.cap + e], a.cand_idx[qi * a.cap + e]);
-  }
-  kq[LPL - 1] = 0ull;
-  if (a.pre_val && lane < a.kpre) kq[LPL - 1] = merge_key(a.pre_val[qi * a.kpre + lane], a.pre_idx[qi * a.kpre + lane]);
-  uint64_t mine;
-  int rank;
-  const int k = select_keys<LPL>(kq, a.k, lane, compact[wave], mine, rank);
-  if (lane < k) {
-    a.out_val[qi * a.k + rank] = merge_key_val(mine);
-    a.out_idx[qi * a.k + rank] = (int64_t)merge_key_idx(mine) + a.idx_base;
-  } else if (lane < a.k) {   // fewer than k rows in all
-    a.out_val[qi * a.k + lane] = kNegInf;
-    a.out_idx[qi * a.k + lane] = -1;
-  }
-}
-
-// select with FOUR waves per query (big candidate buffers: 16 < k <= 64): wave w selects the k best of candidates
-// w, w + 4, ... (wave 0 also holds the sorted extra list), the four results meet in LDS and wave 0 selects and ranks
-// the k best of those <= 4k keys.  LPLQ = slots per lane of a wave = ceil(cap / 256) + 1.
-template <int LPLQ>
-__global__ __launch_bounds__(256) void topk_select4_kernel(SelectArgs a) {
-  __shared__ uint64_t compact[4][64];
-  __shared__ uint64_t stage[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t qi = blockIdx.x;
-  if (a.gate && ((*a.gate != 0) != (a.gate_want != 0))) return;
-  int cnt = a.cand_cnt[qi];
-  cnt = cnt < a.cap ? cnt : a.cap;
-  uint64_t kq[LPLQ];
-#pragma unroll
-  for (int j = 0; j < LPLQ - 1; ++j) {
-    const int e = 4 * (lane + 64 * j) + wave;
-    kq[j] = 0ull;
-    if (e < cnt) kq[j] = merge_key(a.cand_val[qi * a.cap + e], a.cand_idx[qi * a.cap + e]);
-  }
-  kq[LPLQ - 1] = 0ull;
-  if (wave == 0 && a.pre_val && lane < a.kpre)
-    kq[LPLQ - 1] = merge_key(a.pre_val[qi * a.kpre + lane], a.pre_idx[qi * a.kpre + lane]);
-  uint64_t mine;
-  int rank;
-  select_keys<LPLQ>(kq, a.k, lane, compact[wave], mine, rank);
-  stage[wave][lane] = mine;   // 0 beyond the wave's count
-  __syncthreads();
-  if (wave != 0) return;
-  uint64_t k2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) k2[j] = stage[j][lane];
-  const int k = select_keys<4>(k2, a.k, lane, compact[0], mine, rank);
-  if (lane < k) {
-    a.out_val[qi * a.k + rank] = merge_key_val(mine);
-    a.out_idx[qi * a.k + rank] = (int64_t)merge_key_idx(mine) + a.idx_base;
-  } else if (lane < a.k) {   // fewer than k rows in all
-    a.out_val[qi * a.k + lane] = kNegInf;
-    a.out_idx[qi * a.k + lane] = -1;
-  }
-}
-
-// --------------------------------------------------------------------------
-// merge of SORTED partial lists (the prefix lists: nlists x [nq][16]) by selection instead of k rounds of wave
-// maximum: (a) the kout lists with the largest HEAD keys are found with select_keys on the heads (one slot per
-// list); an entry of any other list is below its own head, hence below kout entries of those lists, and cannot be
-// in the top kout: (b) only those kout x 16 <= 256 entries are loaded (4 slots per lane) and (c) selected and ranked.
-// Exact under the (score desc, row asc) order (keys are unique).  ~8 us where the rounds took 17-19 us.
-// Same groups / outputs as topk_merge32_kernel (out_idx32, kth_val, zero_cnt); kin == 16, kout <= 16.
-// --------------------------------------------------------------------------
-template <int HLPL>
-__global__ __launch_bounds__(256) void topk_merge_sel_kernel(MergeArgs<int> a) {
-  __shared__ uint64_t compact[4][64];
-  __shared__ int sel_list[4][16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t qi = (int64_t)blockIdx.x * 4 + wave;
-  if (qi >= a.nq) return;
-  const int ng_ = a.ngroups > 1 ? a.ngroups : 1, grp = (int)blockIdx.y;
-  if (a.zero_cnt && lane == 0 && grp == 0) {
-    a.zero_cnt[qi] = 0;
-    if (qi == 0) a.zero_cnt[a.nq] = 0;
-  }
-  const int nl = (a.nlists - grp + ng_ - 1) / ng_;
-  const int64_t gout = (int64_t)grp * a.nq;
-  // (a) heads: slot j of lane l = list l + 64 j of this group, as TRUE keys (a tie between heads must resolve by
-  //     row index exactly as in the final order); the kout-th largest head key is then the admission bar
-  uint64_t hk[HLPL];
-#pragma unroll
-  for (int j = 0; j < HLPL; ++j) {
-    const int list = lane + 64 * j;
-    hk[j] = 0ull;
-    if (list < nl) {
-      const int64_t o = ((int64_t)(list * ng_ + grp) * a.nq + qi) * a.kin;
-      hk[j] = merge_key(a.vals[o], a.idx[o]);
-    }
-  }
-  uint64_t mine;
-  int rank;
-  const int nsel = select_keys<HLPL>(hk, a.kout, lane, compact[wave], mine, rank);
-  if (lane < nsel && rank == nsel - 1) compact[wave][0] = mine;   // the bar (keys are unique: one lane writes)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const uint64_t bar = nsel > 0 ? compact[wave][0] : ~0ull;
-  int nlist = 0;
-#pragma unroll
-  for (int j = 0; j < HLPL; ++j) {
-    const bool sel = hk[j] != 0ull && hk[j] >= bar;
-    const uint64_t m = __ballot(sel);
-    if (sel) sel_list[wave][nlist + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = lane + 64 * j;
-    nlist += __builtin_popcountll(m);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  // (b) the entries of the selected lists: entry e = lane + 64 j -> list e / 16, position e % 16
-  uint64_t kq[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int e = lane + 64 * j;
-    kq[j] = 0ull;
-    if ((e >> 4) < nlist) {
-      const int list = sel_list[wave][e >> 4];
-      const int64_t o = ((int64_t)(list * ng_ + grp) * a.nq + qi) * a.kin + (e & 15);
-      kq[j] = merge_key(a.vals[o], a.idx[o]);
-    }
-  }
-  // (c)
-  const int k = select_keys<4>(kq, a.kout, lane, compact[wave], mine, rank);
-  if (lane < a.kout) {
-    const bool have = lane < k;
-    const int slot = have ? rank : lane;
-    const float wv = have ? merge_key_val(mine) : kNegInf;
-    const int wi = have ? merge_key_idx(mine) : -1;
-    a.out_val[(gout + qi) * a.kout + slot] = wv;
-    if (a.out_idx) a.out_idx[(gout + qi) * a.kout + slot] = have ? (int64_t)wi + a.idx_base : -1;
-    if (a.out_idx32) a.out_idx32[(gout + qi) * a.kout + slot] = wi;
-    if (slot == a.kout - 1) {
-      if (a.kth_val) a.kth_val[gout + qi] = wv;
-      if (a.kth_idx) a.kth_idx[gout + qi] = wi;
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void row_invnorm_kernel(const T* __restrict__ x, int64_t n, int d,
-                                                          int64_t ldx, float eps,
-                                                          float* __restrict__ out) {
-  // one wave per row; lane l sums elements 4*(l + 64 j) + e in order, then an
-  // xor butterfly 32,16,...,1 (mirrored by oracle/knn_oracle.c: hcir_oracle_row_invnorm).
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n) return;
-  const T* p = x + row * ldx;
-  float s = 0.f;
-  for (int k = 4 * lane; k < d; k += 256) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = (float)p[k + e];
-      s = __builtin_fmaf(v, v, s);
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if (lane == 0) out[row] = 1.0f / fmaxf(sqrtf(s), eps);
-}
-
-__global__ __launch_bounds__(256) void l2_normalize_kernel(const float* __restrict__ x, int64_t n,
-                                                           int d, float eps, float* __restrict__ y32,
-                                                           _Float16* __restrict__ y16) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n) return;
-  const float* p = x + row * (int64_t)d;
-  float s = 0.f;
-  for (int k = 4 * lane; k < d; k += 256) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s = __builtin_fmaf(p[k + e], p[k + e], s);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  const float nrm = fmaxf(sqrtf(s), eps);
-  for (int k = 4 * lane; k < d; k += 256) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = p[k + e] / nrm;
-      if (y32) y32[row * (int64_t)d + k + e] = v;
-      if (y16) y16[row * (int64_t)d + k + e] = (_Float16)v;
-    }
-  }
-}
-
-template <typename T>
-__global__ void convert_kernel(const float* __restrict__ x, int64_t n, T* __restrict__ y) {
-  int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
-  for (; i + 3 < n; i += stride) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[i + e] = (T)v[e];
-  }
-  if (i < n && i + 3 >= n)
-    for (int64_t j = i; j < n; ++j) y[j] = (T)x[j];
-}
-
 __global__ void pass_copy_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int64_t nq,
                                  int kk, int k, int done, int64_t idx_base,
                                  float* __restrict__ out_val, int64_t* __restrict__ out_idx) {
@@ -1429,27 +720,39 @@ __global__ void pass_copy_kernel(const float* __restrict__ pv, const int* __rest
 // sim_topk_plan (sim_plan.h: plain C++, pinned on the CPU by tests/test_sim_plan_host.py).  The code below fills
 // argument structs from that plan and launches: one function per flow, no state passed between them.
 
-// the merge of up to `nlists` (+ the extra) sorted 32-bit-index lists: four waves per query for kout <= 16 with one
-// group, the one-wave kernel otherwise
-inline void launch_merge32(const MergeArgs<int>& m, hipStream_t st) {
+// the merge of `nlists` (+ the extra) sorted 32-bit-index lists by the kernel sim_merge_route names; a launch that
+// could not read every list is refused
+int launch_merge(const MergeArgs& m, hipStream_t st) {
   const int total = m.nlists + (m.extra_val ? 1 : 0);
-  const int merge_grid = (int)hcir_cdiv(m.nq, 4);
-  if (m.kout <= 16 && m.ngroups <= 1 && total <= 256 * 4) {
-    const int lpl = (total + 255) / 256;
-    if (lpl <= 1)
-      hipLaunchKernelGGL(topk_merge32q_kernel<1>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
-    else if (lpl == 2)
-      hipLaunchKernelGGL(topk_merge32q_kernel<2>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
-    else if (lpl == 3)
-      hipLaunchKernelGGL(topk_merge32q_kernel<3>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
-    else
-      hipLaunchKernelGGL(topk_merge32q_kernel<4>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
-    return;
+  const SimMergeRoute r = sim_merge_route(total, m.out.k, m.ngroups);
+  if (r.capacity < total) return HCIR_ERR_UNSUPPORTED;
+  const unsigned merge_grid = (unsigned)hcir_cdiv(m.nq, 4);
+  switch (r.kind) {
+    case SIM_MERGE_FOUR_WAVES:
+      static_assert(kMergeQuadMaxLPL == 4, "one instantiation per lists-per-lane count of sim_merge_route");
+      if (r.lpl == 1)
+        hipLaunchKernelGGL(topk_merge32q_kernel<1>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
+      else if (r.lpl == 2)
+        hipLaunchKernelGGL(topk_merge32q_kernel<2>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
+      else if (r.lpl == 3)
+        hipLaunchKernelGGL(topk_merge32q_kernel<3>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
+      else if (r.lpl == 4)
+        hipLaunchKernelGGL(topk_merge32q_kernel<4>, dim3((unsigned)m.nq), dim3(256), 0, st, m);
+      else
+        return HCIR_ERR_UNSUPPORTED;
+      break;
+    case SIM_MERGE_WAVE:
+      if (r.lpl != kMergeLPL) return HCIR_ERR_UNSUPPORTED;
+      hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3(merge_grid), dim3(256), 0, st, m);
+      break;
+    case SIM_MERGE_SELECT:
+      if (r.lpl != kMergeLPL || m.kin != 16) return HCIR_ERR_UNSUPPORTED;
+      hipLaunchKernelGGL(topk_merge_sel_kernel<kMergeLPL>, dim3(merge_grid, (unsigned)m.ngroups), dim3(256), 0, st, m);
+      break;
+    default: return HCIR_ERR_UNSUPPORTED;
   }
-  if (total > 64 * kMergeLPL)   // (callers keep their list counts within 64 * kCandLPL)
-    hipLaunchKernelGGL(topk_merge32_kernel<kCandLPL>, dim3(merge_grid), dim3(256), 0, st, m);
-  else
-    hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3(merge_grid), dim3(256), 0, st, m);
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
 }
 
 template <typename T, int KP, int QT, int WQ, int WGG>
@@ -1553,39 +856,38 @@ void launch_list_scan(const Call& c, int kp, int qb, const ScanArgs& a, int grid
 }
 
 // partial lists -> the list of the `kout` best in the workspace (prefix / previous pass), rank kout - 1 to kth_val
-MergeArgs<int> merge_to_workspace(const Call& c, const SimWorkspace& w, int nlists, int kin, int kout, float* kth_val) {
-  MergeArgs<int> m{};
+MergeArgs merge_to_workspace(const Call& c, const SimWorkspace& w, int nlists, int kin, int kout, float* kth_val) {
+  MergeArgs m{};
   m.vals = w.part_val;
   m.idx = w.part_idx;
   m.nq = c.nq;
   m.nlists = nlists;
   m.kin = kin;
-  m.kout = kout;
-  m.out_val = w.pre_val;
-  m.out_idx32 = w.pre_idx;
-  m.kth_val = kth_val;
+  m.out.k = kout;
+  m.out.val = w.pre_val;
+  m.out.idx32 = w.pre_idx;
+  m.out.kth_val = kth_val;
   return m;
 }
 // partial lists (+ the prefix list) -> the caller's output
-MergeArgs<int> merge_to_output(const Call& c, const SimWorkspace& w, int nlists, int kin, bool with_prefix,
+MergeArgs merge_to_output(const Call& c, const SimWorkspace& w, int nlists, int kin, bool with_prefix,
                                const int* gate, int gate_want) {
-  MergeArgs<int> m{};
+  MergeArgs m{};
   m.vals = w.part_val;
   m.idx = w.part_idx;
   m.nq = c.nq;
   m.nlists = nlists;
   m.kin = kin;
-  m.kout = c.k;
+  m.out.k = c.k;
   if (with_prefix) {
     m.extra_val = w.pre_val;
     m.extra_idx = w.pre_idx;
     m.kin_extra = c.k;
   }
-  m.out_val = c.out_val;
-  m.out_idx = c.out_idx;
-  m.idx_base = c.idx_base;
-  m.gate = gate;
-  m.gate_want = gate_want;
+  m.out.val = c.out_val;
+  m.out.idx = c.out_idx;
+  m.out.idx_base = c.idx_base;
+  m.gate = TopkGate{gate, gate_want};
   return m;
 }
 
@@ -1595,21 +897,16 @@ int run_single_scan(const SimTopkPlan& p, const SimWorkspace& w, const Call& c, 
   a.gate = gate;
   launch_list_scan(c, p.kp, p.qb, a, p.grid_a);
   HCIR_LAUNCH_CHECK();
-  launch_merge32(merge_to_output(c, w, p.grid_a, p.kp, false, gate, 1), c.st);
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
+  return launch_merge(merge_to_output(c, w, p.grid_a, p.kp, false, gate, 1), c.st);
 }
 
 // phase A of the list flow: rows [0, S) -> the prefix top-k list and its k-th score, the floor of what follows
 int run_list_prefix(const SimTopkPlan& p, const SimWorkspace& w, const Call& c, int* zero_cnt) {
   launch_list_scan(c, p.kp, p.qb, list_scan_args(c, w, p.qb, c.k, 0, p.S), p.grid_a);
   HCIR_LAUNCH_CHECK();
-  MergeArgs<int> m = merge_to_workspace(c, w, p.grid_a, p.kp, c.k, w.floor_val);
-  m.gate_want = 1;  // (no gate: ignored)
+  MergeArgs m = merge_to_workspace(c, w, p.grid_a, p.kp, c.k, w.floor_val);
   m.zero_cnt = zero_cnt;
-  launch_merge32(m, c.st);
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
+  return launch_merge(m, c.st);
 }
 
 // The list flow: phase A unless the caller's flow has run it; phase B: rows [S, ng) with the prefix k-th score as
@@ -1624,9 +921,7 @@ int run_list_two_phase(const SimTopkPlan& p, const SimWorkspace& w, const Call& 
   a.gate = gate;
   launch_list_scan(c, p.kp, p.qb, a, p.grid_b);
   HCIR_LAUNCH_CHECK();
-  launch_merge32(merge_to_output(c, w, p.grid_b, p.kp, true, gate, gate ? 1 : 0), c.st);
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
+  return launch_merge(merge_to_output(c, w, p.grid_b, p.kp, true, gate, gate ? 1 : 0), c.st);
 }
 
 // <= 128 queries, k <= 64, big gallery (docs/LAB_NOTEBOOK.md "sim_topk: candidate flow").
@@ -1644,14 +939,11 @@ int run_candidate_flow(const SimTopkPlan& p, const SimWorkspace& w, const Call& 
   ScanArgs s = list_scan_args(c, w, p.cand_qb, p.G == 1 ? c.k : 16, 0, p.S);
   launch_list_scan(c, 16, p.cand_qb, s, p.cand_grid_a);
   HCIR_LAUNCH_CHECK();
-  MergeArgs<int> m = merge_to_workspace(c, w, p.cand_grid_a, 16, s.k, w.floor_val);
+  MergeArgs m = merge_to_workspace(c, w, p.cand_grid_a, 16, s.k, w.floor_val);
   m.zero_cnt = w.cand_cnt;
   m.ngroups = p.G;
-  if (p.G == 1)
-    launch_merge32(m, c.st);   // four waves per query (the selection merge below: 21.6 us at 32 queries)
-  else
-    hipLaunchKernelGGL(topk_merge_sel_kernel<kMergeLPL>, dim3(merge_grid, p.G), dim3(256), 0, c.st, m);
-  HCIR_LAUNCH_CHECK();
+  // G = 1: four waves per query (the selection merge took 21.6 us there at 32 queries); G > 1: the selection merge
+  if (const int rc = launch_merge(m, c.st)) return rc;
   s.row_begin = p.G == 1 ? p.S : 0;
   s.row_end = c.ng;
   s.floor_val = w.floor_val;
@@ -1675,19 +967,24 @@ int run_candidate_flow(const SimTopkPlan& p, const SimWorkspace& w, const Call& 
     sa.pre_idx = w.pre_idx;
     sa.kpre = c.k;
   }
-  sa.out_val = c.out_val;
-  sa.out_idx = c.out_idx;
+  sa.out.val = c.out_val;
+  sa.out.idx = c.out_idx;
+  sa.out.idx_base = c.idx_base;
+  sa.out.k = c.k;
   sa.nq = c.nq;
-  sa.idx_base = c.idx_base;
-  sa.k = c.k;
-  sa.gate = w.overflow;
-  sa.gate_want = 0;
-  if (p.select == SIM_SELECT_WAVE_SMALL)
+  sa.gate = TopkGate{w.overflow, 0};
+  // slots of a select launch: 64 (LPL - 1) candidates per wave (x 4 waves), the last slot of a lane is the prefix list's
+  constexpr int kSel4LPL = (kCandCapBig + 255) / 256 + 1;
+  static_assert(64 * (kSelLPLSmall - 1) >= kCandCapSmall && 64 * (kCandLPL - 1) >= kCandCap &&
+                    256 * (kSel4LPL - 1) >= kCandCapBig, "a select kernel reads fewer candidates than its scan may append");
+  if (p.select == SIM_SELECT_WAVE_SMALL && p.cand_cap <= kCandCapSmall)
     hipLaunchKernelGGL(topk_select_kernel<kSelLPLSmall>, dim3(merge_grid), dim3(256), 0, c.st, sa);
-  else if (p.select == SIM_SELECT_WAVE)
+  else if (p.select == SIM_SELECT_WAVE && p.cand_cap <= kCandCap)
     hipLaunchKernelGGL(topk_select_kernel<kCandLPL>, dim3(merge_grid), dim3(256), 0, c.st, sa);
+  else if (p.select == SIM_SELECT_FOUR_WAVES && p.cand_cap <= kCandCapBig)
+    hipLaunchKernelGGL(topk_select4_kernel<kSel4LPL>, dim3((unsigned)c.nq), dim3(256), 0, c.st, sa);
   else
-    hipLaunchKernelGGL(topk_select4_kernel<(kCandCapBig + 255) / 256 + 1>, dim3((unsigned)c.nq), dim3(256), 0, c.st, sa);
+    return HCIR_ERR_UNSUPPORTED;
   HCIR_LAUNCH_CHECK();
   return p.fallback_phases == 2 ? run_list_two_phase(p, w, c, w.overflow, p.phase_a_done)
                                 : run_single_scan(p, w, c, w.overflow);
@@ -1718,12 +1015,11 @@ int run_big_tile_flow(const SimTopkPlan& p, const SimWorkspace& w, const Call& c
                          c.st, b);
   });
   HCIR_LAUNCH_CHECK();
-  MergeArgs<int> m = merge_to_output(c, w, p.cand_cap, 1, true, w.overflow, 0);
+  MergeArgs m = merge_to_output(c, w, p.cand_cap, 1, true, w.overflow, 0);
   m.vals = w.cand_val;
   m.idx = w.cand_idx;
   m.nlists_q = w.cand_cnt;
-  launch_merge32(m, c.st);
-  HCIR_LAUNCH_CHECK();
+  if (const int rc = launch_merge(m, c.st)) return rc;
   return run_list_two_phase(p, w, c, w.overflow, p.phase_a_done);
 }
 
@@ -1737,10 +1033,9 @@ int run_multipass(const SimTopkPlan& p, const SimWorkspace& w, const Call& c) {
     a.ceil_idx = pass ? w.ceil_idx : nullptr;
     launch_list_scan(c, p.kp, p.qb, a, p.grid_a);
     HCIR_LAUNCH_CHECK();
-    MergeArgs<int> m = merge_to_workspace(c, w, p.grid_a, p.kp, kk, w.ceil_val);
-    m.kth_idx = w.ceil_idx;
-    hipLaunchKernelGGL(topk_merge32_kernel<kMergeLPL>, dim3((int)hcir_cdiv(c.nq, 4)), dim3(256), 0, c.st, m);
-    HCIR_LAUNCH_CHECK();
+    MergeArgs m = merge_to_workspace(c, w, p.grid_a, p.kp, kk, w.ceil_val);
+    m.out.kth_idx = w.ceil_idx;
+    if (const int rc = launch_merge(m, c.st)) return rc;
     // scatter this pass's [nq][kk] block into out[:, done:done+kk]
     hipLaunchKernelGGL(pass_copy_kernel, dim3((unsigned)hcir_cdiv(c.nq * kk, 256)), dim3(256), 0, c.st,
                        w.pre_val, w.pre_idx, c.nq, kk, c.k, done, c.idx_base, c.out_val, c.out_idx);
@@ -1794,62 +1089,9 @@ int hcir_topk_merge(const float* vals, const int64_t* idx, int32_t nlists, int64
   if (!vals || !idx || !out_val || !out_idx) return HCIR_ERR_INVALID;
   if (nlists <= 0 || nq <= 0 || k_in <= 0 || k_out <= 0) return HCIR_ERR_INVALID;
   if (nlists > 64 * kMergeLPL) return HCIR_ERR_UNSUPPORTED;
-  MergeArgs<int64_t> m{};
-  m.vals = vals;
-  m.idx = idx;
-  m.nq = nq;
-  m.nlists = nlists;
-  m.kin = k_in;
-  m.kout = k_out;
-  m.out_val = out_val;
-  m.out_idx = out_idx;
-  m.idx_base = 0;
-  hipLaunchKernelGGL(topk_merge_kernel<int64_t>, dim3((int)hcir_cdiv(nq, 4)), dim3(256), 0,
+  const Merge64Args m{vals, idx, out_val, out_idx, nq, nlists, k_in, k_out};
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((int)hcir_cdiv(nq, 4)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), m);
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
-}
-
-int hcir_row_invnorm(const void* x, int64_t n, int32_t d, int64_t ldx, int dtype, float eps,
-                     float* out, void* stream) {
-  HCIR_ENTER();
-  if (!x || !out || n <= 0 || d <= 0 || (d & 3) || ldx < d) return HCIR_ERR_INVALID;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)hcir_cdiv(n, 4)), block(256);
-  if (dtype == HCIR_F32)
-    hipLaunchKernelGGL(row_invnorm_kernel<float>, grid, block, 0, st, (const float*)x, n, d, ldx, eps, out);
-  else if (dtype == HCIR_F16)
-    hipLaunchKernelGGL(row_invnorm_kernel<_Float16>, grid, block, 0, st, (const _Float16*)x, n, d, ldx, eps, out);
-  else if (dtype == HCIR_BF16)
-    hipLaunchKernelGGL(row_invnorm_kernel<__bf16>, grid, block, 0, st, (const __bf16*)x, n, d, ldx, eps, out);
-  else
-    return HCIR_ERR_UNSUPPORTED;
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
-}
-
-int hcir_l2_normalize(const float* x, int64_t n, int32_t d, float eps, float* y_f32, void* y_f16,
-                      void* stream) {
-  HCIR_ENTER();
-  if (!x || n <= 0 || d <= 0 || (d & 3)) return HCIR_ERR_INVALID;
-  hipLaunchKernelGGL(l2_normalize_kernel, dim3((unsigned)hcir_cdiv(n, 4)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, n, d, eps, y_f32, (_Float16*)y_f16);
-  HCIR_LAUNCH_CHECK();
-  return HCIR_OK;
-}
-
-int hcir_convert_f32(const float* x, int64_t n, int dtype, void* y, void* stream) {
-  HCIR_ENTER();
-  if (!x || !y || n <= 0) return HCIR_ERR_INVALID;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  int64_t blocks = hcir_cdiv(n, 1024);
-  if (blocks > 4096) blocks = 4096;
-  if (dtype == HCIR_F16)
-    hipLaunchKernelGGL(convert_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, (_Float16*)y);
-  else if (dtype == HCIR_BF16)
-    hipLaunchKernelGGL(convert_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, x, n, (__bf16*)y);
-  else
-    return HCIR_ERR_UNSUPPORTED;
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

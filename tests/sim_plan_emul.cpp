@@ -47,4 +47,54 @@ int emul_geom(int32_t kp, int32_t qb, int32_t* gm, int32_t* max_wg) {
 
 int emul_max_parts() { return kMaxParts; }
 
+void emul_merge_route(int32_t total, int32_t kout, int32_t ngroups, int32_t* out) {
+  const SimMergeRoute r = sim_merge_route(total, kout, ngroups);
+  out[0] = r.kind;
+  out[1] = r.lpl;
+  out[2] = r.capacity;
+}
+
+// Every merge launch of a call, the gated fallback's included, in launch order, as the flows of csrc/sim_topk.hip make
+// them from the plan: 6 values per launch (lists the launch must read - the extra list counted -, kout, groups, then the
+// route's kind, lpl, capacity).  Returns the number of launches (<= max_launches are written).
+int emul_merge_launches(int64_t nq, int64_t ng, int32_t d, int32_t k, int dtype, int has_q_norm, int has_g_norm,
+                        int32_t* out, int max_launches) {
+  const SimTopkPlan p = sim_topk_plan(nq, ng, d, k, dtype, has_q_norm != 0, has_g_norm != 0);
+  int n = 0;
+  auto launch = [&](int lists, bool extra, int kout, int groups) {
+    const int total = lists + (extra ? 1 : 0);
+    const SimMergeRoute r = sim_merge_route(total, kout, groups);
+    if (n < max_launches) {
+      const int32_t v[6] = {total, kout, groups, r.kind, r.lpl, r.capacity};
+      for (int i = 0; i < 6; ++i) out[6 * n + i] = v[i];
+    }
+    ++n;
+  };
+  auto single_scan = [&] { launch(p.grid_a, false, k, 1); };
+  auto list_prefix = [&] { launch(p.grid_a, false, k, 1); };
+  auto two_phase = [&](bool phase_a_done) {
+    if (!phase_a_done) list_prefix();
+    launch(p.grid_b, true, k, 1);
+  };
+  switch (p.flow) {
+    case SIM_FLOW_SINGLE_SCAN: single_scan(); break;
+    case SIM_FLOW_LIST_TWO_PHASE: two_phase(false); break;
+    case SIM_FLOW_CANDIDATE:
+      launch(p.cand_grid_a, false, p.G == 1 ? k : 16, p.G);
+      if (p.fallback_phases == 2)
+        two_phase(p.phase_a_done != 0);
+      else
+        single_scan();
+      break;
+    case SIM_FLOW_BIG_TILE:
+      list_prefix();
+      launch(p.cand_cap, true, k, 1);
+      two_phase(p.phase_a_done != 0);
+      break;
+    default:
+      for (int done = 0; done < k; done += 64) launch(p.grid_a, false, k - done < 64 ? k - done : 64, 1);
+  }
+  return n;
+}
+
 }  // extern "C"

@@ -18,6 +18,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from _topk_route_shapes import INSTANTIATIONS, ROUTE_SHAPES
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FIELDS = ["flow", "kp", "qb", "gm", "npass", "S", "grid_a", "grid_b", "fallback_phases", "phase_a_done", "G", "cand_qb",
@@ -89,6 +91,9 @@ def emul():
     L.emul_sim_workspace_layout.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
     L.emul_sim_plan_candidate.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]
     L.emul_geom.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    L.emul_merge_route.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    L.emul_merge_launches.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     return L
 
 
@@ -178,3 +183,89 @@ def test_candidate_guard(emul):
         for ng in (500, 8191, 8192):
             assert emul.emul_sim_plan_candidate(nq, ng, k, ctypes.byref(S)) == 0 and S.value == -1
         assert emul.emul_sim_plan_candidate(nq, 8193, k, ctypes.byref(S)) == 1 and S.value == 8192
+
+
+# ---- merge routing (sim_merge_route): which kernel of csrc/topk_merge.h a launch gets, and that it can hold its lists
+MERGE_NONE, MERGE_FOUR_WAVES, MERGE_WAVE, MERGE_SELECT = range(4)            # SimMergeKind
+MERGE_KERNEL = {MERGE_FOUR_WAVES: "merge32q", MERGE_WAVE: "merge32", MERGE_SELECT: "merge_sel"}
+SELECT_KERNEL = {SEL_WAVE_SMALL: ("select", 8), SEL_WAVE: ("select", 16), SEL_FOUR_WAVES: ("select4", 13)}
+
+
+def merge_launches(L, nq, ng, d, k, dtype, norms):
+    """[(total lists, kout, groups, kind, lpl, capacity)] of every merge launch of the call, fallback included"""
+    out = np.zeros((16, 6), np.int32)
+    n = L.emul_merge_launches(nq, ng, d, k, dtype, norms, norms, out.ctypes.data, 16)
+    assert 1 <= n <= 16
+    return [tuple(int(v) for v in row) for row in out[:n]]
+
+
+def routes_reached(L, nq, ng, d, k, dtype=F32, norms=0):
+    r = {(MERGE_KERNEL[kind], lpl) for _, _, _, kind, lpl, _ in merge_launches(L, nq, ng, d, k, dtype, norms)}
+    sel = plan(L, nq, ng, d, k, dtype, norms)["select"]
+    return r | ({SELECT_KERNEL[sel]} if sel != SEL_NONE else set())
+
+
+def test_merge_route_table(emul):
+    """sim_merge_route on both sides of each of its thresholds: 256 lists per lane slot of the four-wave kernel up to
+    1024, kout 16 | 17, groups."""
+    def route(total, kout, groups):
+        o = np.zeros(3, np.int32)
+        emul.emul_merge_route(total, kout, groups, o.ctypes.data)
+        return tuple(int(v) for v in o)
+    for total, lpl in ((1, 1), (256, 1), (257, 2), (512, 2), (513, 3), (768, 3), (769, 4), (961, 4), (1024, 4)):
+        assert route(total, 16, 1) == route(total, 1, 0) == (MERGE_FOUR_WAVES, lpl, 256 * lpl)
+    assert route(1025, 16, 1) == route(4, 17, 1) == route(576, 64, 1) == (MERGE_WAVE, 9, 576)
+    assert route(577, 17, 1)[2] < 577                      # more lists than any kernel holds: the launcher refuses
+    assert route(512, 16, 2) == (MERGE_SELECT, 9, 1152) and route(512, 16, 4) == (MERGE_SELECT, 9, 2304)
+    assert route(512, 17, 2) == (MERGE_NONE, 0, 0)
+
+
+def test_every_merge_launch_holds_its_lists(emul):
+    """Sweep of shapes over every branch point of the plan: each merge launch the flow and its gated fallback make
+    goes to a kernel with at least as many list slots as the launch has lists (a smaller one would silently drop lists
+    and return wrong neighbours).  No launch needs more than 576 lists with kout > 16 - the one-wave kernel with 16
+    lists per lane is not needed - and only the selection merge sees groups."""
+    ngs = [37, 500, 1000, 4099, 8192, 8193, 20000, 32767, 32768, 40000, 60000, 90000, 120000, 131072, 131073, 300000,
+           500000, 1000000, 1250000, 1500000, 1600000, 2000000]
+    shapes = launches = 0
+    seen = set()
+    for nq in (1, 32, 33, 64, 65, 128, 129, 300, 880):
+        for k in (1, 10, 16, 17, 32, 33, 50, 64, 65, 100, 642):
+            for ng in ngs:
+                if k > ng:
+                    continue
+                for dtype in (F32, F16, BF16):
+                    for norms in (0, 1):
+                        for d in (768, 72):
+                            shapes += 1
+                            for total, kout, groups, kind, lpl, cap in merge_launches(emul, nq, ng, d, k, dtype, norms):
+                                launches += 1
+                                assert kind != MERGE_NONE and cap >= total, (nq, ng, d, k, dtype, norms, total, kout)
+                                assert not (total > 576 and kout > 16), (nq, ng, d, k, dtype, norms, total, kout)
+                                assert 1 <= kout <= 64 and (groups > 1) == (kind == MERGE_SELECT)
+                                if kind == MERGE_SELECT:
+                                    assert kout == 16 and 2 <= groups <= 4
+                                seen.add((MERGE_KERNEL[kind], lpl))
+    assert shapes > 20000 and launches > shapes
+    assert seen == {r for r in INSTANTIATIONS if r[0].startswith("merge")}
+
+
+def test_route_shapes_reach_every_instantiation(emul):
+    """The coverage table of the GPU test test_topk_merge_routes: each shape reaches exactly the routes written next
+    to it, and together they reach every merge and select instantiation in the build."""
+    union = set()
+    for (nq, ng, d, k), want, _ in ROUTE_SHAPES:
+        got = routes_reached(emul, nq, ng, d, k)
+        assert got == want, ((nq, ng, d, k), got)
+        union |= got
+    assert union == INSTANTIATIONS
+
+
+def test_instantiations_are_those_in_the_source():
+    """INSTANTIATIONS against the launches written in csrc/sim_topk.hip (template arguments by name)."""
+    import re
+    consts = {"kMergeLPL": 9, "kSelLPLSmall": 8, "kCandLPL": 16, "kSel4LPL": 13}
+    src = open(os.path.join(ROOT, "hair-centric-image-retrieval_amd", "csrc", "sim_topk.hip")).read()
+    found = {(name, consts.get(arg) or int(arg))
+             for name, arg in re.findall(r"hipLaunchKernelGGL\(topk_(merge32q|merge32|merge_sel|select4|select)_kernel<(\w+)>", src)}
+    assert found == INSTANTIATIONS

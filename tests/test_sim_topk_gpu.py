@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from _topk_route_shapes import ROUTE_SHAPES
 from oracle import knn as oknn
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +47,45 @@ def test_sim_topk_f32_bit_exact(ops, nq, ng, d, k):
     rv, ri = oknn.cosine_topk(q, g, k)
     np.testing.assert_array_equal(idx.cpu().numpy(), ri)
     np.testing.assert_array_equal(val.cpu().numpy(), rv)
+
+
+@pytest.mark.parametrize("nq,ng,d,k", [s for s, _, _ in ROUTE_SHAPES],
+                         ids=["-".join(map(str, s)) for s, _, _ in ROUTE_SHAPES])
+def test_topk_merge_routes(ops, nq, ng, d, k):
+    """Every merge and select instantiation of csrc/topk_merge.h, at the smallest shape that reaches it (which routes a
+    shape takes is pinned on the CPU by test_sim_plan_host.py::test_route_shapes_reach_every_instantiation): fp32 at
+    d = 8, bit-exact against the C oracle, without and with an index base (added by the shared result writer)."""
+    q, g = _rand((nq, d), 61), _rand((ng, d), 62)
+    rv, ri = oknn.cosine_topk(q, g, k)
+    qd, gd = torch.from_numpy(q).cuda(), torch.from_numpy(g).cuda()
+    for base in (0, 1 << 33):
+        val, idx = ops.sim_topk(qd, gd, k, idx_base=base)
+        np.testing.assert_array_equal(idx.cpu().numpy() - base, ri)
+        np.testing.assert_array_equal(val.cpu().numpy(), rv)
+
+
+def test_topk_merge_routes_tie_across_prefix(ops):
+    """Key order in the shared round loop, at the four-lists-per-lane merge (768 lists + the prefix list): a gallery
+    row from inside the 8192-row prefix repeated behind it ties exactly; the smaller index comes first.  (The 40 pairs
+    are three times as long as the other rows, so the top of every list is made of such pairs.)"""
+    nq, ng, d, k = 40, 120000, 8, 10
+    q, g = _rand((nq, d), 63), _rand((ng, d), 64)
+    for i in range(nq):
+        g[100 + i] *= 3.0
+        g[9000 + 2500 * i] = g[100 + i]
+        q[i] = g[100 + i]
+    val, idx = ops.sim_topk(torch.from_numpy(q).cuda(), torch.from_numpy(g).cuda(), k)
+    rv, ri = oknn.cosine_topk(q, g, k)
+    np.testing.assert_array_equal(idx.cpu().numpy(), ri)
+    np.testing.assert_array_equal(val.cpu().numpy(), rv)
+    idx, val = idx.cpu().numpy(), val.cpu().numpy()
+    pairs = 0
+    for i in range(nq):                       # prefix row first, its copy right behind it
+        for j in range(k - 1):
+            if 100 <= idx[i, j] < 100 + nq:
+                assert idx[i, j + 1] == 9000 + 2500 * (idx[i, j] - 100) and val[i, j] == val[i, j + 1]
+                pairs += 1
+    assert pairs >= 2 * nq
 
 
 def test_row_invnorm_bit_exact(ops):

@@ -1,11 +1,13 @@
 """Compare the gfx950 device code of the kernel sources against another git revision, function by function.
 
 usage: python3 tools/cmp_device_asm.py <base-rev> [file.hip ...]        (default: every csrc/*.hip)
+       `new.hip:old.hip` compares new.hip of the working tree with old.hip of the base revision (kernels that moved).
 Both trees are compiled with `hipcc --cuda-device-only -S` and the flags of csrc/Makefile.  A function's record is its
 body, its `.amdhsa_kernel` descriptor (VGPRs, SGPRs, LDS, scratch) and its `.set` resource symbols, after local labels
 (.LBB*, .Ltmp*, .Lfunc_end*, inline-asm `%=` labels) are renumbered in order of appearance, the function index is
 dropped from block names, and symbols are demangled and passed through RENAMES.  Exit status 1 when a function
-differs or is new; functions that are gone are only listed.  Refactors that must not move code generation run this."""
+differs or is new; functions that are gone are only listed.  Every function listed comes with its size: instructions,
+VGPRs, SGPRs, LDS and scratch bytes.  Refactors that must not move code generation run this."""
 import io, os, re, subprocess, sys, tarfile, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
@@ -16,7 +18,8 @@ EXTRA = {"attn_bwd.hip": ["-fno-slp-vectorize"]}  # as in csrc/Makefile
 # demangled base-revision name -> name in the working tree (template parameters that were removed)
 RENAMES = [(r"^void (\(anonymous namespace\)::gemm_f16_big_kernel<\d+), true>", r"void \1>"),
            (r"^void (\(anonymous namespace\)::attn_bwd_kernel)<1>", r"\1"),
-           (r"^void (\(anonymous namespace\)::png_inflate_kernel)<true>", r"\1")]
+           (r"^void (\(anonymous namespace\)::png_inflate_kernel)<true>", r"\1"),
+           (r"\(anonymous namespace\)::MergeArgs<int>", "(anonymous namespace)::MergeArgs")]
 
 
 def compile_s(tree, f, outdir):
@@ -46,19 +49,30 @@ def functions(asm, base):
         text = re.sub(r"\bBB\d+_", "BB_", text)
         labels = {}
         text = re.sub(r"\.L\w+", lambda m: labels.setdefault(m.group(0), ".L#%d" % len(labels)), text)
+        text = re.sub(r"[ \t]+;", " ;", text)  # comments are padded to a column that depends on the label's length
         out[dem.get(name, name)] = text
     return out
+
+
+def size(text):
+    """instructions and the descriptor's registers / LDS / scratch of one function record"""
+    d = lambda key: (re.findall(r"\.amdhsa_" + key + r" (\d+)", text) or ["-"])[0]
+    return "%d instr, %s VGPR, %s SGPR, %s B LDS, %s B scratch" % (
+        len(re.findall(r"^\t[a-z]\w*", text, re.M)), d("next_free_vgpr"), d("next_free_sgpr"),
+        d("group_segment_fixed_size"), d("private_segment_fixed_size"))
 
 
 def main():
     base, files = sys.argv[1], sys.argv[2:]
     files = files or sorted(f for f in os.listdir(os.path.join(ROOT, CSRC)) if f.endswith(".hip"))
+    pairs = [f.partition(":")[::2] for f in files]
+    pairs = [(n, o or n) for n, o in pairs]
     with tempfile.TemporaryDirectory() as tmp:
         arch = subprocess.run(["git", "-C", ROOT, "archive", base, CSRC, "include"], capture_output=True, check=True)
         with tarfile.open(fileobj=io.BytesIO(arch.stdout)) as t:
             t.extractall(os.path.join(tmp, "base"))
         os.mkdir(os.path.join(tmp, "new"))
-        jobs = [(os.path.join(tmp, "base"), f, tmp + "/base") for f in files] + [(ROOT, f, tmp + "/new") for f in files]
+        jobs = [(os.path.join(tmp, "base"), o, tmp + "/base") for _, o in pairs] + [(ROOT, n, tmp + "/new") for n, _ in pairs]
         with ThreadPoolExecutor(16) as ex:
             asm = list(ex.map(lambda j: compile_s(*j), jobs))
     bad = 0
@@ -67,12 +81,12 @@ def main():
         same = sum(old[k] == new[k] for k in old.keys() & new.keys())
         print(f"{f}: {same} identical, {len(old) - same} differ or gone, {len(new.keys() - old.keys())} new")
         for k in sorted(old.keys() - new.keys()):
-            print("   gone:", k)
+            print("   gone:", k, "[%s]" % size(old[k]))
         for k in sorted(new.keys() - old.keys()):
-            print("   new: ", k)
+            print("   new: ", k, "[%s]" % size(new[k]))
             bad += 1
         for k in sorted(k for k in old.keys() & new.keys() if old[k] != new[k]):
-            print("   DIFFERS:", k)
+            print("   DIFFERS:", k, "[%s] -> [%s]" % (size(old[k]), size(new[k])))
             bad += 1
     return 1 if bad else 0
 
