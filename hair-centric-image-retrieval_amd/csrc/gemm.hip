@@ -20,6 +20,7 @@
 #include "sim_core.h"
 #include "act.h"
 #include "gemm_plan.h"
+#include "patch_plan.h"
 #include <stdlib.h>
 
 namespace {
@@ -37,6 +38,9 @@ constexpr int EPI_RESID_F16_STATS = 7;
 constexpr int EPI_LN_BIAS_F16 = 8;
 constexpr int EPI_LN_BIAS_GELU_F16 = 9;
 constexpr int EPI_BIAS_F16_DUAL_GELU = 10;  // out = fp16(acc + bias) AND out2 = fp16(gelu(acc + bias)) (hcir_gemm_f16_gelu_dual)
+// patch embedding (hcir_patch_embed_fused, PatchGemmArgs): out row m + m / np + 1 = fp16(acc + bias + pos_mult pos[1 + m % np])
+// and, with stats_part, the slice statistics of EPI_RESID_F16_STATS for the stored rows
+constexpr int EPI_PATCH_F16_STATS = 11;
 
 struct GemmArgs {
   const _Float16* a;
@@ -164,6 +168,50 @@ __device__ __forceinline__ float sum8_dpp(float v) {
   return v;
 }
 
+// (mean, sum of squared deviations from that mean) of the 64 STORED fp16 values of one row slice, 8 per lane over the
+// 8 lanes of a 128-B line, for the next LayerNorm.  Two-pass per slice (the values are in registers) and Chan's
+// combination in the finalize kernel: a plain (sum, sum of squares) pair loses the variance to cancellation when
+// |mean| >> std (0.2 % error in rstd at mean/std = 50).
+__device__ __forceinline__ f32x2 slice_stats8(const f16x8& o) {
+  float xv[8], s1 = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    xv[e] = (float)o[e];
+    s1 += xv[e];
+  }
+  const float mean_s = sum8_dpp(s1) * (1.0f / 64.0f);
+  float m2 = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float dv = xv[e] - mean_s;
+    m2 = __builtin_fmaf(dv, dv, m2);
+  }
+  return (f32x2){mean_s, sum8_dpp(m2)};
+}
+
+// Patch rows -> token rows for a block of rows that starts at m0w (which may lie past M on a ragged tile): ONE exact
+// division per block, at the block's first row clamped into M, then a small non-negative offset from it per row (a
+// reciprocal estimate with an exact fix-up).  Offsets are never taken from an unclamped first row.
+struct PatchRowMap {
+  int mb, bi0, rem0, np;
+  float inv;
+  __device__ __forceinline__ PatchRowMap() : mb(0), bi0(0), rem0(0), np(1), inv(1.f) {}
+  __device__ __forceinline__ PatchRowMap(int64_t m0w, int64_t mtot, int np_) : np(np_) {
+    mb = (int)(m0w < mtot ? m0w : mtot - 1);
+    bi0 = mb / np;
+    rem0 = mb - bi0 * np;
+    inv = 1.0f / (float)np;
+  }
+  // image bi and patch pi of row min(m, M - 1), m >= m0w
+  __device__ __forceinline__ void map(int64_t m, int64_t mtot, int& bi, int& pi) const {
+    const int r = rem0 + ((int)(m < mtot ? m : mtot - 1) - mb);
+    int q = (int)((float)r * inv);
+    q += ((q + 1) * np <= r) ? 1 : 0;
+    q -= (q * np > r) ? 1 : 0;
+    bi = bi0 + q;
+    pi = r - q * np;
+  }
+};
 
 // LDS-transposing epilogue of both persistent kernels, for a 16x16x32 accumulator block acc[NTW n-tiles][MTH m-tiles
 // from mt0, of MTT]: (16 NTW) features x (16 MTH) rows, transposed through `region` (16 MTH rows x 128 B, private to
@@ -171,15 +219,16 @@ __device__ __forceinline__ float sum8_dpp(float v) {
 // 128 x 64 wave tile), the 128 x 192 kernel at <4, 6, 3> (one 48-row half of its 64 x 96 wave tile): ONE body, so
 // the two kernels round the same fp32 value once and store the same bits (test_gemm_big_and_mid_kernels_same_bits;
 // the tail split of launch_gemm_big sends rows of one matrix through both).
-template <int EPI, bool FULL, int NTW, int MTT, int MTH>
-__device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const f32x4 (&acc)[NTW][MTT], int mt0,
+template <int EPI, bool FULL, int NTW, int MTT, int MTH, class GA>
+__device__ __forceinline__ void gemm_epilogue_lds_impl(const GA& g, const f32x4 (&acc)[NTW][MTT], int mt0,
                                                        char* region, int64_t m0w, int nbase, int lane) {
   constexpr bool kLn = (EPI == EPI_LN_BIAS_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kGelu = (EPI == HCIR_EPI_BIAS_GELU_F16 || EPI == EPI_LN_BIAS_GELU_F16);
   constexpr bool kResidH = (EPI == HCIR_EPI_BIAS_RESID_F16 || EPI == EPI_RESID_F16_STATS);
   constexpr bool kDual = (EPI == EPI_BIAS_F16_DUAL_GELU);
+  constexpr bool kPatch = (EPI == EPI_PATCH_F16_STATS);
   constexpr bool kF16 = (EPI == HCIR_EPI_BIAS_F16 || kGelu || kLn ||
-                         EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH || kDual);
+                         EPI == HCIR_EPI_AFFINE_RELU_F16 || kResidH || kDual || kPatch);
   constexpr bool kAffine = (EPI == HCIR_EPI_AFFINE_RELU_F16 || EPI == HCIR_EPI_AFFINE_F32);
   constexpr int FPP = kF16 ? 64 : 32;      // output features (128 B) per pass
   constexpr int NPASS = NTW * 16 / FPP;
@@ -242,6 +291,10 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const 
 #pragma unroll
     for (int t = 0; t < NTW; ++t) c1a[t] = *reinterpret_cast<const f32x4*>(g.ln_c1 + nbase + 16 * t + 4 * (lane >> 4));
   }
+  // patch embedding: image / patch index of a row of this block, mapped where it is used (a few VALU instructions
+  // per row; kept in registers through the epilogue the twelve values spilled the stage offsets of the main loop)
+  PatchRowMap rm;
+  if constexpr (kPatch) rm = PatchRowMap(m0w, g.m, g.np);
   // (Issuing the next tile's first stage from here, behind these constant loads and with vmcnt(8), instead of from
   // inside the tile's last k-step - so that this wait does not sit out the rest of the stage's round trip - was
   // measured: 3-5 % SLOWER on every shape, tools/ab_gemm.py; like the early-issue main loop, DESIGN.md "GEMM round 2".)
@@ -283,6 +336,14 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const 
     for (int mt = 0; mt < MTH; ++mt) {
       const int row = mt * 16 + r16;
       if constexpr (kF16) {
+        f32x4 posA[kPatch ? 4 : 1];
+        if constexpr (kPatch) {
+          int bi, pi;
+          rm.map(m0w + row, g.m, bi, pi);
+          const float* prow = g.pos + (int64_t)(1 + pi) * g.n + nbase + 64 * pass + 4 * q16;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) posA[q] = *reinterpret_cast<const f32x4*>(prow + 16 * q);
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {   // 64 features per pass = 4 n-tiles of 16
           const int nt = 4 * pass + q;
@@ -299,6 +360,8 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const 
               x = fmaxf(__builtin_fmaf(x, scaleA[nt][e], bb), 0.f);
             } else if constexpr (kResidH) {
               x = scaleA[nt][e] * (x + bb);
+            } else if constexpr (kPatch) {
+              x = __builtin_fmaf(g.pos_mult, posA[q][e], x + bb);
             } else {
               x += bb;
             }
@@ -359,34 +422,23 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const 
             o = v + oldh[u];
           else
             o = v;
-          const int64_t m = m0w + row;
+          int64_t m = m0w + row;
+          const int64_t mrow = m;
+          if constexpr (kPatch) {  // the token row: class-token rows lie between the images
+            int bi, pi;
+            rm.map(m, g.m, bi, pi);
+            m = (int64_t)bi * (g.np + 1) + 1 + pi;
+          }
           // non-temporal: the 128 KB a workgroup writes per tile would otherwise push the W panels out of the
           // XCD's L2 (W is re-fetched ~50x from the Infinity Cache per qkv launch); +1.4 % end to end
-          if (FULL || m < g.m)
+          if (FULL || mrow < g.m)
             __builtin_nontemporal_store(
                 o, reinterpret_cast<f16x8*>(static_cast<_Float16*>(second ? g.out2 : g.out) + m * g.ldo + n));
-          if constexpr (EPI == EPI_RESID_F16_STATS) {
-            // (mean, sum of squared deviations from that mean) of the 64 STORED fp16 values of this row slice,
-            // for the next LayerNorm.  Two-pass per slice (the values are in registers) and Chan's combination
-            // in the finalize kernel: a plain (sum, sum of squares) pair loses the variance to cancellation
-            // when |mean| >> std (0.2 % error in rstd at mean/std = 50).
-            float xv[8], s1 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              xv[e] = (float)o[e];
-              s1 += xv[e];
-            }
-            const float mean_s = sum8_dpp(s1) * (1.0f / 64.0f);
-            float m2 = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float dv = xv[e] - mean_s;
-              m2 = __builtin_fmaf(dv, dv, m2);
-            }
-            m2 = sum8_dpp(m2);
-            if (rchunk == 0 && (FULL || m < g.m)) {
+          if constexpr (EPI == EPI_RESID_F16_STATS || kPatch) {
+            const f32x2 ss = slice_stats8(o);
+            if (rchunk == 0 && (FULL || mrow < g.m) && (!kPatch || g.stats_part)) {
               const int64_t slice = (nbase >> 6) + pass;
-              *reinterpret_cast<f32x2*>(g.stats_part + (slice * (g.stats_ld ? g.stats_ld : g.m) + m) * 2) = (f32x2){mean_s, m2};
+              *reinterpret_cast<f32x2*>(g.stats_part + (slice * (g.stats_ld ? g.stats_ld : g.m) + m) * 2) = ss;
             }
           }
         }
@@ -436,8 +488,8 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmArgs& g, const 
 // 1.6-1.9 TB/s effective on the fp16 outputs).  The fp32 outputs take bias / residual on the row-contiguous side.
 // [16 MTH rows][128 B] image, 16-B chunks XOR-swizzled with row & 7.
 // Full blocks (all 16 MTH rows inside M) take a branch-free path.
-template <int EPI, int NTW, int MTT, int MTH>
-__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs& g, const f32x4 (&acc)[NTW][MTT], int mt0,
+template <int EPI, int NTW, int MTT, int MTH, class GA>
+__device__ __forceinline__ void gemm_epilogue_lds(const GA& g, const f32x4 (&acc)[NTW][MTT], int mt0,
                                                   char* region, int64_t m0w, int nbase, int lane) {
   // opaque lane id: the epilogue's ~60 loop-invariant LDS / global addresses all derive from it, so hipcc
   // cannot hoist them out of the persistent tile loop into long-lived registers
@@ -1019,6 +1071,184 @@ __global__ void cls_row_kernel(const float* __restrict__ cls, const float* __res
   tok[bi * t * (int64_t)d + n] = (TokT)(cls[n] + pos_mult * pos[n]);
 }
 
+// ---------------------------------------------------------------------------
+// Patch embedding on the persistent 256 x 256 tile engine (hcir_patch_embed_fused; route: patch_plan.h): the geometry,
+// LDS image, MFMA loop, tile order and epilogue body of gemm_f16_big_kernel.  The W rows of a stage go by LDS-DMA
+// exactly as GemmStages issues them; the activation rows have no fp16 source to transfer, so every thread GATHERS its
+// four 16-B slots (8 pixels of one image row = two f32x4 loads each) from the fp32 NCHW image into registers one stage
+// ahead - where the DMA pieces go out - and converts and writes them into the next slot behind the step's MFMAs.
+// With d / 256 n-tiles the image is read from L2 and converted d / 256 times (ViT-B: 3) instead of d / 128 times.
+// GEMM view: m = b * np patch rows, n = d, k = c * 256; out row = token row (EPI_PATCH_F16_STATS).
+// ---------------------------------------------------------------------------
+struct PatchGemmArgs : GemmArgs {
+  const float* img;
+  const float* pos;
+  float pos_mult;
+  int np, gw, c, h, w_px;
+};
+
+__global__ __launch_bounds__(512, 2) void patch_embed_big_kernel(PatchGemmArgs g, int tiles_n, int tiles_m) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * G256::STAGE_BYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_n = wave / G256::WAVES_M, wave_m = wave % G256::WAVES_M;
+  GemmStages<G256> stg(g, lds, tiles_n, tiles_m, tid);
+  const int nkc = stg.nkc, nsteps = stg.nsteps;
+  constexpr int NA = G256::NLOAD - G256::NW;  // activation slots per thread and stage: rows (tid >> 3) + 64 i, chunk tid & 7
+
+  // image origin of the NA patch rows this thread gathers for the tile being issued: channel 0, the patch's image
+  // row ky = chunk >> 1 (a 64-wide k chunk is image rows 4 (kc & 3) .. + 3 of channel kc >> 2), column 8 (chunk & 1);
+  // 32-bit byte offsets from the image of the tile's first row (wave-uniform; patch_plan.h bounds a tile's span)
+  const char* ibase = nullptr;
+  uint32_t aoff[NA];
+  auto set_rows = [&](int t_i) {
+    int n0;
+    int64_t m0;
+    stg.tile_origin(t_i, n0, m0);
+    int otid = tid;
+    asm volatile("" : "+v"(otid));  // (as GemmStages::set_sources: nothing of this hoisted out of the tile loop)
+    const int chunk = otid & 7;
+    const int bfirst = (int)m0 / g.np;  // (patch_plan.h: b * T < 2^31; m0 < M)
+    ibase = reinterpret_cast<const char*>(g.img + (int64_t)bfirst * g.c * g.h * g.w_px);
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      int64_t m = m0 + (otid >> 3) + 64 * i;
+      m = m < g.m ? m : g.m - 1;
+      const int mi = (int)m;
+      const int bi = mi / g.np, pi = mi - bi * g.np;
+      const int py = pi / g.gw, px = pi - py * g.gw;
+      aoff[i] = (uint32_t)((((bi - bfirst) * g.c * g.h + py * 16 + (chunk >> 1)) * g.w_px + px * 16 + 8 * (chunk & 1)) * 4);
+    }
+  };
+  f32x4 stage_a[2 * NA];
+  auto gather_load = [&](int kc) {
+    const char* kbase = ibase + ((int64_t)(kc >> 2) * g.h + 4 * (kc & 3)) * g.w_px * 4;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      stage_a[2 * i] = *reinterpret_cast<const f32x4*>(kbase + aoff[i]);
+      stage_a[2 * i + 1] = *reinterpret_cast<const f32x4*>(kbase + aoff[i] + 16);
+    }
+  };
+  auto gather_store = [&](int slot) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      f16x8 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[e] = (_Float16)stage_a[2 * i][e];
+        v[4 + e] = (_Float16)stage_a[2 * i + 1][e];
+      }
+      *reinterpret_cast<f16x8*>(lds + slot * G256::STAGE_BYTES + sim_slot_off(G256::TN + (tid >> 3) + 64 * i, tid & 7)) = v;
+    }
+  };
+
+  WaveAcc acc;
+  acc.zero();
+
+  if (nsteps > 0) {  // the whole first stage, into slot 0
+    stg.set_sources(0);
+    set_rows(0);
+    gather_load(0);
+#pragma unroll
+    for (int i = 0; i < G256::NW; ++i) stg.issue_piece(0, i);
+    gather_store(0);
+    stg.issue_advance();
+    if (stg.issue_kc == 0 && stg.issue_ti < stg.my_tiles) set_rows(stg.issue_ti);
+  }
+
+  int kc = 0, ti = 0;
+  for (int step = 0; step < nsteps; ++step) {
+    // stage `step` has landed: the W pieces (DMA) and every wave's converted activation slots (LDS writes)
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const char* st = lds + (step & 1) * G256::STAGE_BYTES;
+    const bool do_issue = step + 1 < nsteps;
+    const int islot = (step + 1) & 1;
+    const int r16 = lane & 15, kq = lane >> 4;
+    if (do_issue) gather_load(stg.issue_kc);  // in flight under the whole step
+#pragma unroll
+    for (int ks2 = 0; ks2 < 2; ++ks2) {
+      const int chunk = 4 * ks2 + kq;
+      u32x4 bf[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        bf[mt] = *reinterpret_cast<const u32x4*>(st + sim_slot_off(G256::TN + wave_m * 64 + mt * 16 + r16, chunk));
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        u32x4 af[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          af[q] = *reinterpret_cast<const u32x4*>(
+              st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
+        if (do_issue && ks2 == 0 && half == 0) {  // the four W pieces of stage step+1
+#pragma unroll
+          for (int i = 0; i < G256::NW; ++i) stg.issue_piece(islot, i);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt)
+            acc.a[4 * half + q][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                __builtin_bit_cast(f16x8, af[q]), __builtin_bit_cast(f16x8, bf[mt]), acc.a[4 * half + q][mt],
+                0, 0, 0);
+      }
+    }
+    if (do_issue) {
+      // slot islot was last read in step - 1: every wave has passed this step's barrier since
+      gather_store(islot);
+      stg.issue_advance();
+      if (stg.issue_kc == 0 && stg.issue_ti < stg.my_tiles) set_rows(stg.issue_ti);
+    }
+
+    if (++kc == nkc) {
+      int n0;
+      int64_t m0;
+      stg.tile_origin(ti, n0, m0);
+      // as gemm_f16_big_kernel: slot step&1 is free after this barrier, 8 KB of it per wave.  Rows are counted from
+      // the TILE's first row (m0 + 64 wave_m may lie past M on the ragged tile: the epilogue clamps before it maps)
+      __builtin_amdgcn_s_barrier();
+      gemm_epilogue_lds<EPI_PATCH_F16_STATS, 8, 4, 4>(g, acc.a, 0, lds + (step & 1) * G256::STAGE_BYTES + wave * 8192,
+                                                      m0 + wave_m * 64, n0 + wave_n * 128, lane);
+      acc.zero();
+      kc = 0;
+      ++ti;
+      if (stg.issue_ti < stg.my_tiles) {
+        stg.set_sources(stg.issue_ti);
+        set_rows(stg.issue_ti);
+      }
+    }
+  }
+}
+
+// Class-token rows of hcir_patch_embed_fused: tok[bi][0] = fp16(cls + pos_mult pos[0]) and the slice statistics of the
+// stored values; one thread per 8 features, the 8 lanes of a 64-feature slice side by side (slice_stats8).  d % 64 == 0.
+__global__ __launch_bounds__(256) void cls_row_stats_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
+                                                            float pos_mult, int64_t b, int t, int d,
+                                                            _Float16* __restrict__ tok, float* __restrict__ stats_part) {
+  const int per = d >> 3;
+  const int64_t total = b * per;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool inside = i < total;
+  i = inside ? i : total - 1;  // (every lane of a wave takes part in the 8-lane sums)
+  const int64_t bi = i / per;
+  const int n = (int)(i - bi * per) * 8;
+  f16x8 o;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const f32x4 cv = *reinterpret_cast<const f32x4*>(cls + n + 4 * j);
+    const f32x4 pv = *reinterpret_cast<const f32x4*>(pos + n + 4 * j);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[4 * j + e] = (_Float16)__builtin_fmaf(pos_mult, pv[e], cv[e]);
+  }
+  const f32x2 ss = slice_stats8(o);
+  if (!inside) return;
+  const int64_t row = bi * t;
+  *reinterpret_cast<f16x8*>(tok + row * d + n) = o;
+  if (stats_part && (threadIdx.x & 7) == 0)
+    *reinterpret_cast<f32x2*>(stats_part + ((int64_t)(n >> 6) * (b * t) + row) * 2) = ss;
+}
+
 // (mean, M2) of the 64-feature slices of hcir_gemm_f16_fused -> (mean, rstd) per row by Chan's parallel-variance
 // combination (equal slice sizes), slices visited in index order: deterministic, no cancellation
 __global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int parts, int64_t m, float slice_n,
@@ -1199,6 +1429,21 @@ int hcir_gemm_f16_fused(const void* a, int64_t lda, const void* w, int64_t ldw, 
   return HCIR_OK;
 }
 
+int hcir_gemm_f16_ln_rows(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m,
+                          int32_t n, int32_t k, void* out, int64_t ldo, const float* ln_stats, const float* ln_c1,
+                          void* stream) {
+  HCIR_ENTER();
+  if (!a || !w || !out || !bias || !ln_stats || !ln_c1 || m <= 0 || n <= 0 || k <= 0) return HCIR_ERR_INVALID;
+  if (lda < k || ldw < k || (lda & 7) || (ldw & 7) || ldo < n || (ldo & 7)) return HCIR_ERR_INVALID;
+  if (k % 64 || n % GMid::TN) return HCIR_ERR_UNSUPPORTED;
+  if ((n / GMid::TN) * hcir_cdiv(m, GMid::TM) > 0x7fffffff) return HCIR_ERR_INVALID;
+  GemmArgs g{static_cast<const _Float16*>(a), static_cast<const _Float16*>(w), bias, nullptr, out, m,
+             lda, ldw, ldo, n, k, ln_stats, ln_c1, nullptr, out, nullptr};
+  launch_gemm_mid<EPI_LN_BIAS_F16>(g, static_cast<hipStream_t>(stream));
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
 int hcir_ln_stats_finalize(const float* stats_part, int32_t slices, int64_t m, int32_t n_features, float eps,
                            float* ln_stats, void* stream) {
   HCIR_ENTER();
@@ -1243,6 +1488,54 @@ int hcir_patch_embed(const float* img, int64_t b, int32_t c, int32_t h, int32_t 
     hipLaunchKernelGGL(cls_row_kernel<_Float16>, cgrid, dim3(256), 0, st, cls, pos, pos_mult, b, np + 1, d,
                        static_cast<_Float16*>(tok));
   }
+  HCIR_LAUNCH_CHECK();
+  return HCIR_OK;
+}
+
+int hcir_patch_embed_route(int64_t b, int32_t c, int32_t h, int32_t w_px, int32_t p, int32_t d, int64_t ldw,
+                           int tok_dtype) {
+  if (b <= 0 || c <= 0 || h <= 0 || w_px <= 0 || p <= 0 || d <= 0 || h % p || w_px % p) return HCIR_ERR_INVALID;
+  return patch_embed_plan(b, c, h, w_px, p, d, ldw, tok_dtype).route;
+}
+
+int hcir_patch_embed_fused(const float* img, int64_t b, int32_t c, int32_t h, int32_t w_px, int32_t p,
+                           const void* w_f16, int64_t ldw, const float* bias, const float* cls, const float* pos,
+                           float pos_mult, int32_t d, void* tok, int tok_dtype, float* stats_part, void* stream) {
+  HCIR_ENTER();
+  if (!img || !w_f16 || !bias || !cls || !pos || !tok || b <= 0) return HCIR_ERR_INVALID;
+  if (p <= 0 || p > 32 || c <= 0 || h <= 0 || w_px <= 0 || h % p || w_px % p || d <= 0 || (d & 7))
+    return HCIR_ERR_INVALID;
+  if (tok_dtype != HCIR_F32 && tok_dtype != HCIR_F16) return HCIR_ERR_UNSUPPORTED;
+  const PatchPlan q = patch_embed_plan(b, c, h, w_px, p, d, ldw, tok_dtype);
+  if (q.route != HCIR_PATCH_ROUTE_BIG) return HCIR_ERR_UNSUPPORTED;
+  PatchGemmArgs g{};
+  g.a = nullptr;
+  g.w = static_cast<const _Float16*>(w_f16);
+  g.bias = bias;
+  g.scale = nullptr;
+  g.out = tok;
+  g.m = q.rows;
+  g.lda = 0;
+  g.ldw = ldw;
+  g.ldo = d;
+  g.n = d;
+  g.k = c * 256;
+  g.stats_part = stats_part;
+  g.resid = tok;
+  g.stats_ld = b * q.t;
+  g.img = img;
+  g.pos = pos;
+  g.pos_mult = pos_mult;
+  g.np = q.np;
+  g.gw = w_px / 16;
+  g.c = c;
+  g.h = h;
+  g.w_px = w_px;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(patch_embed_big_kernel, dim3(q.grid), dim3(G256::NT), 0, st, g, q.tn, q.tm);
+  HCIR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cls_row_stats_kernel, dim3((unsigned)hcir_cdiv(b * (d >> 3), 256)), dim3(256), 0, st, cls, pos,
+                     pos_mult, b, q.t, d, static_cast<_Float16*>(tok), stats_part);
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

@@ -25,6 +25,8 @@ EPI_BIAS_F16, EPI_BIAS_GELU_F16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_AFFINE_RE
     EPI_BIAS_RESID_F16 = range(7)
 GEMM_ROUTE_SMALL, GEMM_ROUTE_MID, GEMM_ROUTE_BIG, GEMM_ROUTE_SPLIT = range(4)   # hcir_gemm_route
 GEMM_ROUTE_EPI_DUAL = 10
+PATCH_ROUTE_TILE128, PATCH_ROUTE_BIG = range(2)   # hcir_patch_embed_route
+ERR_UNSUPPORTED = -2
 
 _lib = None
 
@@ -60,9 +62,13 @@ SIGNATURES = {
     "hcir_gemm_route": (c_int, [c_i64, c_i32, c_i32, c_int, c_vp]),
     "hcir_gemm_f16_fused": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_int,
                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_gemm_f16_ln_rows": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "hcir_ln_stats_finalize": (c_int, [c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "hcir_patch_embed": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp,
                                  c_f32, c_i32, c_vp, c_int, c_vp]),
+    "hcir_patch_embed_route": (c_int, [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_int]),
+    "hcir_patch_embed_fused": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                       c_f32, c_i32, c_vp, c_int, c_vp, c_vp]),
     "hcir_attn_fwd": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp]),
     "hcir_cls_head": (c_int, [c_vp, c_int, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_int, c_vp, c_vp, c_vp]),
     "hcir_patch_mean": (c_int, [c_vp, c_int, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),

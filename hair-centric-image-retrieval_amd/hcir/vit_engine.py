@@ -158,6 +158,9 @@ class VitEngine:
             bufs = dict(
                 tok=torch.empty((b, t, d), dtype=self.resid_dtype, device=dev),
                 ln=torch.empty((m, d), dtype=torch.float16, device=dev),
+                # (the CLS-only last block writes Q for the class rows only; the attention kernel's first query tile
+                # loads, never stores, the Q rows behind them: an earlier block has written those - the block's
+                # column-range launch needs the row statistics an earlier block leaves)
                 qkv=torch.empty((m, 3 * d), dtype=torch.float16, device=dev),
                 att=torch.empty((m, d), dtype=torch.float16, device=dev),
                 hid=torch.empty((m, self.mlp), dtype=torch.float16, device=dev),
@@ -168,6 +171,7 @@ class VitEngine:
                 # LayerNorm fold: partial (sum, sumsq) slices of the residual rows and their (mean, rstd)
                 stats_part=torch.empty((max(d // 64, 1), m, 2), dtype=torch.float32, device=dev),
                 stats=torch.empty((m, 2), dtype=torch.float32, device=dev),
+                stats_c=torch.empty((b, 2), dtype=torch.float32, device=dev),   # ... of the class rows
             )
             self._bufs = {k: v for k, v in self._bufs.items() if k[2] != slot}  # one shape resident per slot
             self._bufs[key] = bufs
@@ -199,10 +203,6 @@ class VitEngine:
         st = torch.cuda.current_stream(x.device).cuda_stream
         w = self._buffers(b, t, slot)
         tok, ln, qkv, att, hid = w["tok"], w["ln"], w["qkv"], w["att"], w["hid"]
-        check(L.hcir_patch_embed(x.data_ptr(), b, c, hh, ww, ps, self.conv_w.data_ptr(), self.conv_w.shape[1],
-                                 self.conv_b.data_ptr(), self.cls.data_ptr(), self.pos.data_ptr(),
-                                 self.pos_mult, d, tok.data_ptr(), self._rt, st), "hcir_patch_embed")
-        self._mark("patch_embed")
         scale = (d // self.heads) ** -0.5
         last = len(self.layers) - 1
         # LayerNorm fold: fp16 residual stream and every GEMM of the block on the persistent kernel
@@ -212,6 +212,21 @@ class VitEngine:
         sp, stats = w["stats_part"], w["stats"]
         nsl = d // 64
         have_stats = False  # `stats` holds (mean, rstd) of the current residual rows
+        kpad = self.conv_w.shape[1]
+        if fuse and L.hcir_patch_embed_route(b, c, hh, ww, ps, d, kpad, self._rt) == _lib.PATCH_ROUTE_BIG:
+            # patch embedding on the persistent tile engine: the same token bits as hcir_patch_embed.  Its row
+            # statistics are not asked for: block 0 keeps its separate ln_1 launch, because folding it would move every
+            # embedding by fp16 rounding noise against the unfolded form (4e-5 in the benchmark's similarity values)
+            check(L.hcir_patch_embed_fused(x.data_ptr(), b, c, hh, ww, ps, self.conv_w.data_ptr(), kpad,
+                                           self.conv_b.data_ptr(), self.cls.data_ptr(), self.pos.data_ptr(),
+                                           self.pos_mult, d, tok.data_ptr(), self._rt, None, st),
+                  "hcir_patch_embed_fused")
+            self._mark("patch_embed")
+        else:
+            check(L.hcir_patch_embed(x.data_ptr(), b, c, hh, ww, ps, self.conv_w.data_ptr(), kpad,
+                                     self.conv_b.data_ptr(), self.cls.data_ptr(), self.pos.data_ptr(),
+                                     self.pos_mult, d, tok.data_ptr(), self._rt, st), "hcir_patch_embed")
+            self._mark("patch_embed")
 
         def resid_gemm(a, k, wt, bias, ls, rows, pitch, want_stats, what):
             """tok rows (pitch apart) += ls o (a . wt^T + bias); want_stats (every row only): and their statistics."""
@@ -225,11 +240,21 @@ class VitEngine:
                 check(L.hcir_gemm_f16(a.data_ptr(), k, wt.data_ptr(), k, bias.data_ptr(), _ptr(ls), rows, d, k,
                                       self._resid_epi, tok.data_ptr(), pitch, st), what)
 
+        def off(tensor, elems):
+            """Device pointer of `tensor` advanced by `elems` elements (None stays None)."""
+            return None if tensor is None else tensor.data_ptr() + elems * tensor.element_size()
+
         for li, l in enumerate(self.layers):
+            # CLS-only last block with the fold on: K and V for every row = the same launch over the columns [d, 3d)
+            # (W / c1 / c2 advanced by d rows resp. elements; same kernel, same k order: the same bits); Q below.
+            # Without the fold the block's qkv launch stays whole: a class-row Q from the 128 x 128 kernel would not
+            # have the bits of the persistent kernel's
+            cls_last = cls_only_last and li == last and fuse and have_stats
+            c0 = d if cls_last else 0
             if fuse and have_stats:
-                check(L.hcir_gemm_f16_fused(tok.data_ptr(), d, l.qkv_wg.data_ptr(), d, l.qkv_c2.data_ptr(), None,
-                                            m, 3 * d, d, _lib.EPI_BIAS_F16, qkv.data_ptr(), 3 * d,
-                                            stats.data_ptr(), l.qkv_c1.data_ptr(), None, st),
+                check(L.hcir_gemm_f16_fused(tok.data_ptr(), d, off(l.qkv_wg, c0 * d), d, off(l.qkv_c2, c0), None,
+                                            m, 3 * d - c0, d, _lib.EPI_BIAS_F16, off(qkv, c0), 3 * d,
+                                            stats.data_ptr(), off(l.qkv_c1, c0), None, st),
                       "hcir_gemm_f16_fused(ln1+qkv)")
             else:
                 check(L.hcir_layernorm_f16(tok.data_ptr(), self._rt, m, d, d, l.ln1_w.data_ptr(),
@@ -237,6 +262,13 @@ class VitEngine:
                 self._mark("layernorm")
                 check(L.hcir_gemm_f16(ln.data_ptr(), d, l.qkv_w.data_ptr(), d, _ptr(l.qkv_b), None, m, 3 * d, d,
                                       _lib.EPI_BIAS_F16, qkv.data_ptr(), 3 * d, st), "hcir_gemm_f16(qkv)")
+            if cls_last:
+                # Q for the b class rows (tok[bi][0], pitch t*d -> qkv[bi*t], pitch t*3d), the only queries attention
+                # runs: the same folded form on the 128 x 192 persistent kernel, bit-identical to the whole launch's rows
+                w["stats_c"].copy_(stats.view(b, t, 2)[:, 0])
+                check(L.hcir_gemm_f16_ln_rows(tok.data_ptr(), t * d, l.qkv_wg.data_ptr(), d, l.qkv_c2.data_ptr(), b, d,
+                                              d, qkv.data_ptr(), t * 3 * d, w["stats_c"].data_ptr(),
+                                              l.qkv_c1.data_ptr(), st), "hcir_gemm_f16_ln_rows(q, class rows)")
             self._mark("gemm_qkv")
             # behind the qkv GEMM: every row of tok, or - cls_only_last, last block - the class-token rows only: row b
             # of the compact buffers <-> tok[b][0] (row pitch t*d).  The LayerNorm fold stays off for those

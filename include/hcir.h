@@ -235,6 +235,14 @@ int hcir_gemm_f16_fused(const void* a, int64_t lda, const void* w, int64_t ldw, 
                         const float* scale, int64_t m, int32_t n, int32_t k, int epilogue,
                         void* out, int64_t ldo, const float* ln_stats, const float* ln_c1,
                         float* stats_part, void* stream);
+/* The LayerNorm-folded HCIR_EPI_BIAS_F16 form of hcir_gemm_f16_fused for ANY number of rows m >= 1 (a few rows picked
+ * out of a larger matrix by their pitch lda - the class-token rows of the last ViT block), always on the persistent
+ * 128 x 192 kernel: the same k order and epilogue arithmetic as the 256 x 256 kernel, so row r of this call holds the
+ * bits that row would have in a hcir_gemm_f16_fused launch over the whole matrix.  ln_stats [m][2] belongs to the m
+ * rows of THIS call.  K % 64 == 0 and N % 128 == 0, else HCIR_ERR_UNSUPPORTED. */
+int hcir_gemm_f16_ln_rows(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int64_t m,
+                          int32_t n, int32_t k, void* out, int64_t ldo, const float* ln_stats,
+                          const float* ln_c1, void* stream);
 int hcir_ln_stats_finalize(const float* stats_part, int32_t slices, int64_t m, int32_t n_features,
                            float eps, float* ln_stats, void* stream);
 
@@ -252,6 +260,25 @@ int hcir_patch_embed(const float* img, int64_t b, int32_t c, int32_t h, int32_t 
                      int32_t p, const void* w_f16, int64_t ldw, const float* bias,
                      const float* cls, const float* pos, float pos_mult, int32_t d, void* tok,
                      int tok_dtype, void* stream);
+/* The same patch embedding on the persistent 256 x 256 tile engine of hcir_gemm_f16 (weights by LDS-DMA, the image
+ * gathered and converted once per 256-feature n-tile), for P == 16, tok_dtype == HCIR_F16, d % 256 == 0 and
+ * ldw == c * 256; every other shape returns HCIR_ERR_UNSUPPORTED with tok untouched (use hcir_patch_embed).
+ * tok: same contract as hcir_patch_embed (fp32 sum, one rounding to fp16).  stats_part (may be NULL): for EVERY
+ * token row, class-token rows included, the (mean, sum of squared deviations from it) of each 64-feature slice of
+ * the fp16 values as stored, [d / 64][b * T][2] - the producer side of the LayerNorm fold, read by
+ * hcir_ln_stats_finalize with m = b * T.
+ * hcir_patch_embed_route: which of the two a shape takes; host arithmetic only, nothing is launched.  Returns the
+ * route, or HCIR_ERR_INVALID (a size < 1, image sides no multiple of p). */
+typedef enum {
+  HCIR_PATCH_ROUTE_TILE128 = 0, /* hcir_patch_embed: 128 x 128 tiles, both operands staged through registers */
+  HCIR_PATCH_ROUTE_BIG = 1      /* hcir_patch_embed_fused: persistent 256 x 256 tiles */
+} hcir_patch_route_kind;
+int hcir_patch_embed_route(int64_t b, int32_t c, int32_t h, int32_t w_px, int32_t p, int32_t d, int64_t ldw,
+                           int tok_dtype);
+int hcir_patch_embed_fused(const float* img, int64_t b, int32_t c, int32_t h, int32_t w_px,
+                           int32_t p, const void* w_f16, int64_t ldw, const float* bias,
+                           const float* cls, const float* pos, float pos_mult, int32_t d, void* tok,
+                           int tok_dtype, float* stats_part, void* stream);
 
 /* Fused multi-head self-attention forward over packed qkv:
  *   qkv fp16 [B][T][3][H][hd]  (rows of the in_proj / qkv GEMM),
