@@ -21,6 +21,7 @@
 #include "act.h"
 #include "gemm_plan.h"
 #include "patch_plan.h"
+#include "gemm_stage_addr.h"
 #include <stdlib.h>
 
 namespace {
@@ -58,13 +59,8 @@ struct GemmArgs {
   int64_t stats_ld = 0;   // rows per slice of stats_part (0: m) - a launch over a row range of a larger matrix
 };
 
-// XCD-aware tile order: consecutive workgroup ids are dealt round-robin over the 8
-// XCDs (MI355X_MICROARCH.md §Workgroup dispatch); remap so that one XCD walks a
-// contiguous run of tiles and re-uses the W panel / A panel from its own L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, j = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
+// XCD-aware tile order (gemm_stage_addr.h)
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) { return gemm_xcd_remap(bid, nwg); }
 
 template <int EPI, int NTILES>
 __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, const f32x16 (&acc)[NTILES][2],
@@ -569,11 +565,7 @@ __device__ unsigned long long g_gemm_stamps[256 * 8];
   } while (0)
 #endif
 
-constexpr int kGemmNGroup = 3;      // tools/ab_gemm.py, batch 880: fc1 908 -> 890 us, qkv 574 -> 568 us against n
-                                    // fastest over the whole N
-constexpr int kGemmNGroupWide = 6;  // group size when it divides tiles_n (fc1: 12 n-tiles): the activation panels are
-                                    // then fetched by two XCD sets instead of four (PMC: fc1 reads x5.3 -> see DESIGN);
-                                    // time flat against 3 (profiles/r3_diag_ab_gemm_ngroup.txt), fabric bytes -20 %
+// (the n-group sizes of the 256 x 256 tile order, kGemmNGroup / kGemmNGroupWide: gemm_stage_addr.h)
 
 // Geometry of a persistent kernel: NT threads as WAVES_N x WAVES_M waves on a TN(n) x TM(m) tile; a stage is TN W
 // rows then TM activation rows of 128 B (BK = 64), filled by NLOAD 16-B LDS-DMA pieces per thread, the first NW of
@@ -605,17 +597,24 @@ struct GMid {
 // Stage issuer of both persistent kernels: which tiles this workgroup owns, where a tile lies, and the LDS-DMA
 // pieces of the next stage to issue (stages run on across tile boundaries).  The kernels keep their own MFMA loops
 // and decide where in them the pieces go out.
+//
+// Source addresses (gemm_stage_addr.h): a thread keeps TWO per-lane byte offsets for the whole kernel, `woff` for
+// its W pieces and `aoff` for its activation pieces; everything that changes from piece to piece, k-step to k-step
+// and tile to tile is wave-uniform and goes into the transfer's scalar base.  Only a ragged tile (the last row of
+// tiles, a_last < TM - 1) computes clamped per-lane offsets, when its activation pieces are issued.  A tile's origin
+// is computed ONCE, when the issuer reaches the tile (next_tile), and handed on to the epilogue (origin()).
 template <class G>
 struct GemmStages {
-  // State first, configuration after it, `issue_kc` ... `soff` in this order: hipcc numbers the loop-carried values
-  // in member order, and every other order measurably reschedules the 256 x 256 kernel (tools/cmp_device_asm.py:
-  // instruction counts move by 1-2 in all of its epilogues).
+  // State first, configuration after it: hipcc numbers the loop-carried values in member order (reordering them
+  // reschedules the 256 x 256 kernel: compare with tools/cmp_device_asm.py).  All of the state is wave-uniform; the
+  // two lane offsets are written once and sit behind the configuration they are made from.
   int issue_kc = 0, issue_ti = 0;  // next stage to issue
-  const char* wbase = nullptr;
+  const char* wbase = nullptr;     // W / activation origin of tile issue_ti
   const char* abase = nullptr;
-  // per-thread DMA source offsets of the tile being issued (row + swizzled chunk), in bytes from the
-  // tile's W / activation origin: 32-bit VGPR offsets on wave-uniform 64-bit bases (global saddr mode)
-  uint32_t soff[G::NLOAD];
+  int a_last = 0;                  // last valid activation row of tile issue_ti, from its first row; at most TM - 1
+  // origins of tiles issue_ti, issue_ti - 1, issue_ti - 2: the issuer runs one tile (at one k-step per tile, two)
+  // ahead of the tile whose epilogue comes next
+  GemmTileOrigins org;
   const GemmArgs& g;
   char* const lds;
   const int tiles_n, tiles_m, tid;
@@ -624,78 +623,97 @@ struct GemmStages {
   const int my_tiles =
       (int)blockIdx.x < ntiles ? (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
   const int nsteps = my_tiles * nkc;
+  const int wave_dst = __builtin_amdgcn_readfirstlane((tid & ~63) * 16);  // the wave's 1 KB of a piece's 8 (NT / 64) KB
+  // per-thread DMA source offsets (row tid >> 3 + swizzled chunk), in bytes: 32-bit VGPR offsets on wave-uniform
+  // 64-bit bases (global saddr mode); the same for every piece, k-step and tile
+  uint32_t woff, aoff;
 
   __device__ __forceinline__ GemmStages(const GemmArgs& g_, char* lds_, int tiles_n_, int tiles_m_, int tid_)
-      : g(g_), lds(lds_), tiles_n(tiles_n_), tiles_m(tiles_m_), tid(tid_) {}
-
-  // origin of this workgroup's ti-th tile
-  __device__ __forceinline__ void tile_origin(int ti, int& n0, int64_t& m0) const {
-    const int t = xcd_remap((int)blockIdx.x + ti * (int)gridDim.x, ntiles);
-    if constexpr (G::N_GROUPED) {
-      // n-grouped order: the W panels of one group of n-tiles stay in the XCD's L2 while every m-tile streams past
-      // them (a W set wider than the 4 MB L2 - fc1: 12 panels, 4.7 MB - is otherwise re-fetched for every row of tiles)
-      const int ngrp = (tiles_n % kGemmNGroupWide == 0 && tiles_n > kGemmNGroupWide) ? kGemmNGroupWide : kGemmNGroup;
-      if (tiles_n % ngrp == 0 && tiles_n > ngrp) {
-        const int per = ngrp * tiles_m;
-        const int grp = t / per, rem = t - grp * per;
-        n0 = (grp * ngrp + rem % ngrp) * G::TN;
-        m0 = (int64_t)(rem / ngrp) * G::TM;
-        return;
-      }
-    }
-    n0 = (t % tiles_n) * G::TN;
-    m0 = (int64_t)(t / tiles_n) * G::TM;
+      : g(g_), lds(lds_), tiles_n(tiles_n_), tiles_m(tiles_m_), tid(tid_) {
+    set_lane_offsets();
   }
 
-  __device__ __forceinline__ void set_sources(int t_i) {
-    int n0;
-    int64_t m0;
-    tile_origin(t_i, n0, m0);
-    wbase = reinterpret_cast<const char*>(g.w + (int64_t)n0 * g.ldw);
-    abase = reinterpret_cast<const char*>(g.a + m0 * g.lda);
-    // opaque thread id: the per-piece row / chunk values below are cheap to recompute once per tile; hoisted out of
-    // the tile loop they stayed live through the main loop (and were SPILLED in the dual-output variant, whose
-    // per-tile reload then waited - vmcnt(0) - for the stage in flight)
+  // The two lane offsets, from an opaque thread id.  Once per kernel; the one kernel whose epilogue has no register
+  // to spare for them (the dual-output epilogue) calls this again behind the epilogue, so that they do not live
+  // through it: six instructions.
+  __device__ __forceinline__ void set_lane_offsets() {
     int otid = tid;
     asm volatile("" : "+v"(otid));
-#pragma unroll
-    for (int i = 0; i < G::NLOAD; ++i) {
-      const int piece = otid + G::NT * i;
-      const int row = piece >> 3, chunk = (piece & 7) ^ ((row >> 1) & 7);
-      if (row < G::TN) {
-        const int nr = n0 + row > g.n - 1 ? g.n - 1 - n0 : row;
-        soff[i] = (uint32_t)(((int64_t)nr * g.ldw + chunk * 8) * 2);
-      } else {
-        int64_t mr = row - G::TN;
-        mr = m0 + mr > g.m - 1 ? g.m - 1 - m0 : mr;
-        soff[i] = (uint32_t)((mr * g.lda + chunk * 8) * 2);
-      }
+    woff = gemm_lane_off(otid, g.ldw);
+    aoff = gemm_lane_off(otid, g.lda);
+  }
+
+  // origin of this workgroup's ti-th tile, from scratch (the issuer itself: next_tile)
+  __device__ __forceinline__ void tile_origin(int ti, int& n0, int64_t& m0) const {
+    gemm_tile_origin<G::N_GROUPED, G::TN, G::TM>((int)blockIdx.x, (int)gridDim.x, ti, tiles_n, tiles_m, n0, m0);
+  }
+
+  // origin of the tile whose epilogue is due: ti == issue_ti - 1, or issue_ti - 2 when every step ends a tile
+  __device__ __forceinline__ void origin(int ti, int& n0, int64_t& m0) const {
+    int mt;
+    org.get(issue_ti - ti, n0, mt);
+    m0 = (int64_t)mt * G::TM;
+  }
+
+  // the issuer has reached tile issue_ti: its origin and bases; the origins of the two tiles before it move on
+  __device__ __forceinline__ void next_tile() {
+    org.shift();
+    if (issue_ti < my_tiles) {
+      int n0;
+      int64_t m0;
+      tile_origin(issue_ti, n0, m0);
+      org.set(n0, (int)(m0 / G::TM));
+      wbase = reinterpret_cast<const char*>(g.w + (int64_t)n0 * g.ldw);
+      abase = reinterpret_cast<const char*>(g.a + m0 * g.lda);
+      a_last = gemm_tile_last_row<G::TM>(g.m, m0);
     }
   }
 
-  __device__ __forceinline__ void issue_piece(int slot, int i) const {
+  __device__ __forceinline__ bool ragged() const { return a_last < G::TM - 1; }
+
+  template <bool RAGGED>
+  __device__ __forceinline__ void issue_piece_as(int slot, int i) const {
     // pieces 0..NW-1 are W rows, the rest activation rows (i is a constant after unrolling).  Default cache policy
     // on both operands: `nt` (aux 2) on the activation rows measured +-1 %, on the W rows -9..-13 %
     // (every CU of an XCD re-reads them from L2).  The transfer is issued outside the compiler's view (common.h
     // lds_dma16): +1.3 % over the layer against __builtin_amdgcn_global_load_lds (qkv +2.6 %)
-    lds_dma16((i < G::NW ? wbase : abase) + issue_kc * 128, soff[i],
-              lds_addr(lds) + slot * G::STAGE_BYTES + ((tid & ~63) + G::NT * i) * 16);
+    const uint32_t dst = lds_addr(lds) + slot * G::STAGE_BYTES + wave_dst + G::NT * i * 16;
+    // ragged: rows clamped to the matrix, counted from the TILE's first row, from an opaque thread id: nothing of
+    // it outlives the piece
+    int otid = tid;
+    if constexpr (RAGGED) asm volatile("" : "+v"(otid));
+    int64_t base;
+    uint32_t off;
+    gemm_piece_source<G::NT, G::NW, RAGGED>(i, otid, a_last, g.lda, g.ldw, woff, aoff, base, off);
+    lds_dma16((i < G::NW ? wbase : abase) + issue_kc * 128 + base, off, dst);
   }
+
+  // pieces i0 .. i0 + cnt - 1 (constants after unrolling); ONE wave-uniform branch where activation rows are among them
+  __device__ __forceinline__ void issue_pieces(int slot, int i0, int cnt) const {
+    if (i0 + cnt > G::NW && ragged()) {
+#pragma unroll
+      for (int i = i0; i < i0 + cnt; ++i) issue_piece_as<true>(slot, i);
+    } else {
+#pragma unroll
+      for (int i = i0; i < i0 + cnt; ++i) issue_piece_as<false>(slot, i);
+    }
+  }
+
+  __device__ __forceinline__ void issue_piece(int slot, int i) const { issue_pieces(slot, i, 1); }
 
   __device__ __forceinline__ void issue_advance() {
     if (++issue_kc == nkc) {
       issue_kc = 0;
       ++issue_ti;
-      if (issue_ti < my_tiles) set_sources(issue_ti);
+      next_tile();
     }
   }
 
   // the whole first stage, into slot 0
   __device__ __forceinline__ void issue_first() {
     if (nsteps > 0) {
-      set_sources(0);
-#pragma unroll
-      for (int i = 0; i < G::NLOAD; ++i) issue_piece(0, i);
+      next_tile();
+      issue_pieces(0, 0, G::NLOAD);
       issue_advance();
     }
   }
@@ -763,8 +781,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
           af[q] = *reinterpret_cast<const u32x4*>(
               st + sim_slot_off(wave_n * 128 + (4 * half + q) * 16 + r16, chunk));
         if (do_issue && ks2 == 0) {  // the eight DMA pieces of stage step+1 in the first 32-k substep
-#pragma unroll
-          for (int i = 0; i < 4; ++i) stg.issue_piece(islot, 4 * half + i);
+          stg.issue_pieces(islot, 4 * half, 4);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -781,7 +798,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
     if (++kc == nkc) {
       int n0;
       int64_t m0;
-      stg.tile_origin(ti, n0, m0);
+      stg.origin(ti, n0, m0);
       HCIR_GSTAMP(ti == 1, 1);
       // all waves are done reading slot step&1 (their MFMAs have consumed it) after this barrier;
       // the slot stays free until the DMA of stage step+2 is issued behind the next step's barrier.
@@ -794,10 +811,10 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_big_kernel(GemmArgs g, int ti
       acc.zero();
       kc = 0;
       ++ti;
-      // the DMA source offsets of the tile being issued are RE-DERIVED here instead of living through the epilogue:
-      // the dual-output variant spilled them, and its reload made the compiler put vmcnt(0) in front of every DMA
-      // group of the main loop (MFMA busy 39 % against 57 % for the other variants)
-      if (stg.issue_ti < stg.my_tiles) stg.set_sources(stg.issue_ti);
+      // nothing of the issuer is re-derived here: its two lane offsets are the same for every tile, and the bases and
+      // the origin of the tile being issued are scalars (eight per-piece VGPR offsets living through the epilogue
+      // were SPILLED in the dual-output variant, and the reload put vmcnt(0) in front of every DMA group)
+      if constexpr (EPI == EPI_BIAS_F16_DUAL_GELU) stg.set_lane_offsets();
     }
   }
 }
@@ -857,8 +874,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
 #pragma unroll
       for (int hq = 0; hq < 2; ++hq) {
         if (do_issue && ks2 == 0) {  // the ten DMA pieces of stage step+1 in the first 32-k substep
-#pragma unroll
-          for (int i = 0; i < 5; ++i) stg.issue_piece(islot, 5 * hq + i);
+          stg.issue_pieces(islot, 5 * hq, 5);
         }
 #pragma unroll
         for (int q = 2 * hq; q < 2 * hq + 2; ++q)
@@ -873,7 +889,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mid_kernel(GemmArgs g, int ti
     if (++kc == nkc) {
       int n0;
       int64_t m0;
-      stg.tile_origin(ti, n0, m0);
+      stg.origin(ti, n0, m0);
       // every wave is done reading slot step&1; it stays free until the DMA of stage step+2 goes out behind the
       // next step's barrier.  Per wave a private 6 KB piece of it: 48 rows x 128 B, two row halves per tile.
       __builtin_amdgcn_s_barrier();
@@ -1106,7 +1122,7 @@ __global__ __launch_bounds__(512, 2) void patch_embed_big_kernel(PatchGemmArgs g
     int64_t m0;
     stg.tile_origin(t_i, n0, m0);
     int otid = tid;
-    asm volatile("" : "+v"(otid));  // (as GemmStages::set_sources: nothing of this hoisted out of the tile loop)
+    asm volatile("" : "+v"(otid));  // (opaque: nothing of this hoisted out of the tile loop)
     const int chunk = otid & 7;
     const int bfirst = (int)m0 / g.np;  // (patch_plan.h: b * T < 2^31; m0 < M)
     ibase = reinterpret_cast<const char*>(g.img + (int64_t)bfirst * g.c * g.h * g.w_px);
@@ -1146,7 +1162,7 @@ __global__ __launch_bounds__(512, 2) void patch_embed_big_kernel(PatchGemmArgs g
   acc.zero();
 
   if (nsteps > 0) {  // the whole first stage, into slot 0
-    stg.set_sources(0);
+    stg.next_tile();
     set_rows(0);
     gather_load(0);
 #pragma unroll
@@ -1213,10 +1229,7 @@ __global__ __launch_bounds__(512, 2) void patch_embed_big_kernel(PatchGemmArgs g
       acc.zero();
       kc = 0;
       ++ti;
-      if (stg.issue_ti < stg.my_tiles) {
-        stg.set_sources(stg.issue_ti);
-        set_rows(stg.issue_ti);
-      }
+      if (stg.issue_ti < stg.my_tiles) set_rows(stg.issue_ti);
     }
   }
 }
