@@ -187,6 +187,7 @@ extern "C" int hcir_bn1d_fwd(const float* x, int64_t ldx, int64_t rows, int32_t 
                              void* stream) {
   HCIR_ENTER();
   if (!x || !gamma || !beta || !save_mean || !save_rstd || (!y_f32 && !y_f16) || rows <= 0 || f <= 0) return HCIR_ERR_INVALID;
+  if (ldx < f || (y_f32 && ldy32 < f) || (y_f16 && ldy16 < f)) return HCIR_ERR_INVALID;
   hipLaunchKernelGGL(bn1d_fwd_kernel, dim3((unsigned)hcir_cdiv(f, kBnCols)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
                      ldx, rows, f, gamma, beta, eps, momentum, relu, running_mean, running_var, save_mean, save_rstd, y_f32,
                      ldy32, static_cast<_Float16*>(y_f16), ldy16);
@@ -201,6 +202,7 @@ extern "C" int hcir_bn1d_bwd(const float* dy, int64_t lddy, const float* x, int6
   HCIR_ENTER();
   if (!dy || !x || !gamma || !save_mean || !save_rstd || !dx_f16 || !dgamma || !dbeta || rows <= 0 || f <= 0)
     return HCIR_ERR_INVALID;
+  if (lddy < f || ldx < f || lddx < f || (relu_out_f16 && ldr < f)) return HCIR_ERR_INVALID;
   hipLaunchKernelGGL(bn1d_bwd_kernel, dim3((unsigned)hcir_cdiv(f, kBnCols)), dim3(256), 0, static_cast<hipStream_t>(stream), dy,
                      lddy, x, ldx, rows, f, gamma, save_mean, save_rstd, static_cast<const _Float16*>(relu_out_f16), ldr,
                      dy_scale, static_cast<_Float16*>(dx_f16), lddx, dgamma, dbeta);

@@ -568,13 +568,16 @@ int hcir_positive_transform(const float* images, int64_t b, int32_t c, int32_t h
 /* BatchNorm1d in TRAINING mode over x fp32 [rows][f] (lightly SimCLRProjectionHead, HP/src/main_backbone.py:589):
  * batch mean / biased variance, y = (x - mean) rstd gamma + beta (+ ReLU), running statistics updated with `momentum`
  * and the unbiased variance as torch does (running_* may be NULL).  Outputs y_f32 and / or y_f16 (one may be NULL);
- * save_mean / save_rstd [f] are kept for the backward. */
+ * save_mean / save_rstd [f] are kept for the backward.  ldx, ldy32, ldy16: row pitches in elements; a pitch of a
+ * non-NULL operand below f is HCIR_ERR_INVALID (checked on the host, before the launch). */
 int hcir_bn1d_fwd(const float* x, int64_t ldx, int64_t rows, int32_t f, const float* gamma, const float* beta,
                   float eps, float momentum, int relu, float* running_mean, float* running_var, float* save_mean,
                   float* save_rstd, float* y_f32, int64_t ldy32, void* y_f16, int64_t ldy16, void* stream);
 /* Its backward: dx (fp16 [rows][f], the operand of the dgrad / wgrad GEMMs in front), dgamma, dbeta [f].
  * relu_out_f16 (optional): the forward's fp16 ReLU output; the incoming gradient is zero where it is <= 0.
- * dy_scale (optional DEVICE scalar): dy is multiplied by it first (the caller's power-of-two renormalisation). */
+ * dy_scale (optional DEVICE scalar): dy is multiplied by it first (the caller's power-of-two renormalisation);
+ * dgamma and dbeta are sums of the scaled, masked gradient.  lddy, ldx, lddx and, with relu_out_f16, ldr below f:
+ * HCIR_ERR_INVALID before the launch. */
 int hcir_bn1d_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int32_t f,
                   const float* gamma, const float* save_mean, const float* save_rstd, const void* relu_out_f16,
                   int64_t ldr, const float* dy_scale, void* dx_f16, int64_t lddx, float* dgamma, float* dbeta,
