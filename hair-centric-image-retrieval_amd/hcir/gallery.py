@@ -1,7 +1,7 @@
 """hcir.gallery — a gallery resident in HBM and the "exact by verification" search.
 
 `ResidentGallery(g32)` keeps the fp32 rows (the reference's gallery) and, optionally, an fp16
-MIRROR of them.  `search(q, k)` returns exactly what the exact fp32 scan returns — same indices,
+MIRROR of them (fp16 only: the bound below is that of an fp16 rounding).  `search(q, k)` returns exactly what the exact fp32 scan returns — same indices,
 bit-identical scores — but streams only the half-size mirror for (almost) every query:
 
   1. filter   hcir_sim_topk(fp16 q, fp16 mirror, kc = 16)            HBM-streaming / fp16 MFMA
@@ -39,6 +39,10 @@ class ResidentGallery:
         ops._dev(g32, "gallery")
         if g32.dtype != torch.float32 or g32.dim() != 2:
             raise HcirError("ResidentGallery expects an fp32 [N, D] tensor")
+        if mirror not in (None, torch.float16):
+            # the refine kernel derives ||q - q~|| from an fp16 rounding of the query: with any other mirror
+            # its E_i is not a bound, and the certificate would be unsound
+            raise HcirError(f"ResidentGallery: the mirror is fp16 or None, not {mirror}")
         self.g32 = g32
         self.idx_base = int(idx_base)
         self.mirror = None

@@ -98,8 +98,21 @@ int hcir_sim_topk(const void* q, int64_t nq, const void* g, int64_t ng, int32_t 
  * the candidate set can belong to the exact top-k, given |exact - mirror score| <= err_bound[i].
  * err_bound is a device array [nq], or NULL: then E_i is computed in the kernel from the HOST array
  * mirror_consts = {max_j ||g_j - g~_j||, max_j ||g~_j||, max_j ||g_j||, gamma_d} of an fp16 mirror
- * (derivation: hcir/gallery.py).  The caller re-runs uncertified queries through
- * hcir_sim_topk(HCIR_F32). */
+ * (derivation: hcir/gallery.py).  The mirror is fp16 and nothing else: the kernel takes ||q - q~||
+ * from an fp16 rounding of q, so with a bf16 mirror E_i would not be a bound.  The caller re-runs
+ * uncertified queries through hcir_sim_topk(HCIR_F32).
+ * Pinned by tests/test_refine_gpu.py against oracle/refine.py, bit for bit:
+ *   - candidate indices are TRUSTED: an index >= 0 must satisfy idx_base <= index < idx_base + ng
+ *     (ng itself is not used, no range check is made); an index < 0 is an empty slot;
+ *   - g_inv_norm is indexed by index - idx_base, q_inv_norm by the query;
+ *   - a candidate whose score is NaN never ranks: it is dropped like an empty slot;
+ *   - equal scores rank by index ascending;
+ *   - with v valid candidates, v < k, slots [v, k) hold -inf / -1;
+ *   - certified[i] = 1 when cand_idx[i][kc-1] < 0 (the filter returned every row it has);
+ *     otherwise k valid candidates must exist and fl32(cand_val[i][kc-1] + E_i) < the k-th score,
+ *     strictly: equality is not certified, and a NaN or infinite E_i certifies nothing.
+ * Returns HCIR_ERR_INVALID, before any launch, for d % 8 != 0, kc > 64, k > kc, nq <= 0, or
+ * err_bound and mirror_consts both NULL. */
 int hcir_topk_refine_f32(const float* q, int64_t nq, const float* g, int64_t ng, int32_t d,
                          const int64_t* cand_idx, const float* cand_val, int32_t kc, int32_t k,
                          int64_t idx_base, const float* q_inv_norm, const float* g_inv_norm,
