@@ -68,15 +68,17 @@ def chunk(kind: bytes, payload: bytes) -> bytes:
 
 def write_png(img: np.ndarray, color_type: int, filters: Union[int, Sequence[int]] = 0,
               plan: Optional[Sequence[tuple]] = None, level: int = 6, idat_sizes: Optional[Sequence[int]] = None,
-              palette: Optional[np.ndarray] = None, extra_chunks: Sequence[bytes] = ()) -> bytes:
-    """img [h, w, channels(color_type)] uint8 -> PNG file bytes, 8-bit, non-interlaced."""
+              palette: Optional[np.ndarray] = None, extra_chunks: Sequence[bytes] = (),
+              zstream: Optional[bytes] = None) -> bytes:
+    """img [h, w, channels(color_type)] uint8 -> PNG file bytes, 8-bit, non-interlaced.
+    zstream: a ready zlib stream (deflate_writer.py) that goes into the IDATs unchanged instead of the compressed
+    scanlines of `img`, which then only gives the IHDR its size; `idat_sizes` cuts it wherever it says."""
     if img.ndim == 2:
         img = img[:, :, None]
     h, w, c = img.shape
     assert c == CHANNELS[color_type] and img.dtype == np.uint8
     fl: List[int] = [filters] * h if isinstance(filters, int) else list(filters)
-    raw = filter_rows(img, fl)
-    z = deflate_segments(raw, plan or [(None, "dynamic", level)])
+    z = zstream if zstream is not None else deflate_segments(filter_rows(img, fl), plan or [(None, "dynamic", level)])
     out = b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, color_type, 0, 0, 0))
     for e in extra_chunks:
         out += e

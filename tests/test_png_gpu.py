@@ -108,7 +108,8 @@ def test_live_pillow_sweep(hcir_built):
 
 @pytest.mark.parametrize("count", [256, 704])
 def test_big_batches_and_determinism(streams, hcir_built, count):
-    """256 files: three wavefronts per image (lookup | decoder | copier); 704 files: the full-chip form, two per image."""
+    """256 and 704 files (more than the chip holds at once): the launch is three wavefronts per image (lookup |
+    decoder | copier, dim3(192)) at every batch size."""
     names, files, wins = streams
     order = np.random.default_rng(2).integers(0, len(files), count)
     batch = [files[i] for i in order]
