@@ -14,13 +14,11 @@
 //                   into an online (max, sum-of-exp2) pair; diagonal skipped, positive captured.
 //   ntxent_rows   : one thread per row merges the per-column-tile partials in tile order
 //                   (deterministic), writes row_lse and the row's loss term.
-//   ntxent_reduce : one workgroup sums the 2B loss terms in a fixed tree -> mean loss.
-#include "sim_core.h"
+//   pair_mean_reduce (pair_tiles.h): one workgroup sums the 2B loss terms in a fixed tree -> mean loss.
+// The tile main loop and the online merge are pair_tiles.h, shared with supcon.hip.
+#include "pair_tiles.h"
 
 namespace {
-
-constexpr float kLog2e = 1.44269504088896340736f;
-constexpr float kLn2 = 0.69314718055994530942f;
 
 template <typename T>
 __global__ __launch_bounds__(256) void ntxent_prep(const T* __restrict__ z0, const T* __restrict__ z1,
@@ -55,48 +53,16 @@ struct NtArgs {
 
 template <typename T, bool GLDS, bool BWD = false>
 __global__ __launch_bounds__(256, 2) void ntxent_tiles(NtArgs a) {
-  using Cfg = SimCfg<T, 2, 2, 2>;  // 128 column rows streamed x 128 logits rows resident
-  constexpr int EPS = SimElem<T>::kPerStage;
+  using Cfg = PairCfg<T>;
   __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_c = wave >> 1, wave_r = wave & 1;
   const int r = lane & 31, h = lane >> 5;
   const T* zn = static_cast<const T*>(a.zn);
   const int64_t c0 = (int64_t)blockIdx.x * 128, r0 = (int64_t)blockIdx.y * 128;
-  const int nkc = (a.d + EPS - 1) / EPS;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[x][y][i] = 0.f;
-
-  if constexpr (GLDS) {
-    sim_stage_glds<T, Cfg>(lds, zn, c0, a.n - 1, zn, r0, a.n - 1, a.d, 0, tid);
-    for (int kc = 0; kc < nkc; ++kc) {
-      const int cur = kc & 1;
-      sim_glds_retire_and_sync();
-      if (kc + 1 < nkc)
-        sim_stage_glds<T, Cfg>(lds + (cur ^ 1) * Cfg::STAGE_BYTES, zn, c0, a.n - 1, zn, r0, a.n - 1, a.d,
-                               kc + 1, tid);
-      sim_stage_mfma<T, Cfg, 2>(acc, lds + cur * Cfg::STAGE_BYTES, wave_c, wave_r, lane);
-    }
-  } else {
-    u32x4 regs[Cfg::NLOAD];
-    sim_stage_load<T, Cfg>(regs, zn, c0, a.n - 1, zn, r0, a.n - 1, a.d, 0, tid);
-    sim_stage_store<Cfg>(regs, lds, tid);
-    __syncthreads();
-    for (int kc = 0; kc < nkc; ++kc) {
-      const int cur = kc & 1;
-      if (kc + 1 < nkc) sim_stage_load<T, Cfg>(regs, zn, c0, a.n - 1, zn, r0, a.n - 1, a.d, kc + 1, tid);
-      sim_stage_mfma<T, Cfg, 2>(acc, lds + cur * Cfg::STAGE_BYTES, wave_c, wave_r, lane);
-      if (kc + 1 < nkc) sim_stage_store<Cfg>(regs, lds + (cur ^ 1) * Cfg::STAGE_BYTES, tid);
-      __syncthreads();
-    }
-  }
-  __syncthreads();  // stage buffers are re-used below for the in-workgroup merge
+  pair_tile_products<T, GLDS>(acc, lds, zn, c0, r0, a.n, a.d, tid, lane, wave_c, wave_r);
 
   const float ninf = -__builtin_huge_valf();
   if constexpr (BWD) {
@@ -175,11 +141,7 @@ __global__ __launch_bounds__(256, 2) void ntxent_tiles(NtArgs a) {
     for (int s = 0; s < 4; ++s) {  // fixed order: deterministic
       const float mp = red[s * 3], lp = red[s * 3 + 1];
       pv = fmaxf(pv, red[s * 3 + 2]);
-      if (lp > 0.f) {
-        const float mn = fmaxf(m, mp);
-        l = l * __builtin_amdgcn_exp2f(m - mn) + lp * __builtin_amdgcn_exp2f(mp - mn);
-        m = mn;
-      }
+      pair_lse_merge(m, l, mp, lp);
     }
     const int64_t o = (int64_t)blockIdx.x * a.n + r0 + tid;
     a.pm[o] = m;
@@ -210,20 +172,6 @@ __global__ __launch_bounds__(256) void ntxent_rows(const float* __restrict__ pm,
   const float lse2 = m + log2f(l);  // log2 domain
   if (row_lse) row_lse[row] = lse2 * kLn2;
   row_loss[row] = (lse2 - pv) * kLn2;
-}
-
-__global__ __launch_bounds__(1024) void ntxent_reduce(const float* __restrict__ row_loss, int64_t n,
-                                                      float* __restrict__ loss) {
-  __shared__ float red[1024];
-  float local = 0.f;
-  for (int64_t row = threadIdx.x; row < n; row += 1024) local += row_loss[row];  // fixed order
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = red[0] / (float)n;
 }
 
 // zt[k][i] = zn[i][k] as fp16 (the "weight" operand of dU = W . U on hcir_gemm_f16), and lse -> log2 domain
@@ -318,7 +266,7 @@ int nt_run(const void* z0, const void* z1, int64_t b, int d, float inv_t, float*
   hipLaunchKernelGGL(ntxent_rows, dim3((unsigned)hcir_cdiv(n, 256)), dim3(256), 0, st, w.pm, w.pl, w.pp, n,
                      nct, w.row_loss, row_lse);
   HCIR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ntxent_reduce, dim3(1), dim3(1024), 0, st, w.row_loss, n, loss);
+  hipLaunchKernelGGL(pair_mean_reduce, dim3(1), dim3(1024), 0, st, w.row_loss, n, loss);
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
 }

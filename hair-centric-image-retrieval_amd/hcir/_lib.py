@@ -51,6 +51,11 @@ SIGNATURES = {
     "hcir_ntxent_fwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_int, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "hcir_ntxent_bwd_workspace_bytes": (c_sz, [c_i64, c_i32, c_int]),
     "hcir_ntxent_bwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_int, c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_supcon_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_int, c_int]),
+    "hcir_supcon_fwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_int, c_f32, c_f32, c_int, c_vp, c_vp, c_vp, c_vp,
+                                c_sz, c_vp]),
+    "hcir_supcon_bwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_int, c_f32, c_f32, c_int, c_vp, c_vp, c_f32, c_vp,
+                                c_vp, c_sz, c_vp]),
     "hcir_layernorm_f16": (c_int, [c_vp, c_int, c_i64, c_i32, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "hcir_gemm_f16": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_int,
                               c_vp, c_i64, c_vp]),

@@ -3,6 +3,9 @@
 hcir_ntxent_fwd (fused normalise + 2B x 2B MFMA cosine + masked log-sum-exp) and, when the inputs
 require grad, differentiated by hcir_ntxent_bwd through a torch.autograd.Function — a drop-in
 `criterion(out0, out1)` for a training loop whose backbone runs on PyTorch-ROCm.
+
+SupConLoss with the constructor/forward signature of the reference's class (HairPretraining/utils/losses.py:8-101; call
+sites HairPretraining/src/pretrain_engine.py:76,390), computed by hcir_supcon_fwd / hcir_supcon_bwd the same way.
 """
 from __future__ import annotations
 
@@ -44,6 +47,119 @@ def ntxent_backward(out0, out1, temperature, lse, grad_out: float):
                             float(grad_out), g0.data_ptr(), g1.data_ptr(), ws.data_ptr(), ws.numel(),
                             _stream(out0)), "hcir_ntxent_bwd")
     return g0, g1
+
+
+def _supcon_labels(features: torch.Tensor, labels):
+    """labels as a contiguous int64 [B] tensor on the features' device (None stays None); no value is read here."""
+    if labels is None:
+        return None
+    if not isinstance(labels, torch.Tensor):
+        labels = torch.as_tensor(labels)
+    if labels.is_floating_point() or labels.is_complex():
+        raise HcirError(f"SupConLoss compares labels as 64-bit integers, got {labels.dtype}")
+    return labels.reshape(-1).to(device=features.device, dtype=torch.int64).contiguous()
+
+
+def supcon_forward(features: torch.Tensor, labels, temperature: float, base_temperature: float,
+                   normalize: bool = False, want_saved: bool = False):
+    """hcir_supcon_fwd on contiguous [B, V, D] features; labels None or int64 [B] on the same device.  Returns the
+    loss, or (loss, row_lse, row_npos) with want_saved."""
+    _dev(features, "features")
+    if features.dim() != 3 or not features.is_contiguous():
+        raise HcirError(f"supcon_forward expects contiguous [B, V, D] features, got {tuple(features.shape)}")
+    if features.dtype not in _DT:
+        raise HcirError(f"unsupported dtype {features.dtype}")
+    b, v, d = features.shape
+    L = _lib.lib()
+    dt = _DT[features.dtype]
+    ws = _ws.get(features.device, L.hcir_supcon_workspace_bytes(b, v, d, dt, 0))
+    loss = torch.empty((), dtype=torch.float32, device=features.device)
+    lse = torch.empty(b * v, dtype=torch.float32, device=features.device) if want_saved else None
+    npos = torch.empty(b * v, dtype=torch.int32, device=features.device) if want_saved else None
+    check(L.hcir_supcon_fwd(features.data_ptr(), None if labels is None else labels.data_ptr(), b, v, d, dt,
+                            1.0 / temperature, temperature / base_temperature, int(bool(normalize)),
+                            loss.data_ptr(), None if lse is None else lse.data_ptr(),
+                            None if npos is None else npos.data_ptr(), ws.data_ptr(), ws.numel(),
+                            _stream(features)), "hcir_supcon_fwd")
+    return (loss, lse, npos) if want_saved else loss
+
+
+def supcon_backward(features, labels, temperature, base_temperature, normalize, lse, npos, grad_out: float):
+    b, v, d = features.shape
+    if (b * v) % 8:
+        raise HcirError("hcir_supcon_bwd needs batch size x n_views to be a multiple of 8")
+    L = _lib.lib()
+    dt = _DT[features.dtype]
+    ws = _ws.get(features.device, L.hcir_supcon_workspace_bytes(b, v, d, dt, 1))
+    grad = torch.empty_like(features)
+    check(L.hcir_supcon_bwd(features.data_ptr(), None if labels is None else labels.data_ptr(), b, v, d, dt,
+                            1.0 / temperature, 1.0 / base_temperature, int(bool(normalize)), lse.data_ptr(),
+                            npos.data_ptr(), float(grad_out), grad.data_ptr(), ws.data_ptr(), ws.numel(),
+                            _stream(features)), "hcir_supcon_bwd")
+    return grad
+
+
+class _SupConFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, labels, temperature, base_temperature, normalize):
+        features = features.contiguous()
+        loss, lse, npos = supcon_forward(features, labels, temperature, base_temperature, normalize, want_saved=True)
+        ctx.save_for_backward(features, lse, npos)
+        ctx.labels = labels
+        ctx.cfg = (temperature, base_temperature, normalize)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        features, lse, npos = ctx.saved_tensors
+        g = supcon_backward(features, ctx.labels, *ctx.cfg, lse, npos, float(grad))  # one host read of dL
+        return g, None, None, None, None
+
+
+class SupConLoss(nn.Module):
+    """SupConLoss(temperature=0.07, contrast_mode='all', base_temperature=0.07) of HairPretraining/utils/losses.py:8-101
+    (the criterion of the simclr_supcon step, HairPretraining/src/pretrain_engine.py:76,390), computed by
+    hcir_supcon_fwd / hcir_supcon_bwd.  `normalize=False` is the drop-in for the class; `normalize=True` fuses the
+    F.normalize the reference's model applies to its output (HairPretraining/src/backbone.py:414-417), and its
+    backward, into the loss, as NTXentLoss does."""
+
+    def __init__(self, temperature: float = 0.07, contrast_mode: str = "all", base_temperature: float = 0.07,
+                 normalize: bool = False):
+        super().__init__()
+        if contrast_mode == "one":
+            raise NotImplementedError("contrast_mode='one' is never used by the reference (every SupConLoss there is "
+                                      "built with the default 'all', HairPretraining/src/pretrain_engine.py:76)")
+        if contrast_mode != "all":
+            raise ValueError("Unknown mode: {}".format(contrast_mode))
+        if abs(temperature) < 1e-8 or abs(base_temperature) < 1e-8:
+            raise ValueError(f"Illegal temperature: abs({temperature}) or abs({base_temperature}) < 1e-8")
+        self.temperature = temperature
+        self.contrast_mode = contrast_mode
+        self.base_temperature = base_temperature
+        self.normalize = bool(normalize)
+
+    def forward(self, features: torch.Tensor, labels=None, mask=None) -> torch.Tensor:
+        if len(features.shape) < 3:
+            raise ValueError("`features` needs to be [bsz, n_views, ...], at least 3 dimensions are required")
+        if labels is not None and mask is not None:
+            raise ValueError("Cannot define both `labels` and `mask`")
+        if mask is not None:
+            raise NotImplementedError("an explicit `mask` is never passed by the reference (its one call site, "
+                                      "HairPretraining/src/pretrain_engine.py:390, passes labels); use labels")
+        if len(features.shape) > 3:
+            features = features.reshape(features.shape[0], features.shape[1], -1)
+        if labels is not None:
+            labels = _supcon_labels(features, labels)
+            if labels.shape[0] != features.shape[0]:
+                raise ValueError("Num of labels does not match num of features")
+        if not features.is_cuda:
+            raise HcirError(f"SupConLoss got `features` on {features.device}; the loss runs on a HIP device only "
+                            "(no CPU fallback)")
+        if torch.is_grad_enabled() and features.requires_grad:
+            if (features.shape[0] * features.shape[1]) % 8:
+                raise HcirError("hcir_supcon_bwd needs batch size x n_views to be a multiple of 8")
+            return _SupConFn.apply(features, labels, self.temperature, self.base_temperature, self.normalize)
+        return supcon_forward(features.contiguous(), labels, self.temperature, self.base_temperature, self.normalize)
 
 
 class _NTXentFn(torch.autograd.Function):

@@ -38,7 +38,7 @@ from typing import Callable, Dict, Optional
 import torch
 import torch.nn.functional as F
 
-from .losses import NTXentLoss
+from .losses import NTXentLoss, SupConLoss
 from . import optim as hcir_optim
 from ._lib import HcirError
 from .momentum import update_momentum
@@ -192,3 +192,40 @@ class SHAMTrainStep:
             mse if mse is not None else zero, pos_dist.mean(), neg_dist.mean(), violations.sum())]).tolist()
         out.update(zip(("total", "contrastive", "triplet", "mse", "pos_dist", "neg_dist", "margin_violations"), vals))
         return out
+
+
+class SupConTrainStep:
+    """The body of Trainer.train_one_epoch_simclr_supcon's batch loop (HairPretraining/src/pretrain_engine.py:380-398),
+    the reference CLIs' default --mode: the two SimCLR views through ONE model call, split and stacked to [B, 2, P],
+    the criterion (hcir.losses.SupConLoss, hcir_supcon_fwd / _bwd) with the batch's labels, then
+    scaler.scale(loss).backward(); scaler.step; scaler.update; zero_grad.  No gradient clipping: the reference does
+    none here.  As in SHAMTrainStep the criterion sees fp32 features: the model runs its own precision, the loss
+    kernels compute in the dtype they are handed.  -> {"loss": float}."""
+
+    def __init__(self, model, optimizer, scaler=None, criterion=None):
+        self.model = model
+        self.optimizer = optimizer
+        self.scaler = scaler
+        self.criterion = criterion if criterion is not None else SupConLoss()                    # :76
+
+    def __call__(self, batch: Dict[str, torch.Tensor], **_loop_state) -> Dict[str, float]:
+        """One optimisation step on {'anchor', 'pos1', 'labels'}: image batches [B,3,H,W] and [B] integer labels on
+        the HIP device.  The loop variables SHAMTrainStep takes (epoch, batch_id, ...) are accepted and unused."""
+        model, opt, scaler = self.model, self.optimizer, self.scaler
+        model.train()                                                                           # :377
+        labels = batch["labels"]
+        images = torch.cat([batch["anchor"], batch["pos1"]], dim=0)                             # :384
+        bsz = labels.shape[0]                                                                   # :385
+        features = model(images)                                                                # :387
+        f1, f2 = torch.split(features, [bsz, bsz], dim=0)                                       # :388
+        features = torch.cat([f1.unsqueeze(1), f2.unsqueeze(1)], dim=1).float()                 # :389
+        loss = self.criterion(features, labels)                                                 # :390
+        if scaler is not None:                                                                  # :394-397
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
+        opt.zero_grad()                                                                         # :398
+        return {"loss": float(loss.detach())}

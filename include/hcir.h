@@ -158,6 +158,33 @@ int hcir_ntxent_bwd(const void* z0, const void* z1, int64_t b, int32_t d, int dt
                     size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Supervised contrastive loss (SupConLoss, HairPretraining/utils/losses.py:8-101, contrast_mode 'all';
+ * the simclr_supcon step, HairPretraining/src/pretrain_engine.py:76,390).
+ *   feat [B][V][D];  row r = v*B + i is view v of sample i,  N = V*B;  y_r = labels[r mod B]
+ *   (labels NULL: y_r = r mod B, the SimCLR case);  x_r = the row, or row / max(||row||, 1e-12) with normalize;
+ *   s_ij = x_i.x_j * inv_t;  lse_i = log sum_{j != i} exp(s_ij);  m_ij = [y_i == y_j, j != i],  n_i = sum_j m_ij;
+ *   loss = mean_i t_over_base [n_i > 0] (lse_i - sum_j m_ij s_ij / max(n_i, 1)),  t_over_base = T / T_base.
+ * A row without positives contributes 0 and still counts in the mean.  V = 2, labels NULL, normalize and
+ * t_over_base = 1 is hcir_ntxent_fwd's loss.  Outputs: loss (1 float), row_lse[N] and row_npos[N] (saved for the
+ * backward, either may be NULL).  Labels are compared as 64-bit integers.  The N x N logits are never materialised;
+ * no atomics, results are bit-identical from run to run.
+ * Backward: p_ij = exp(s_ij - lse_i), G_ij = [n_i > 0](p_ij - m_ij / n_i), W = G + G^T written once as fp16 [N][N]
+ * into the workspace, g = W.x on hcir_gemm_f16, dfeat = grad_out * inv_base / N * g (inv_base = 1 / T_base), through
+ * the projection rn_i (g_i - (g_i.u_i) u_i) with normalize; dfeat is [B][V][D] in the input dtype.
+ * hcir_supcon_workspace_bytes(..., backward): bytes for the forward (0) or the backward (1).
+ * Status: HCIR_ERR_INVALID for a null feat/loss (backward: feat/row_lse/row_npos/dfeat), b, v, d <= 0, N < 2,
+ * d % 8 != 0, inv_t == 0 or NaN, and for a backward with N % 8 != 0 (hcir_gemm_f16's rule); HCIR_ERR_UNSUPPORTED for a
+ * dtype other than HCIR_F32/F16/BF16; HCIR_ERR_WORKSPACE for a null or short workspace.  Nothing is written on an error.
+ * ------------------------------------------------------------------ */
+size_t hcir_supcon_workspace_bytes(int64_t b, int32_t v, int32_t d, int dtype, int backward);
+int hcir_supcon_fwd(const void* feat, const int64_t* labels, int64_t b, int32_t v, int32_t d, int dtype,
+                    float inv_t, float t_over_base, int normalize, float* loss, float* row_lse,
+                    int32_t* row_npos, void* workspace, size_t workspace_bytes, void* stream);
+int hcir_supcon_bwd(const void* feat, const int64_t* labels, int64_t b, int32_t v, int32_t d, int dtype,
+                    float inv_t, float inv_base, int normalize, const float* row_lse, const int32_t* row_npos,
+                    float grad_out, void* dfeat, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * ViT building blocks (fp16 MFMA, fp32 accumulate, fp32 residual stream).
  * ------------------------------------------------------------------ */
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""An epoch of SHAMTrainStep fed from an annotation CSV + image directory, input on the device.
+"""An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep) fed from an annotation CSV + image directory, input on
+the device.
 
     python tools/train_from_files.py --csv data/data_train.csv --img-dir data/train --batch-size 1024
 
@@ -20,15 +21,19 @@ sys.path.insert(0, os.path.join(ROOT, "hair-centric-image-retrieval_amd"))
 
 
 def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, prev_margin_violations: float = 0.0,
-                on_step=None):
-    """One pass over `loader` (batches are hcir.dataloader.TrainViewBatch).  -> list of the step's loss dicts."""
+                on_step=None, with_labels: bool = False):
+    """One pass over `loader` (batches are hcir.dataloader.TrainViewBatch).  -> list of the step's loss dicts.
+    with_labels (--mode supcon): the batch's class labels travel with the views as views["labels"]."""
     device = torch.device(device)
     side = torch.cuda.Stream(device=device)
     main = torch.cuda.current_stream(device)
 
     def produce(batch):   # enqueue only: nothing here waits for the device
         with torch.cuda.stream(side):
-            return batch.views(device, generator, defer_check=True)
+            views, check = batch.views(device, generator, defer_check=True)
+            if with_labels:
+                views["labels"] = batch.labels.to(device, non_blocking=True)
+            return views, check
 
     it = iter(loader)
     first = next(it, None)
@@ -60,6 +65,11 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--mode", choices=("sham", "supcon"), default="sham",
+                    help="sham: the HSimCLR step (SHAMTrainStep).  supcon: the reference's simclr_supcon step "
+                         "(SupConTrainStep) on the batch's class labels, with SHAM2(model) as encoder plus projection "
+                         "head and SupConLoss(normalize=True); the reference's SupConResNet, a CIFAR-style trunk "
+                         "(HairPretraining/src/backbone.py:276-358), is not built")
     ap.add_argument("--max-steps", type=int, default=0)
     ap.add_argument("--hip-train", action="store_true",
                     help="ResNet models: body convolutions forward and backward on the HIP kernels (hcir.conv_train)")
@@ -79,7 +89,7 @@ def main():
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
-    from hcir.pretrain_engine import SHAMTrainStep
+    from hcir.pretrain_engine import SHAMTrainStep, SupConTrainStep
     torch.manual_seed(a.seed)
     ds = EncodedDataset(a.csv, a.img_dir, return_names=True)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, drop_last=True,
@@ -94,7 +104,11 @@ def main():
         opt, scaler = optim.get_optimizer(model, a.lr, a.weight_decay, a.beta1, a.beta2), optim.GradScaler()
     else:
         opt, scaler = torch.optim.Adam(model.parameters(), lr=a.lr), torch.amp.GradScaler("cuda")
-    step = SHAMTrainStep(model, opt, scaler, warm_up_epochs=a.warm_up_epochs)
+    if a.mode == "supcon":
+        from hcir.losses import SupConLoss
+        step = SupConTrainStep(model, opt, scaler, SupConLoss(normalize=True))
+    else:
+        step = SHAMTrainStep(model, opt, scaler, warm_up_epochs=a.warm_up_epochs)
 
     class Stop(Exception):
         pass
@@ -105,7 +119,8 @@ def main():
             raise Stop
 
     try:
-        train_epoch(step, loader, "cuda", torch.Generator().manual_seed(a.seed), on_step=report)
+        train_epoch(step, loader, "cuda", torch.Generator().manual_seed(a.seed), on_step=report,
+                    with_labels=a.mode == "supcon")
     except Stop:
         pass
 
