@@ -167,6 +167,13 @@ SIGNATURES = {
     "hcir_stem_wgrad_f16": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
     "hcir_stem_wgrad_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
     "hcir_stem_wgrad_parts": (c_i32, [c_i64, c_i32, c_i32]),
+    "hcir_mim_mask_tokens": (c_int, [c_vp, c_int, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp]),
+    "hcir_mim_mask_bwd": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_mim_mask_bwd_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "hcir_mim_patch_targets": (c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "hcir_mim_l1_fwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
+                                c_vp]),
+    "hcir_mim_l1_workspace_bytes": (c_sz, [c_i64]),
 }
 
 

@@ -1,23 +1,29 @@
-"""hcir.backbone — the two baseline wrappers of HP/src/backbone.py that sit on the kNN path,
+"""hcir.backbone — the baseline wrappers of HP/src/backbone.py that are built,
 with the reference's constructor signatures:
 
   SimCLR(model="resnet18")   HP/src/backbone.py:648-681  (the second definition, which wins)
   MAE(vit)                   HP/src/backbone.py:462-525  (extract_features = encoder CLS)
   vit_base_patch16_224()     timm ctor the CLI passes to MAE (HP/knn_classification.py:146-147)
+  SimMIM(vit)                HP/src/backbone.py:549-601  (pre-training forward, fused masked-patch L1 loss and
+                             extract_features; the torchvision vit_b_16 of hcir.vit_train / hcir.vit_engine with
+                             mask tokens in front of it and a Linear(768, 768) decoder behind it, csrc/mim.hip)
+  random_token_mask(...)     lightly.models.utils.random_token_mask, which SimMIM draws its masks with
 
-The other SSL baselines of that file (MSN, DenseCL, BYOL, DINO, SimMIM, DINOv2, SiameseIMViT)
+The other SSL baselines of that file (MSN, DenseCL, BYOL, DINO, DINOv2, SiameseIMViT)
 are comparison methods outside the hot path and are not built.
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from functools import partial
 
 import torch
 from torch import nn
 
-from . import _tv_resnet, models_vit
+from . import _tv_resnet, models_vit, train_ops
 from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper
 from .vit_engine import EngineCache, VitLayer, VitSpec
+from .vit_train import VitTrainer, vit_mim_l1_with_grad, vit_mim_with_grad
 
 
 class SimCLR(HipTrunkSwitches, nn.Module):
@@ -120,4 +126,141 @@ class MAE(nn.Module):
             raise NotImplementedError("this model family is inference-only on the HIP path (the differentiable ViT is SHAM2 / ViTWrapper.forward_cls, hcir.vit_train): wrap the call in torch.no_grad()")
         eng = self._cache.get(list(self.backbone.vit.parameters()), self._spec, images.device)
         tok = eng.forward_tokens(images, cls_only_last=True)
+        return eng.cls_embedding(tok, final_norm=True, l2_normalize=False)
+
+
+def random_token_mask(size, mask_ratio: float = 0.6, mask_class_token: bool = False, device=None, generator=None):
+    """lightly.models.utils.random_token_mask: (idx_keep [b, num_keep], idx_mask [b, T - num_keep]) token indices, a
+    random permutation per image cut at num_keep = int(T (1 - mask_ratio)) (at least 1 where the class token is
+    kept).  The class token (index 0) sorts first, so it is never masked, unless mask_class_token.  torch on the
+    device: the table is [b, 197].  `generator` (not a lightly argument) makes the draw repeatable; one that lives on
+    another device draws there."""
+    b, seq = size
+    num_keep = int(seq * (1 - mask_ratio))
+    gdev = device if generator is None else generator.device
+    noise = torch.rand(b, seq, device=gdev, generator=generator)
+    if device is not None:
+        noise = noise.to(device)
+    if not mask_class_token and seq > 0:
+        noise[:, 0] = -1
+        num_keep = max(1, num_keep)
+    indices = torch.argsort(noise, dim=1)
+    return indices[:, :num_keep], indices[:, num_keep:]
+
+
+class _MaskedTVViT(nn.Module):
+    """lightly MaskedVisionTransformerTorchvision(vit=vit) container: keys backbone.vit.*, backbone.mask_token."""
+
+    def __init__(self, vit):
+        super().__init__()
+        self.vit = vit
+        self.mask_token = nn.Parameter(torch.zeros(1, 1, vit.hidden_dim))
+        nn.init.normal_(self.mask_token, std=0.02)
+
+
+class SimMIM(nn.Module):
+    """SimMIM(vit) of HP/src/backbone.py:549-601 on the HIP path; `vit` is hcir._tv_vit.vit_b_16() (torchvision's
+    layout).  State-dict keys are the reference's: backbone.vit.* (with heads.head.{weight,bias}, which its
+    checkpoints carry because it hands lightly the whole vit_b_16; unused here and never given a gradient),
+    backbone.mask_token, decoder.{weight,bias}.  lightly's encode() adds the position once (pos_mult = 1.0, unlike
+    ViTWrapper).  Dropout is 0 in vit_b_16.
+
+      forward(images)         -> (x_out [b, n, P], target [b, n, P]) as the reference, differentiable
+      masked_loss(images)     -> nn.L1Loss()(x_out, target) through hcir_mim_l1_fwd (the training step's path)
+      extract_features(images) -> class token after the final LayerNorm, of a forward with a FRESH random 75 % mask
+                                 per call: a reference quirk (:570-578), kept; idx_mask [b, 0] embeds
+                                 unmasked
+    idx_mask (int64 [b, n], lightly's: token indices, distinct per image) may be passed to each; it is validated
+    here, on the host, before anything is launched."""
+
+    def __init__(self, vit):
+        super().__init__()
+        decoder_dim = vit.hidden_dim
+        self.mask_ratio = 0.75
+        self.patch_size = vit.patch_size
+        self.sequence_length = vit.seq_length
+        if not hasattr(vit, "heads"):       # the container omits torchvision's classification head; the checkpoints have it
+            head = nn.Linear(vit.hidden_dim, 1000)
+            nn.init.zeros_(head.weight)
+            nn.init.zeros_(head.bias)
+            vit.heads = nn.Sequential(OrderedDict([("head", head)]))
+        self.backbone = _MaskedTVViT(vit)
+        self.decoder = nn.Linear(decoder_dim, vit.patch_size ** 2 * 3)
+        self._cache = EngineCache()
+
+    # -- HIP engine / trainer ----------------------------------------------------------------------------------
+    def _spec(self) -> VitSpec:
+        vit = self.backbone.vit
+        layers = []
+        for blk in vit.encoder.layers:
+            mha = blk.self_attention
+            layers.append(VitLayer(
+                ln1_w=blk.ln_1.weight, ln1_b=blk.ln_1.bias, qkv_w=mha.in_proj_weight, qkv_b=mha.in_proj_bias,
+                proj_w=mha.out_proj.weight, proj_b=mha.out_proj.bias, ln2_w=blk.ln_2.weight, ln2_b=blk.ln_2.bias,
+                fc1_w=blk.mlp[0].weight, fc1_b=blk.mlp[0].bias, fc2_w=blk.mlp[3].weight, fc2_b=blk.mlp[3].bias))
+        return VitSpec(patch=vit.patch_size, dim=vit.hidden_dim, heads=vit.num_heads, eps=1e-6, pos_mult=1.0,
+                       conv_w=vit.conv_proj.weight, conv_b=vit.conv_proj.bias, cls=vit.class_token,
+                       pos=vit.encoder.pos_embedding, layers=layers, final_ln_w=vit.encoder.ln.weight,
+                       final_ln_b=vit.encoder.ln.bias)
+
+    def trainer(self, device: torch.device) -> VitTrainer:
+        tr = getattr(self, "_trainer", None)
+        if tr is None or tr.device != device:
+            tr = VitTrainer(self._spec(), device, cls_only_last=False,
+                            mim=(self.backbone.mask_token, self.decoder.weight, self.decoder.bias))
+            self._trainer = tr
+        return tr
+
+    # -- masks -------------------------------------------------------------------------------------------------
+    def _idx_mask(self, images, idx_mask, lowest: int, generator=None):
+        """The mask of a call: drawn here (trusted), or the caller's, checked on the host: int64 [b, n] on the images'
+        device, every index in [lowest, sequence_length), no index twice in a row."""
+        b = images.shape[0]
+        if idx_mask is None:
+            return random_token_mask((b, self.sequence_length), self.mask_ratio, device=images.device,
+                                     generator=generator)[1].contiguous()
+        if not torch.is_tensor(idx_mask) or idx_mask.dtype != torch.int64 or idx_mask.dim() != 2 \
+                or idx_mask.shape[0] != b:
+            raise ValueError(f"idx_mask must be an int64 tensor [{b}, n]")
+        if idx_mask.shape[1]:
+            lo, hi = int(idx_mask.min()), int(idx_mask.max())
+            if lo < lowest or hi >= self.sequence_length:
+                raise ValueError(f"idx_mask holds token indices in [{lowest}, {self.sequence_length}); got {lo}..{hi}")
+            s = idx_mask.sort(dim=1).values
+            if bool((s[:, 1:] == s[:, :-1]).any()):
+                raise ValueError("idx_mask names a token twice in one image")
+        return idx_mask.to(images.device).contiguous()
+
+    def _masked_idx(self, images, idx_mask):
+        idx_mask = self._idx_mask(images, idx_mask, 1)       # a masked class token has no target patch
+        if idx_mask.shape[1] == 0:
+            raise ValueError("no masked token: the loss over zero elements is undefined")
+        return idx_mask
+
+    # -- the three calls ---------------------------------------------------------------------------------------
+    def forward(self, images, idx_mask=None):
+        idx_mask = self._masked_idx(images, idx_mask)
+        images = images.float().contiguous()
+        x_out = vit_mim_with_grad(self.trainer(images.device), images, idx_mask)                 # :589-593
+        b, n = idx_mask.shape
+        target = train_ops.mim_patch_targets(images, idx_mask, self.patch_size).view(b, n, -1)   # :596-599
+        return x_out, target
+
+    def masked_loss(self, images, idx_mask=None):
+        """criterion(*model(images)) of the reference's step (nn.L1Loss, HP/src/pretrain_engine.py:83,520-522) as one
+        differentiable 0-d loss: the target is never stored, the backward runs on the signs."""
+        idx_mask = self._masked_idx(images, idx_mask)
+        return vit_mim_l1_with_grad(self.trainer(images.device), images, idx_mask)
+
+    def extract_features(self, images, idx_mask=None, generator=None):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("SimMIM.extract_features is inference-only on the HIP path: wrap the call in "
+                                      "torch.no_grad(); forward / masked_loss are differentiable")
+        idx_mask = self._idx_mask(images, idx_mask, 0, generator)
+        eng = self._cache.get(list(self.backbone.vit.parameters()), self._spec, images.device)
+        mask = None
+        if idx_mask.shape[1]:
+            mask = torch.zeros((images.shape[0], self.sequence_length), dtype=torch.uint8, device=images.device)
+            mask.scatter_(1, idx_mask, 1)
+        tok = eng.forward_tokens(images, cls_only_last=True, token_mask=mask, mask_token=self.backbone.mask_token)
         return eng.cls_embedding(tok, final_norm=True, l2_normalize=False)

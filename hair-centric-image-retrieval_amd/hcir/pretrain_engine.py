@@ -229,3 +229,33 @@ class SupConTrainStep:
             opt.step()
         opt.zero_grad()                                                                         # :398
         return {"loss": float(loss.detach())}
+
+
+class SimMIMTrainStep:
+    """The body of Trainer.train_one_epoch_simMIM's batch loop (HairPretraining/src/pretrain_engine.py:514-532) for an
+    hcir.backbone.SimMIM model: one view per image, `predictions, targets = model(images)` and
+    `criterion(predictions, targets)` (nn.L1Loss, :83) as the model's fused masked_loss (the walk, then
+    hcir_mim_l1_fwd; the backward runs on the signs), then scaler.scale(loss).backward(); scaler.step; scaler.update;
+    zero_grad.  No gradient clipping: the reference does none here.  -> {"loss": float}."""
+
+    def __init__(self, model, optimizer, scaler=None):
+        self.model = model
+        self.optimizer = optimizer
+        self.scaler = scaler
+
+    def __call__(self, batch, **_loop_state) -> Dict[str, float]:
+        """One optimisation step on an image batch [B,3,H,W] on the HIP device, or on a dict of views whose 'anchor'
+        is that batch.  The loop variables SHAMTrainStep takes (epoch, batch_id, ...) are accepted and unused."""
+        model, opt, scaler = self.model, self.optimizer, self.scaler
+        model.train()
+        images = batch["anchor"] if isinstance(batch, dict) else batch                          # :518-519
+        loss = model.masked_loss(images)                                                        # :520-522
+        if scaler is not None:                                                                  # :526-529
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
+        opt.zero_grad()                                                                         # :530
+        return {"loss": float(loss.detach())}

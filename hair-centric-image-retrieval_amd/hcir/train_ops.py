@@ -205,6 +205,75 @@ def attn_cls_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, lse:
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# SimMIM (csrc/mim.hip): the two ops of the masked walk, the patch targets and the masked-patch L1 loss
+# ---------------------------------------------------------------------------------------------------------------
+def mim_mask_tokens(tok: torch.Tensor, b: int, t: int, mask: torch.Tensor, mask_token: torch.Tensor,
+                    pos: torch.Tensor, pos_mult: float) -> None:
+    """tok[b][k] = mask_token + pos_mult pos[k] where mask[b][k] != 0 (uint8 [b, t]); other rows untouched."""
+    _dev(tok, "tok")
+    _dev(mask, "mask")
+    if mask.dtype != torch.uint8 or mask.numel() != b * t:
+        raise HcirError("mim_mask_tokens: mask is a uint8 table [b, t]")
+    d = mask_token.numel()
+    check(_lib.lib().hcir_mim_mask_tokens(tok.data_ptr(), _XDT[tok.dtype], b, t, d, mask.data_ptr(),
+                                          mask_token.data_ptr(), pos.data_ptr(), float(pos_mult), _stream(tok)),
+          "hcir_mim_mask_tokens")
+
+
+def mim_mask_bwd(dtok: torch.Tensor, b: int, t: int, mask: torch.Tensor, g_mask_token: torch.Tensor,
+                 dpatch: torch.Tensor) -> None:
+    """g_mask_token[d] = sum of the masked rows of dtok (fp32 [b t, d]); dpatch[b (t-1), d] = fp16 of the patch rows of
+    dtok, +0 where masked."""
+    for x, nm in ((dtok, "dtok"), (mask, "mask"), (g_mask_token, "g_mask_token"), (dpatch, "dpatch")):
+        _dev(x, nm)
+    if dtok.dtype != torch.float32 or dpatch.dtype != torch.float16 or mask.dtype != torch.uint8:
+        raise HcirError("mim_mask_bwd: dtok fp32, dpatch fp16, mask uint8")
+    d = g_mask_token.numel()
+    if dpatch.shape[0] < b * (t - 1) or dtok.shape[0] < b * t or mask.numel() != b * t:
+        raise HcirError("mim_mask_bwd: buffers shorter than the shape")
+    L = _lib.lib()
+    ws = _ws.get(dtok.device, L.hcir_mim_mask_bwd_workspace_bytes(b, t, d))
+    check(L.hcir_mim_mask_bwd(dtok.data_ptr(), b, t, d, mask.data_ptr(), g_mask_token.data_ptr(), dpatch.data_ptr(),
+                              ws.data_ptr(), ws.numel(), _stream(dtok)), "hcir_mim_mask_bwd")
+
+
+def _mim_image_args(img: torch.Tensor, idx: torch.Tensor):
+    _dev(img, "images")
+    _dev(idx, "idx_mask")
+    if img.dtype != torch.float32 or img.dim() != 4 or idx.dtype != torch.int64 or idx.dim() != 2 \
+            or idx.shape[0] != img.shape[0]:
+        raise HcirError("images fp32 [b, C, H, W] and idx_mask int64 [b, n]")
+    return tuple(img.shape), idx.shape[1]
+
+
+def mim_patch_targets(img: torch.Tensor, idx: torch.Tensor, ps: int) -> torch.Tensor:
+    """patchify(img)[idx - 1] as fp32 [b n, C ps ps], lightly's element order (py, px, c)."""
+    (b, c, h, w), n = _mim_image_args(img, idx)
+    out = torch.empty((b * n, c * ps * ps), dtype=torch.float32, device=img.device)
+    check(_lib.lib().hcir_mim_patch_targets(img.data_ptr(), b, c, h, w, ps, idx.data_ptr(), n, out.data_ptr(),
+                                            _stream(img)), "hcir_mim_patch_targets")
+    return out
+
+
+def mim_l1_fwd(pred: torch.Tensor, img: torch.Tensor, idx: torch.Tensor, ps: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean |pred - patchify(img)[idx - 1]| as a 0-d fp32 tensor, sign(pred - target) as fp16 [pad64(b n), P] with
+    zero pad rows: the operand the backward walk's weight-gradient GEMM takes); pred fp16, at least b n rows of P."""
+    (b, c, h, w), n = _mim_image_args(img, idx)
+    _dev(pred, "pred")
+    p = c * ps * ps
+    if pred.dtype != torch.float16 or pred.dim() != 2 or pred.shape[1] != p or pred.shape[0] < b * n:
+        raise HcirError(f"mim_l1_fwd: pred fp16 [>= {b * n}, {p}], got {tuple(pred.shape)} {pred.dtype}")
+    loss = torch.empty((), dtype=torch.float32, device=img.device)
+    sgn = torch.empty(((b * n + 63) // 64 * 64, p), dtype=torch.float16, device=img.device)
+    sgn[b * n:].zero_()
+    L = _lib.lib()
+    ws = _ws.get(img.device, L.hcir_mim_l1_workspace_bytes(b * n))
+    check(L.hcir_mim_l1_fwd(pred.data_ptr(), img.data_ptr(), b, c, h, w, ps, idx.data_ptr(), n, loss.data_ptr(),
+                            sgn.data_ptr(), ws.data_ptr(), ws.numel(), _stream(img)), "hcir_mim_l1_fwd")
+    return loss, sgn
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # losses (torch.autograd Functions over the HIP kernels)
 # ---------------------------------------------------------------------------------------------------------------
 class _TripletFn(torch.autograd.Function):

@@ -178,8 +178,13 @@ class VitEngine:
         return bufs
 
     # -- forward ---------------------------------------------------------------
-    def forward_tokens(self, x: torch.Tensor, cls_only_last: bool = False, slot: int = 0) -> torch.Tensor:
+    def forward_tokens(self, x: torch.Tensor, cls_only_last: bool = False, slot: int = 0,
+                       token_mask: Optional[torch.Tensor] = None,
+                       mask_token: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x fp32 [B,3,H,W] on the HIP device -> token buffer [B,T,D] in resid_dtype (engine-owned).
+
+        token_mask (uint8 [B,T] on the device) with mask_token ([.., D]): the tokens with a non-zero byte become
+        mask_token + pos_mult * pos right after the patch embedding (hcir_mim_mask_tokens; SimMIM's encode).
 
         cls_only_last: the caller consumes only the class token (extract_features).  The last block
         then computes K and V for every token but attention queries, proj, LN2 and the MLP for the
@@ -227,6 +232,16 @@ class VitEngine:
                                      self.conv_b.data_ptr(), self.cls.data_ptr(), self.pos.data_ptr(),
                                      self.pos_mult, d, tok.data_ptr(), self._rt, st), "hcir_patch_embed")
             self._mark("patch_embed")
+        if token_mask is not None:
+            if mask_token is None:
+                raise HcirError("token_mask needs mask_token")
+            if (not token_mask.is_cuda or token_mask.dtype != torch.uint8 or tuple(token_mask.shape) != (b, t)
+                    or not token_mask.is_contiguous() or mask_token.numel() != d):
+                raise HcirError(f"token_mask: contiguous uint8 [{b}, {t}] on the HIP device; mask_token: {d} values")
+            mt = _f32(mask_token.reshape(-1), self.device)
+            check(L.hcir_mim_mask_tokens(tok.data_ptr(), self._rt, b, t, d, token_mask.data_ptr(), mt.data_ptr(),
+                                         self.pos.data_ptr(), self.pos_mult, st), "hcir_mim_mask_tokens")
+            self._mark("mim_mask_tokens")
 
         def resid_gemm(a, k, wt, bias, ls, rows, pitch, want_stats, what):
             """tok rows (pitch apart) += ls o (a . wt^T + bias); want_stats (every row only): and their statistics."""

@@ -25,6 +25,14 @@ as under the reference's fp16 autocast).  `vit_cls_with_grad` wraps both in a to
 SHAM2.forward composes with torch's optimizer, GradScaler and clip_grad_norm_ exactly as in the reference loop.
 Every launch goes through `ops` (hcir.train_ops: no CPU path); tests/test_vit_walk_host.py runs the same walk over
 float64 stand-ins on the CPU against torch's autograd.
+A second exit serves SimMIM (hcir.backbone.SimMIM; HairPretraining/src/backbone.py:580-601): `forward_mim` puts the
+mask token on the masked rows right after the patch embedding (ops.mim_mask_tokens), runs every block on every row -
+the same `_block_forward` - and ends in the final LayerNorm and the decoder GEMM on the masked rows, gathered into
+compact [pad64(b n), .] buffers as the class rows are; `backward_mim` runs the decoder's and that LayerNorm's backward
+on the compact rows, scatters into the zeroed stream gradient, walks the same `_block_backward` and replaces the
+patch-row copy by ops.mim_mask_bwd (mask-token gradient; masked rows give conv_proj nothing).  `vit_mim_with_grad`
+and `vit_mim_l1_with_grad` (the walk, then hcir_mim_l1_fwd; the backward runs on the sign matrix) wrap it;
+tests/test_mim_host.py is the wiring test.
 """
 from __future__ import annotations
 
@@ -55,14 +63,17 @@ class _Block:
 
 class _Saved:
     """Activations of one training forward (device buffers; rows padded to a multiple of 64 with zeros)."""
-    __slots__ = ("b", "t", "m", "patches", "blocks", "last", "x_out")
+    __slots__ = ("b", "t", "m", "patches", "blocks", "last", "x_out", "mim")
 
 
 class VitTrainer:
     """fp16 operand copies of a ViT's weights (as stored and transposed) + the training forward / backward."""
 
     def __init__(self, spec: VitSpec, device: torch.device, keep_recomputable: bool = True,
-                 cls_only_last: bool = True, ops=train_ops):
+                 cls_only_last: bool = True, ops=train_ops, mim=None):
+        """mim: (mask_token [1, 1, d], decoder weight [P, d], decoder bias [P]) of a SimMIM model; enables
+        forward_mim / backward_mim, the walk's second exit."""
+        self.mim = None if mim is None else tuple(mim)
         self.keep_recomputable = bool(keep_recomputable)
         # forward() returns the class token only, so the last block's other rows are dead work (see _row_set)
         self.cls_only_last = bool(cls_only_last)
@@ -81,6 +92,8 @@ class VitTrainer:
         self.scale = (self.dim // self.heads) ** -0.5
         if self.dim % 256 or self.mlp % 256 or (3 * spec.conv_w.shape[2] * spec.conv_w.shape[3]) % 256:
             raise HcirError("training path needs dim, mlp and C*P*P to be multiples of 256 (hcir_gemm_f16_tn)")
+        if self.mim is not None and (self.mim[1].shape[0] % 256 or self.mim[1].shape[1] != self.dim):
+            raise HcirError("the SimMIM decoder is Linear(dim, P) with P a multiple of 256 (hcir_gemm_f16_tn)")
         self._key = None
         self.refresh()
 
@@ -94,9 +107,13 @@ class VitTrainer:
         out += [s.final_ln_w, s.final_ln_b]
         return out
 
+    def mim_params(self) -> List[torch.Tensor]:
+        """mask_token, decoder.weight, decoder.bias: what backward_mim's gradients end with, behind params()."""
+        return list(self.mim)
+
     def refresh(self) -> None:
         """(Re)build the fp16 operand copies when a parameter changed (optimizer step, load_state_dict)."""
-        ps = self.params()
+        ps = self.params() + (self.mim_params() if self.mim is not None else [])
         key = tuple((p.data_ptr(), p._version) for p in ps)
         if key == self._key:
             return
@@ -117,6 +134,9 @@ class VitTrainer:
                 fc1_w=f16(l.fc1_w), fc1_wt=f16t(l.fc1_w), fc1_b=f32(l.fc1_b),
                 fc2_w=f16(l.fc2_w), fc2_wt=f16t(l.fc2_w), fc2_b=f32(l.fc2_b)))
         self.fln_w, self.fln_b = f32(s.final_ln_w), f32(s.final_ln_b)
+        if self.mim is not None:
+            mt, dw, db = self.mim
+            self.mask_token, self.dec_w, self.dec_wt, self.dec_b = f32(mt.reshape(-1)), f16(dw), f16t(dw), f32(db)
         self._key = key
 
     # -- buffers: their dtypes and device come from ops.ACT / ops.ACC and self.device alone ------------------------
@@ -149,6 +169,35 @@ class VitTrainer:
 
     # -- forward ------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor):
+        sv, cur = self._forward_blocks(x, None, self.cls_only_last)
+        cls = self._acc(sv.b, self.dim)
+        self.ops.cls_head(cur, sv.b, sv.last.nq, self.fln_w, self.fln_b, self.eps, cls)
+        return cls, sv
+
+    def forward_mim(self, x: torch.Tensor, idx_mask: torch.Tensor):
+        """The SimMIM exit (HairPretraining/src/backbone.py:580-601): the tokens `idx_mask` (int64 [b, n], distinct
+        per image, in [0, t)) are replaced by the mask token in front of the encoder, every block runs on every row,
+        and the masked rows go through the final LayerNorm and the decoder.  -> (pred [pad64(b n), P] in the operand
+        dtype, pad rows zero; what backward_mim needs).  The caller has validated idx_mask."""
+        ops, d = self.ops, self.dim
+        b, n = idx_mask.shape
+        t = self.pos.shape[0]
+        mask = torch.zeros((b, t), dtype=torch.uint8, device=self.device)
+        mask.scatter_(1, idx_mask, 1)
+        sv, cur = self._forward_blocks(x, mask, False)
+        rows = b * n
+        # the gather: row i * n + j of the compact buffers <-> token (i, idx_mask[i][j])
+        flat = (torch.arange(b, device=self.device)[:, None] * t + idx_mask).reshape(-1)
+        xc, ln = self._act(rows, d), self._act(rows, d)
+        xc[:rows] = cur[flat]
+        ops.layernorm(xc, rows, self.fln_w, self.fln_b, self.eps, ln)
+        pred = self._act(rows, self.dec_w.shape[0])
+        ops.gemm(ln, self.dec_w, self.dec_b, rows, pred)
+        sv.mim = SimpleNamespace(mask=mask, flat=flat, rows=rows, xc=xc, ln=ln)
+        return pred, sv
+
+    def _forward_blocks(self, x: torch.Tensor, mask, cls_only_last: bool):
+        """patch_embed, the mask tokens where `mask` (uint8 [b, t]) is given, and every block."""
         ops = self.ops
         if x.device.type != ops.DEVICE_TYPE:
             raise HcirError(f"input is on {x.device}; the hcir ViT runs on a HIP device only")
@@ -167,19 +216,22 @@ class VitTrainer:
             raise HcirError("C*P*P must be a multiple of 64")
         m = b * t
         sv = _Saved()
-        sv.b, sv.t, sv.m, sv.blocks = b, t, m, []
+        sv.b, sv.t, sv.m, sv.blocks, sv.mim = b, t, m, [], None
         # im2col of the patches in (c, ky, kx) order: the weight gradient of conv_proj needs it (data movement only)
         gh, gw = hh // ps, ww // ps
         sv.patches = self._act(b * gh * gw, c * ps * ps)
         sv.patches[: b * gh * gw] = x.reshape(b, c, gh, ps, gw, ps).permute(0, 2, 4, 1, 3, 5).reshape(b * gh * gw, -1)
         cur = self._act(m, d)
         ops.patch_embed(x, ps, self.conv_w, self.conv_b, self.cls, self.pos, self.pos_mult, cur)
+        if mask is not None:
+            # lightly's mask_at_index stands before the position add; patch_embed has added the position already
+            ops.mim_mask_tokens(cur, b, t, mask, self.mask_token, self.pos, self.pos_mult)
         # The LayerNorm outputs and gelu(u) are KEPT as well (they are the A operands of the weight-gradient GEMMs):
         # 3.6 KB more per token and layer - 65 GB for config C3's three 1024-image forwards, of 288 - instead of two
         # LayerNorm and one GELU launch per layer in the backward (keep_recomputable=False restores the recompute:
         # the forward then writes them to two scratch buffers that every full-height block shares).
         scratch = None if self.keep_recomputable else (self._act(m, d), self._act(m, self.mlp))
-        full, sv.last = self._row_set(b, t, False), self._row_set(b, t, self.cls_only_last)
+        full, sv.last = self._row_set(b, t, False), self._row_set(b, t, cls_only_last)
         for li, w in enumerate(self.lw):
             rs = sv.last if li == len(self.lw) - 1 else full
             x_res = cur                                   # the row set's residual input
@@ -189,9 +241,7 @@ class VitTrainer:
             blk, cur = self._block_forward(w, cur, x_res, b, t, rs, scratch)
             sv.blocks.append(blk)
         sv.x_out = cur                                    # [b][rs.nq][d]: the class token is row 0 of each image
-        cls = self._acc(b, d)
-        ops.cls_head(cur, b, sv.last.nq, self.fln_w, self.fln_b, self.eps, cls)
-        return cls, sv
+        return sv, cur
 
     def _block_forward(self, w, x, x_res, b, t, rs, scratch):
         """One block from the stream `x` (all b*t rows) to its output on the rows of `rs`, whose residual input is
@@ -227,22 +277,57 @@ class VitTrainer:
 
     def backward(self, sv: _Saved, d_cls: torch.Tensor) -> List[torch.Tensor]:
         """Gradients (fp32, shapes of `params()`) of sum(cls * d_cls)."""
-        ops, b, t, m, d = self.ops, sv.b, sv.t, sv.m, self.dim
+        ops, b, d = self.ops, sv.b, self.dim
+        fw, lw = self._stream_work(sv)
+        g_flw, g_flb = self._acc(d), self._acc(d)
+        dcls16 = _to(d_cls, self.device, ops.ACT)
+        ops.layernorm_bwd(sv.x_out, dcls16, self.fln_w, self.eps, None, lw.dres, g_flw, g_flb, accumulate=False, rows=b,
+                          ldx=sv.last.nq * d, ldr=sv.last.nq * d)
+        return self._walk_backward(sv, fw, lw, g_flw, g_flb)
+
+    def backward_mim(self, sv: _Saved, d_pred: torch.Tensor) -> List[torch.Tensor]:
+        """Gradients (fp32) of sum(pred * d_pred) in `params()` order, then mask_token, decoder.weight, decoder.bias.
+        d_pred: [>= b n, P]; a buffer of forward_mim's height in the operand dtype with zero pad rows is used as it
+        is (the sign matrix of ops.mim_l1_fwd), anything else is copied into one."""
+        ops, d, mm = self.ops, self.dim, sv.mim
+        rows, pdim = mm.rows, self.dec_w.shape[0]
+        if d_pred.dtype == ops.ACT and tuple(d_pred.shape) == (_pad64(rows), pdim):
+            dp = d_pred
+        else:
+            dp = self._act(rows, pdim)
+            dp[:rows] = d_pred[:rows]
+        # decoder: pred = LN_final(x)[masked rows] . W^T + bias
+        g_dw, g_db = self._acc(pdim, d), self._acc(pdim)
+        ops.gemm_tn(dp, mm.ln, g_dw, accumulate=False)
+        ops.colsum(dp, g_db, accumulate=False, rows=rows)
+        dln = self._act(rows, d)
+        ops.gemm(dp, self.dec_wt, None, rows, dln)
+        g_flw, g_flb, dxc = self._acc(d), self._acc(d), self._acc(_pad64(rows), d)
+        ops.layernorm_bwd(mm.xc, dln, self.fln_w, self.eps, None, dxc, g_flw, g_flb, accumulate=False, rows=rows)
+        fw, lw = self._stream_work(sv)
+        fw.dres[mm.flat] = dxc[:rows]                     # the scatter into the zeroed stream gradient
+        return self._walk_backward(sv, fw, lw, g_flw, g_flb) + [g_dw, g_db]
+
+    def _stream_work(self, sv: _Saved):
+        """Work buffers of a backward: those of the stream and those of the last block's row set."""
+        m, d = sv.m, self.dim
         # every gradient buffer is WRITTEN (accumulate=False) by the kernel that produces it: no zero fill (12 fills
         # per block); the fp16 work buffers only need their pad rows zero (operands of the TN GEMM)
         fw = self._work(m)                                # the stream: dres is dL / d(residual stream)
         fw.dqkv = self._act(m, 3 * d)
         # gelu(u) / LayerNorm output: recomputed per block only when the forward did not keep them
         fw.hbuf, fw.lnbuf = (None, None) if self.keep_recomputable else (self._act(m, self.mlp), self._act(m, d))
+        lw = fw if sv.last.rows == m else self._work(sv.b)   # the last block's row set has its own residual gradient
+        return fw, lw
+
+    def _walk_backward(self, sv: _Saved, fw, lw, g_flw, g_flb) -> List[torch.Tensor]:
+        """From dL / d(last block's output) in lw.dres down to the parameters of the patch embedding: the gradients in
+        `params()` order, then - on the masked walk - the mask token's."""
+        ops, b, t, m, d = self.ops, sv.b, sv.t, sv.m, self.dim
         full, last = self._row_set(b, t, False), sv.last
-        lw = fw if last.rows == m else self._work(b)      # the last block's row set has its own residual gradient
-        g_flw, g_flb = self._acc(d), self._acc(d)
-        dcls16 = _to(d_cls, self.device, ops.ACT)
-        ops.layernorm_bwd(sv.x_out, dcls16, self.fln_w, self.eps, None, lw.dres, g_flw, g_flb, accumulate=False, rows=b,
-                          ldx=last.nq * d, ldr=last.nq * d)
         # dy16 = fp16(dres) and its column sums (the bias gradient of the Linear in front) come out of the LayerNorm
         # backward that produced dres - except for the last block, whose dres is the gradient of the final LayerNorm
-        # (class-token rows only)
+        # (class-token rows only, or the masked rows)
         layer_grads, fc2_b = [], None
         for li in range(len(self.lw) - 1, -1, -1):
             rs, k = (last, lw) if li == len(self.lw) - 1 else (full, fw)
@@ -251,11 +336,20 @@ class VitTrainer:
         layer_grads.reverse()
         # ---- patch embedding: tok[b][0] = cls + pos_mult pos[0]; tok[b][1+p] = W patch + bias + pos_mult pos[1+p]
         dtok = fw.dres[:m].view(b, t, d)
-        g_cls = dtok[:, 0].sum(0)
+        mm = sv.mim
+        if mm is None:
+            g_cls = dtok[:, 0].sum(0)
+        else:                                             # a masked class token is the mask token, not cls
+            g_cls = (dtok[:, 0] * (mm.mask[:, :1] == 0).to(dtok.dtype)).sum(0)
         g_pos = dtok.sum(0) * self.pos_mult
         npat = b * (t - 1)
         dpatch = self._act(npat, d)
-        dpatch[:npat] = dtok[:, 1:].reshape(npat, d)
+        if mm is None:
+            dpatch[:npat] = dtok[:, 1:].reshape(npat, d)
+        else:
+            # masked rows are mask_token + pos_mult pos: their gradient goes to the mask token, not to conv_proj
+            g_mt = self._acc(d)
+            ops.mim_mask_bwd(fw.dres, b, t, mm.mask, g_mt, dpatch)
         g_cw, g_cb = self._acc(d, sv.patches.shape[1]), self._acc(d)
         ops.gemm_tn(dpatch, sv.patches, g_cw, accumulate=False)
         ops.colsum(dpatch, g_cb, accumulate=False, rows=npat)
@@ -264,6 +358,8 @@ class VitTrainer:
         for g in layer_grads:
             out += [g[n] for n in _GRADS]
         out += [g_flw, g_flb]
+        if mm is not None:
+            out.append(g_mt.view(self.mim[0].shape))
         return out
 
     def _block_backward(self, w, blk, b, t, rs, k, fw, fc2_b, first):
@@ -317,21 +413,78 @@ class _VitClsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_cls):
-        # The backward's GEMM operands are fp16.  An incoming gradient far from 1 (no GradScaler: d_cls ~ 1e-5 at
-        # batch 1024; or a loss scale of 2^24) would push dS = P (dP - D) and the dgrad operands into fp16's subnormal
-        # / overflow range, so the gradient is renormalised here by a POWER OF TWO (exact in fp32 and fp16) to
-        # max|d_cls| in [0.5, 1), and the fp32 results are scaled back.  Device-side only (no host sync); a
-        # non-finite or all-zero d_cls passes through unscaled, so an overflowed GradScaler step still shows infs.
-        amax = d_cls.detach().abs().max().float()
-        ok = torch.isfinite(amax) & (amax > 0)
-        k = torch.where(ok, -torch.floor(torch.log2(torch.where(ok, amax, torch.ones_like(amax)))) - 1.0,
-                        torch.zeros_like(amax)).clamp_(-100.0, 100.0)
-        up, down = torch.exp2(k), torch.exp2(-k)
+        up, down = _pow2_renorm(d_cls)
         grads = ctx.trainer.backward(ctx.saved, d_cls * up)
         ctx.saved = None
         torch._foreach_mul_(grads, down)
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.mask))
 
 
+def _pow2_renorm(grad: torch.Tensor):
+    """(up, down) device scalars, up = 2^k with max|grad| * up in [0.5, 1) and down = 2^-k.
+    The backward's GEMM operands are fp16.  An incoming gradient far from 1 (no GradScaler: d_cls ~ 1e-5 at
+    batch 1024; or a loss scale of 2^24) would push dS = P (dP - D) and the dgrad operands into fp16's subnormal
+    / overflow range, so the gradient is renormalised by a POWER OF TWO (exact in fp32 and fp16) and the fp32 results
+    are scaled back.  Device-side only (no host sync); a non-finite or all-zero gradient passes through unscaled, so
+    an overflowed GradScaler step still shows infs."""
+    amax = grad.detach().abs().max().float()
+    ok = torch.isfinite(amax) & (amax > 0)
+    k = torch.where(ok, -torch.floor(torch.log2(torch.where(ok, amax, torch.ones_like(amax)))) - 1.0,
+                    torch.zeros_like(amax)).clamp_(-100.0, 100.0)
+    return torch.exp2(k), torch.exp2(-k)
+
+
 def vit_cls_with_grad(trainer: VitTrainer, x: torch.Tensor) -> torch.Tensor:
     return _VitClsFn.apply(trainer, x, *trainer.params())
+
+
+class _VitMimFn(torch.autograd.Function):
+    """x_out = decoder(LN_final(ViT(x with mask tokens))[masked rows]) as fp32 [b, n, P], with gradients for every
+    backbone parameter, the mask token and the decoder (none for the images)."""
+
+    @staticmethod
+    def forward(ctx, trainer: VitTrainer, x: torch.Tensor, idx_mask: torch.Tensor, *params):
+        pred, saved = trainer.forward_mim(x, idx_mask)
+        ctx.trainer, ctx.saved = trainer, saved
+        ctx.mask = [p.requires_grad for p in params]
+        b, n = idx_mask.shape
+        return pred[: b * n].view(b, n, -1).to(trainer.ops.ACC)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        up, down = _pow2_renorm(d_out)
+        grads = ctx.trainer.backward_mim(ctx.saved, (d_out * up).reshape(-1, d_out.shape[-1]))
+        ctx.saved = None
+        torch._foreach_mul_(grads, down)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.mask))
+
+
+class _VitMimL1Fn(torch.autograd.Function):
+    """mean |x_out - patchify(x)[idx_mask - 1]| with x_out as in _VitMimFn: the walk, then hcir_mim_l1_fwd.  The loss
+    is linear in sgn = sign(x_out - target), so the backward walk runs on sgn as its fp16 operand (exact: no loss
+    scale can push it out of fp16's range) and grad_out / N multiplies the finished fp32 gradients on the device."""
+
+    @staticmethod
+    def forward(ctx, trainer: VitTrainer, x: torch.Tensor, idx_mask: torch.Tensor, *params):
+        x = x.to(trainer.ops.ACC).contiguous()
+        pred, saved = trainer.forward_mim(x, idx_mask)
+        loss, ctx.sgn = trainer.ops.mim_l1_fwd(pred, x, idx_mask, trainer.patch)
+        ctx.trainer, ctx.saved = trainer, saved
+        ctx.inv_n = 1.0 / (idx_mask.numel() * pred.shape[1])
+        ctx.mask = [p.requires_grad for p in params]
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = ctx.trainer.backward_mim(ctx.saved, ctx.sgn)
+        ctx.saved = ctx.sgn = None
+        torch._foreach_mul_(grads, g.detach().to(grads[0].dtype) * ctx.inv_n)
+        return (None, None, None) + tuple(gr if need else None for gr, need in zip(grads, ctx.mask))
+
+
+def vit_mim_with_grad(trainer: VitTrainer, x: torch.Tensor, idx_mask: torch.Tensor) -> torch.Tensor:
+    return _VitMimFn.apply(trainer, x, idx_mask, *(trainer.params() + trainer.mim_params()))
+
+
+def vit_mim_l1_with_grad(trainer: VitTrainer, x: torch.Tensor, idx_mask: torch.Tensor) -> torch.Tensor:
+    return _VitMimL1Fn.apply(trainer, x, idx_mask, *(trainer.params() + trainer.mim_params()))

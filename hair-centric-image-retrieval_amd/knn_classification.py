@@ -3,7 +3,8 @@
 MI355X hot path.  Same flags (HP/knn_classification.py:47-67) and the same output file
 `<save_path>/<mode>_<model>[_<SHAM_mode>]/knn_evaluation_results.txt`.
 
-Modes on the hot path: SHAM (resnet18 / resnet50 / vit_b_16), simclr, mae.  The other --mode
+Modes on the hot path: SHAM (resnet18 / resnet50 / vit_b_16), simclr, mae, simMIM (whose embedding is the class
+token of a forward with a fresh random 75 % mask, as in the reference).  The other --mode
 values name SSL baselines that are out of scope: accepted by argparse,
 rejected with a clear error.  --eval_type knn, linear_prob (`linear_probe_results.txt`: the L-BFGS fit of
 hcir.linear_probe on the device) and inter_intra_distance (`variance_analysis_both.txt`) are built;
@@ -89,9 +90,16 @@ def build_model(args):
         model = MAE(vit_base_patch16_224())
         if args.checkpoint_path:
             model.load_state_dict(load(args.checkpoint_path)['model_state_dict'], strict=False)  # decoder not built
+    elif args.mode == "simMIM":
+        from hcir._tv_vit import vit_b_16
+        from hcir.backbone import SimMIM
+        model = SimMIM(vit_b_16())                                      # HP/knn_classification.py:158-160
+        if args.checkpoint_path:
+            sd = load(args.checkpoint_path)     # a trainer dict, or the raw state_dict the reference's CLI loads
+            model.load_state_dict(sd['model_state_dict'] if 'model_state_dict' in sd else sd)
     else:
         raise SystemExit(f"--mode {args.mode}: this SSL baseline is outside the MI355X hot path "
-                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae")
+                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae, simMIM")
     if args.checkpoint_path:
         print("Model weights loaded!")
     if getattr(args, "resnet_engine", "torch") == "hip" and hasattr(model, "hip_trunk"):

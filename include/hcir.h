@@ -1026,6 +1026,53 @@ size_t hcir_stem_wgrad_workspace_bytes(int64_t b, int32_t h, int32_t w);
  * gradient returns for the shape. */
 int32_t hcir_stem_wgrad_parts(int64_t b, int32_t h, int32_t w);
 
+/* ------------------------------------------------------------------ *
+ * SimMIM pre-training around the ViT walk (csrc/mim.hip; hcir/backbone.py SimMIM, hcir/vit_train.py).  Serves
+ * HairPretraining/src/backbone.py:549-601 and src/pretrain_engine.py:514-532: lightly's mask_at_index in front of the
+ * encoder, patchify + the gather of the masked patches, nn.L1Loss.  Four memory-bound passes; the network between
+ * them is the existing walk.  b images, t = 1 + patches tokens per image, d features, P = C ps ps elements per patch.
+ * No float atomics: partial sums go to `workspace` and are added in a fixed order, two calls give the same bits.
+ * 16-byte accesses throughout: HCIR_ERR_UNSUPPORTED unless d % 8 == 0 resp. P % 8 == 0 (and P <= 12288, one patch
+ * in LDS); HCIR_ERR_INVALID for a size below 1, an image side that is no multiple of ps, or a NULL pointer;
+ * HCIR_ERR_WORKSPACE for a NULL or short workspace.  Statuses are decided before anything is launched.
+ * Token indices `idx` (int64, lightly's idx_mask: 0 = class token, 1 + p = patch p) are read on the device and
+ * range-checked there: a row whose index is outside [1, t) reads no image, is written as zero and adds nothing to a
+ * sum.  The byte mask of the other two calls is a table [b][t] indexed by position: it cannot address anything.
+ * ------------------------------------------------------------------ */
+
+/* tok[b][k][:] = round(mask_token + pos_mult * pos[k]) for every (b, k) with mask[b][k] != 0 (k = 0, the class token,
+ * included); every other row is left as it is.  tok [b][t][d] in tok_dtype (HCIR_F32 | HCIR_F16) as hcir_patch_embed
+ * wrote it; mask_token fp32 [d], pos fp32 [t][d].  One fp32 fma (one rounding), one rounding to tok_dtype. */
+int hcir_mim_mask_tokens(void* tok, int tok_dtype, int64_t b, int32_t t, int32_t d, const uint8_t* mask,
+                         const float* mask_token, const float* pos, float pos_mult, void* stream);
+/* Backward of the above, one pass over the stream gradient dtok fp32 [b][t][d]:
+ *   g_mask_token[d]          = sum over the rows with mask != 0 of dtok[b][k][:]          (fp32, overwritten)
+ *   dpatch[b (t-1) + p][:]   = mask[b][1 + p] ? +0 : fp16(dtok[b][1 + p][:])              (fp16 [b (t-1)][d])
+ * Rows of dpatch behind b (t-1) are not touched.  The b t rows are cut into chunks = clamp(ceil(b t / 64), 1, 256)
+ * shares of ceil(b t / chunks) consecutive rows; inside a share 8 row lanes (row % 8 within the share) add their rows
+ * in order, the lanes are added in order, then the shares in order. */
+int hcir_mim_mask_bwd(const float* dtok, int64_t b, int32_t t, int32_t d, const uint8_t* mask, float* g_mask_token,
+                      void* dpatch, void* workspace, size_t workspace_bytes, void* stream);
+/* HOST.  chunks * d * 4 bytes; 0 for a shape without a kernel. */
+size_t hcir_mim_mask_bwd_workspace_bytes(int64_t b, int32_t t, int32_t d);
+/* out[b n + j][(py ps + px) C + ch] = img[b][ch][gy ps + py][gx ps + px] with patch idx[b][j] - 1 = gy (W / ps) + gx:
+ * the rows patchify(img)[idx - 1] in lightly's element order, channel fastest.  img fp32 [b][C][H][W], idx int64
+ * [b][n], out fp32 [b n][P].  Data movement only: bit-exact. */
+int hcir_mim_patch_targets(const float* img, int64_t b, int32_t c, int32_t h, int32_t w, int32_t ps,
+                           const int64_t* idx, int32_t n, float* out, void* stream);
+/* loss = mean over all b n P elements of |pred - target| (fp32 device scalar) and sgn = sign(pred - target) in
+ * {-1, 0, +1} (fp16 [b n][P]), target = the rows hcir_mim_patch_targets would write, read from the image and never
+ * stored.  pred fp16 [b n][P].  Differences and sums are fp32.  Workgroup w of blocks = min(b n, 1024) takes the
+ * ceil(b n / blocks) rows from w ceil(b n / blocks); a thread adds its elements in order, a workgroup its threads by
+ * the xor butterfly and its four waves in order, a last launch the workgroups (thread i the parts i, i + 256, ...,
+ * then the same workgroup sum) and multiplies by 1 / (b n P).  The gradient of the loss is grad_out / (b n P) * sgn:
+ * there is no backward kernel. */
+int hcir_mim_l1_fwd(const void* pred, const float* img, int64_t b, int32_t c, int32_t h, int32_t w, int32_t ps,
+                    const int64_t* idx, int32_t n, float* loss, void* sgn, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* HOST.  blocks * 4 bytes for rows = b n. */
+size_t hcir_mim_l1_workspace_bytes(int64_t rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep) fed from an annotation CSV + image directory, input on
-the device.
+"""An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep, --mode simmim: SimMIMTrainStep) fed from an annotation CSV
++ image directory, input on the device.
 
     python tools/train_from_files.py --csv data/data_train.csv --img-dir data/train --batch-size 1024
 
@@ -21,16 +21,17 @@ sys.path.insert(0, os.path.join(ROOT, "hair-centric-image-retrieval_amd"))
 
 
 def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, prev_margin_violations: float = 0.0,
-                on_step=None, with_labels: bool = False):
+                on_step=None, with_labels: bool = False, view_kwargs=None):
     """One pass over `loader` (batches are hcir.dataloader.TrainViewBatch).  -> list of the step's loss dicts.
-    with_labels (--mode supcon): the batch's class labels travel with the views as views["labels"]."""
+    with_labels (--mode supcon): the batch's class labels travel with the views as views["labels"].
+    view_kwargs: keywords of hcir.views.simclr_views (min_scale, cj_prob, ...) for the batch's views."""
     device = torch.device(device)
     side = torch.cuda.Stream(device=device)
     main = torch.cuda.current_stream(device)
 
     def produce(batch):   # enqueue only: nothing here waits for the device
         with torch.cuda.stream(side):
-            views, check = batch.views(device, generator, defer_check=True)
+            views, check = batch.views(device, generator, defer_check=True, **(view_kwargs or {}))
             if with_labels:
                 views["labels"] = batch.labels.to(device, non_blocking=True)
             return views, check
@@ -65,11 +66,14 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--mode", choices=("sham", "supcon"), default="sham",
+    ap.add_argument("--mode", choices=("sham", "supcon", "simmim"), default="sham",
                     help="sham: the HSimCLR step (SHAMTrainStep).  supcon: the reference's simclr_supcon step "
                          "(SupConTrainStep) on the batch's class labels, with SHAM2(model) as encoder plus projection "
                          "head and SupConLoss(normalize=True); the reference's SupConResNet, a CIFAR-style trunk "
-                         "(HairPretraining/src/backbone.py:276-358), is not built")
+                         "(HairPretraining/src/backbone.py:276-358), is not built.  simmim: the reference's simMIM step "
+                         "(SimMIMTrainStep) on SimMIM(vit_b_16), one view per image with lightly's MAETransform "
+                         "settings (min_scale 0.2, flip, no colour jitter, grayscale or blur) on the device view "
+                         "kernel, which resamples bilinearly where MAETransform resamples bicubically")
     ap.add_argument("--max-steps", type=int, default=0)
     ap.add_argument("--hip-train", action="store_true",
                     help="ResNet models: body convolutions forward and backward on the HIP kernels (hcir.conv_train)")
@@ -89,22 +93,35 @@ def main():
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
-    from hcir.pretrain_engine import SHAMTrainStep, SupConTrainStep
+    from hcir.pretrain_engine import SHAMTrainStep, SimMIMTrainStep, SupConTrainStep
     torch.manual_seed(a.seed)
     ds = EncodedDataset(a.csv, a.img_dir, return_names=True)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, drop_last=True,
                                          num_workers=a.workers, collate_fn=functools.partial(collate_train_views),
                                          pin_memory=False)
-    model = SHAM2(a.model).cuda()
-    model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
-    model.hip_train_norm = a.hip_train_norm
-    model.hip_train_stem = a.hip_train_stem
+    if a.mode == "simmim":
+        if a.model != "vit_b_16":
+            ap.error("--mode simmim trains the torchvision vit_b_16")
+        if a.fused_optim:
+            ap.error("--mode simmim steps with torch's Adam and GradScaler (SimMIMTrainStep: scaler.step / update)")
+        from hcir._tv_vit import vit_b_16
+        from hcir.backbone import SimMIM
+        model = SimMIM(vit_b_16()).cuda()
+    else:
+        model = SHAM2(a.model).cuda()
+        model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
+        model.hip_train_norm = a.hip_train_norm
+        model.hip_train_stem = a.hip_train_stem
     if a.fused_optim:
         from hcir import optim
         opt, scaler = optim.get_optimizer(model, a.lr, a.weight_decay, a.beta1, a.beta2), optim.GradScaler()
     else:
         opt, scaler = torch.optim.Adam(model.parameters(), lr=a.lr), torch.amp.GradScaler("cuda")
-    if a.mode == "supcon":
+    view_kwargs = None
+    if a.mode == "simmim":
+        step = SimMIMTrainStep(model, opt, scaler)
+        view_kwargs = dict(min_scale=0.2, cj_prob=0.0, random_gray_scale=0.0, gaussian_blur=0.0)
+    elif a.mode == "supcon":
         from hcir.losses import SupConLoss
         step = SupConTrainStep(model, opt, scaler, SupConLoss(normalize=True))
     else:
@@ -120,7 +137,7 @@ def main():
 
     try:
         train_epoch(step, loader, "cuda", torch.Generator().manual_seed(a.seed), on_step=report,
-                    with_labels=a.mode == "supcon")
+                    with_labels=a.mode == "supcon", view_kwargs=view_kwargs)
     except Stop:
         pass
 
