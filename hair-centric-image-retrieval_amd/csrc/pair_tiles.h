@@ -1,6 +1,7 @@
-// pair_tiles.h — the all-pairs logits tile of the contrastive losses (ntxent.hip, supcon.hip).
+// pair_tiles.h — the logits tile of the contrastive losses (ntxent.hip, supcon.hip, ntxent_bank.hip).
 //
-// Both losses multiply the [N, D] row matrix by itself on the sim_core.h engine: workgroup (x = column tile of
+// The all-pairs losses multiply the [N, D] row matrix by itself, the memory-bank loss multiplies its [N, D] query rows
+// by the [K, D] bank, on the sim_core.h engine: workgroup (x = column tile of
 // 128, y = row block of 128), a lane owns one logits ROW and receives 16 column scores per MFMA tile.  What is
 // shared lives here: the stage / MFMA main loop, the online (max, sum of exp2) merge of two partials, and the
 // fixed-tree mean of the per-row loss terms.  The epilogues (which column is a positive) stay in the two files.
@@ -13,13 +14,14 @@ constexpr float kLn2 = 0.69314718055994530942f;
 template <typename T>
 using PairCfg = SimCfg<T, 2, 2, 2>;  // 128 column rows streamed x 128 logits rows resident
 
-// acc[ct][rt] = the 4 x (32 x 32) products of this wave: columns c0 + wave_c*64 + ct*32 + acc_row(i, h), row
-// r0 + wave_r*64 + rt*32 + (lane & 31).  Rows past n - 1 read row n - 1.  Ends on a barrier: the stage buffers are
+// acc[ct][rt] = the 4 x (32 x 32) products of this wave: columns c0 + wave_c*64 + ct*32 + acc_row(i, h) of the
+// [ncols, D] matrix `cols`, row r0 + wave_r*64 + rt*32 + (lane & 31) of the [nrows, D] matrix `rows`.  Columns past
+// ncols - 1 read column ncols - 1, rows past nrows - 1 read row nrows - 1.  Ends on a barrier: the stage buffers are
 // free for the caller's in-workgroup merge.
 template <typename T, bool GLDS>
-__device__ __forceinline__ void pair_tile_products(f32x16 (&acc)[2][2], char* lds, const T* __restrict__ zn,
-                                                   int64_t c0, int64_t r0, int64_t n, int d, int tid, int lane,
-                                                   int wave_c, int wave_r) {
+__device__ __forceinline__ void pair_tile_products(f32x16 (&acc)[2][2], char* lds, const T* __restrict__ cols,
+                                                   int64_t c0, int64_t ncols, const T* __restrict__ rows, int64_t r0,
+                                                   int64_t nrows, int d, int tid, int lane, int wave_c, int wave_r) {
   using Cfg = PairCfg<T>;
   constexpr int EPS = SimElem<T>::kPerStage;
   const int nkc = (d + EPS - 1) / EPS;
@@ -31,28 +33,36 @@ __device__ __forceinline__ void pair_tile_products(f32x16 (&acc)[2][2], char* ld
       for (int i = 0; i < 16; ++i) acc[x][y][i] = 0.f;
 
   if constexpr (GLDS) {
-    sim_stage_glds<T, Cfg>(lds, zn, c0, n - 1, zn, r0, n - 1, d, 0, tid);
+    sim_stage_glds<T, Cfg>(lds, cols, c0, ncols - 1, rows, r0, nrows - 1, d, 0, tid);
     for (int kc = 0; kc < nkc; ++kc) {
       const int cur = kc & 1;
       sim_glds_retire_and_sync();
       if (kc + 1 < nkc)
-        sim_stage_glds<T, Cfg>(lds + (cur ^ 1) * Cfg::STAGE_BYTES, zn, c0, n - 1, zn, r0, n - 1, d, kc + 1, tid);
+        sim_stage_glds<T, Cfg>(lds + (cur ^ 1) * Cfg::STAGE_BYTES, cols, c0, ncols - 1, rows, r0, nrows - 1, d, kc + 1, tid);
       sim_stage_mfma<T, Cfg, 2>(acc, lds + cur * Cfg::STAGE_BYTES, wave_c, wave_r, lane);
     }
   } else {
     u32x4 regs[Cfg::NLOAD];
-    sim_stage_load<T, Cfg>(regs, zn, c0, n - 1, zn, r0, n - 1, d, 0, tid);
+    sim_stage_load<T, Cfg>(regs, cols, c0, ncols - 1, rows, r0, nrows - 1, d, 0, tid);
     sim_stage_store<Cfg>(regs, lds, tid);
     __syncthreads();
     for (int kc = 0; kc < nkc; ++kc) {
       const int cur = kc & 1;
-      if (kc + 1 < nkc) sim_stage_load<T, Cfg>(regs, zn, c0, n - 1, zn, r0, n - 1, d, kc + 1, tid);
+      if (kc + 1 < nkc) sim_stage_load<T, Cfg>(regs, cols, c0, ncols - 1, rows, r0, nrows - 1, d, kc + 1, tid);
       sim_stage_mfma<T, Cfg, 2>(acc, lds + cur * Cfg::STAGE_BYTES, wave_c, wave_r, lane);
       if (kc + 1 < nkc) sim_stage_store<Cfg>(regs, lds + (cur ^ 1) * Cfg::STAGE_BYTES, tid);
       __syncthreads();
     }
   }
   __syncthreads();
+}
+
+// The all-pairs form: columns and rows of one [n, D] matrix.
+template <typename T, bool GLDS>
+__device__ __forceinline__ void pair_tile_products(f32x16 (&acc)[2][2], char* lds, const T* __restrict__ zn,
+                                                   int64_t c0, int64_t r0, int64_t n, int d, int tid, int lane,
+                                                   int wave_c, int wave_r) {
+  pair_tile_products<T, GLDS>(acc, lds, zn, c0, n, zn, r0, n, d, tid, lane, wave_c, wave_r);
 }
 
 // (m, l) <- (m, l) merged with the partial (mp, lp) of an online log-sum-exp in the log2 domain; an empty partial

@@ -8,12 +8,16 @@ with the reference's constructor signatures:
                              extract_features; the torchvision vit_b_16 of hcir.vit_train / hcir.vit_engine with
                              mask tokens in front of it and a Linear(768, 768) decoder behind it, csrc/mim.hip)
   random_token_mask(...)     lightly.models.utils.random_token_mask, which SimMIM draws its masks with
+  DenseCL(backbone)          HP/src/backbone.py:123-161  (ResNet trunk without pool and fc, global and local heads, their
+                             momentum twins; the trunk on hcir.conv_train.train_trunk_map / hcir.resnet_engine behind the
+                             HipTrunkSwitches; the step's losses and matching are hcir.losses / hcir.dense)
 
-The other SSL baselines of that file (MSN, DenseCL, BYOL, DINO, DINOv2, SiameseIMViT)
+The other SSL baselines of that file (MSN, BYOL, DINO, DINOv2, SiameseIMViT)
 are comparison methods outside the hot path and are not built.
 """
 from __future__ import annotations
 
+import copy
 from collections import OrderedDict
 from functools import partial
 
@@ -21,7 +25,9 @@ import torch
 from torch import nn
 
 from . import _tv_resnet, models_vit, train_ops
-from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper
+from . import conv_train
+from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper, deactivate_requires_grad
+from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
 from .vit_train import VitTrainer, vit_mim_l1_with_grad, vit_mim_with_grad
 
@@ -264,3 +270,97 @@ class SimMIM(nn.Module):
             mask.scatter_(1, idx_mask, 1)
         tok = eng.forward_tokens(images, cls_only_last=True, token_mask=mask, mask_token=self.backbone.mask_token)
         return eng.cls_embedding(tok, final_norm=True, l2_normalize=False)
+
+
+class DenseCLProjectionHead(nn.Module):
+    """lightly.models.modules.DenseCLProjectionHead(input_dim, hidden_dim, output_dim): Linear -> ReLU -> Linear with
+    biases and no BatchNorm; keys layers.{0,2}.{weight,bias}."""
+
+    def __init__(self, input_dim: int = 2048, hidden_dim: int = 2048, output_dim: int = 512):
+        super().__init__()
+        self.layers = nn.Sequential(nn.Linear(input_dim, hidden_dim), nn.ReLU(inplace=True),
+                                    nn.Linear(hidden_dim, output_dim))
+
+    def forward(self, x):
+        return self.layers(x)
+
+
+class DenseCL(HipTrunkSwitches, nn.Module):
+    """DenseCL(backbone) of HP/src/backbone.py:123-161: `backbone` is a ResNet trunk without its pool and fc,
+    nn.Sequential(*list(resnet50().children())[:-2]) (HP/mainpretrain.py:159-162), with a global and a local
+    DenseCLProjectionHead(feature_dim, feature_dim, 512) and momentum twins of all three.  State-dict keys are the
+    reference's: backbone.*, backbone_momentum.*, projection_head_{global,local}[_momentum].layers.{0,2}.{weight,bias}.
+    `feature_dim` (not a reference argument; 2048 there) is the trunk's output width: 512 for a ResNet-18 trunk.
+
+      forward(x)           -> (features [B, HW, C], global [B, 512], local [B, HW, 512]), differentiable
+      forward_momentum(x)  -> the same three through the momentum modules, without gradient.  (The reference's method
+                              runs the QUERY modules under no_grad, :150-157 - its momentum modules are updated and
+                              never read.  Ours reads them, as lightly's DenseCL example and the method's name do.)
+      extract_features(x)  -> pooled trunk features [B, C]
+
+    HipTrunkSwitches: the 8-child trunk is handed to the 9-child code as a view
+    nn.Sequential(*backbone.children(), pool) that shares the modules and is registered nowhere.  With hip_trunk an
+    eval-mode extract_features under no_grad runs hcir.resnet_engine; with hip_train (and hip_train_norm /
+    hip_train_stem on top) a train-mode forward / forward_momentum runs hcir.conv_train.train_trunk_map, whose fp16
+    NHWC map IS the [B, HW, C] features: dense matching, the local head and the pool read it without a permute.  Off,
+    everything is the torch path.  The two heads are torch modules either way."""
+
+    def __init__(self, backbone, feature_dim: int = 2048):
+        super().__init__()
+        self.backbone = backbone
+        self.projection_head_global = DenseCLProjectionHead(feature_dim, feature_dim, 512)
+        self.projection_head_local = DenseCLProjectionHead(feature_dim, feature_dim, 512)
+
+        self.backbone_momentum = copy.deepcopy(self.backbone)
+        self.projection_head_global_momentum = copy.deepcopy(self.projection_head_global)
+        self.projection_head_local_momentum = copy.deepcopy(self.projection_head_local)
+        self.pool = nn.AdaptiveAvgPool2d((1, 1))
+
+        deactivate_requires_grad(self.backbone_momentum)
+        deactivate_requires_grad(self.projection_head_global_momentum)
+        deactivate_requires_grad(self.projection_head_local_momentum)
+
+    # -- the HIP paths -------------------------------------------------------------------------------------------
+    def _trunk_view(self, which: str) -> nn.Sequential:
+        """The 9-child trunk hcir.resnet_engine.layer_table expects, sharing the modules of attribute `which`; built
+        per call (a few modules in a list) and never assigned to self, so it adds no state-dict key."""
+        return nn.Sequential(*getattr(self, which).children(), self.pool)
+
+    def trunk_engine(self, which: str, device: torch.device):
+        caches = self.__dict__.setdefault("_trunk_caches", {})
+        return caches.setdefault(which, ResNetEngineCache()).get(self._trunk_view(which), device)
+
+    def _map_active(self, trunk: nn.Module, x: torch.Tensor, need_grad: bool) -> bool:
+        # hip_train_active's conditions; a momentum trunk runs the same walk under no_grad
+        return (bool(self.hip_train) and trunk.training and (torch.is_grad_enabled() or not need_grad) and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1 and x.shape[1] == 3
+                and x.shape[2] >= 7 and x.shape[3] >= 7)
+
+    def _three(self, which: str, head_global, head_local, x, need_grad: bool):
+        trunk = getattr(self, which)
+        if self._map_active(trunk, x, need_grad):
+            fmap = conv_train.train_trunk_map(self._trunk_view(which), x, fused_norm=bool(self.hip_train_norm),
+                                              fused_stem=bool(self.hip_train_stem))      # fp16 [B, h, w, C]
+            b, h, w, c = fmap.shape
+            features = fmap.view(b, h * w, c)
+            pooled = self.pool(fmap.permute(0, 3, 1, 2).float()).flatten(start_dim=1)
+            local_in = features if torch.is_autocast_enabled() else features.float()
+            return features, head_global(pooled), head_local(local_in)
+        features = trunk(x)
+        glob = head_global(self.pool(features).flatten(start_dim=1))
+        features = features.flatten(start_dim=2).permute(0, 2, 1)
+        return features, glob, head_local(features)
+
+    # -- the reference's three calls -----------------------------------------------------------------------------
+    def forward(self, x):
+        return self._three("backbone", self.projection_head_global, self.projection_head_local, x, True)
+
+    @torch.no_grad()
+    def forward_momentum(self, x):
+        return self._three("backbone_momentum", self.projection_head_global_momentum,
+                           self.projection_head_local_momentum, x, False)
+
+    def extract_features(self, x):
+        if hip_trunk_active(self.hip_trunk, self.backbone, x):
+            return self.trunk_engine("backbone", x.device).forward(x)
+        return self.pool(self.backbone(x)).flatten(start_dim=1)

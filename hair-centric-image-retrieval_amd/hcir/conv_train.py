@@ -266,14 +266,27 @@ def train_trunk(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool = False,
     runs then).  The table is rebuilt, and with it resnet_engine's structure checks (stem, pooling, every body conv
     has a kernel) are repeated, on every call: an edited trunk raises HcirError whenever the edit was made (host cost:
     DESIGN.md §3.4)."""
+    a = _trunk_map(trunk, x, fused_norm, fused_stem)
+    return list(trunk.children())[8](a.permute(0, 3, 1, 2).float()).flatten(start_dim=1)
+
+
+def _trunk_map(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool, fused_stem: bool) -> torch.Tensor:
     table = layer_table(trunk)
     kids = list(trunk.children())
     if fused_stem and not x.requires_grad:
         a = stem_train(x, kids[0], kids[1])
     else:
         a = kids[3](kids[2](kids[1](kids[0](x)))).permute(0, 2, 3, 1).contiguous().half()
-    a = walk(table, a, norm=bn_act_nhwc if fused_norm else torch_norm)
-    return kids[8](a.permute(0, 3, 1, 2).float()).flatten(start_dim=1)
+    return walk(table, a, norm=bn_act_nhwc if fused_norm else torch_norm)
+
+
+def train_trunk_map(trunk: nn.Sequential, x: torch.Tensor, fused_norm: bool = False,
+                    fused_stem: bool = False) -> torch.Tensor:
+    """train_trunk without its final pool: x fp32 [B,3,H,W] -> the last stage's fp16 NHWC map [B,h,w,C], which read as
+    [B, h*w, C] is the layout dense matching and a per-position head take (hcir.backbone.DenseCL).  `trunk` is the
+    9-child nn.Sequential layer_table checks; its pool is not run.  Under no_grad (a momentum trunk) the same kernels
+    run forward only: batch statistics, running-stat updates included."""
+    return _trunk_map(trunk, x, fused_norm, fused_stem)
 
 
 def hip_train_active(enabled: bool, trunk: nn.Module, x: torch.Tensor) -> bool:

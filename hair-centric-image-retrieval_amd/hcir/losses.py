@@ -4,6 +4,9 @@ hcir_ntxent_fwd (fused normalise + 2B x 2B MFMA cosine + masked log-sum-exp) and
 require grad, differentiated by hcir_ntxent_bwd through a torch.autograd.Function — a drop-in
 `criterion(out0, out1)` for a training loop whose backbone runs on PyTorch-ROCm.
 
+With a memory bank (memory_bank_size=(K, D), the DenseCL criteria) the loss is hcir_ntxent_bank_fwd / _bwd and the
+module keeps lightly's queue.
+
 SupConLoss with the constructor/forward signature of the reference's class (HairPretraining/utils/losses.py:8-101; call
 sites HairPretraining/src/pretrain_engine.py:76,390), computed by hcir_supcon_fwd / hcir_supcon_bwd the same way.
 """
@@ -178,22 +181,150 @@ class _NTXentFn(torch.autograd.Function):
         return g0, g1, None
 
 
+def ntxent_bank_forward(out0: torch.Tensor, out1: torch.Tensor, bank: torch.Tensor, temperature: float,
+                        want_saved: bool = False):
+    """hcir_ntxent_bank_fwd on contiguous [N, D] rows of one dtype and an fp32 [K, D] bank.  Returns (loss, k_unit), or
+    (loss, k_unit, row_lse, row_pos) with want_saved; k_unit fp32 [N, D] are the normalised rows of out1."""
+    _dev(out0, "out0")
+    _dev(out1, "out1")
+    _dev(bank, "bank")
+    if out0.shape != out1.shape or out0.dim() != 2 or out0.dtype != out1.dtype:
+        raise HcirError(f"NTXentLoss expects two [N, D] tensors of one dtype, got {tuple(out0.shape)} "
+                        f"{out0.dtype} / {tuple(out1.shape)} {out1.dtype}")
+    if out0.dtype not in _DT:
+        raise HcirError(f"unsupported dtype {out0.dtype}")
+    n, d = out0.shape
+    if bank.dim() != 2 or bank.shape[1] != d or bank.dtype != torch.float32 or not bank.is_contiguous():
+        raise HcirError(f"NTXentLoss memory bank must be a contiguous fp32 [K, {d}] tensor, got {tuple(bank.shape)} "
+                        f"{bank.dtype}")
+    k = bank.shape[0]
+    L = _lib.lib()
+    dt = _DT[out0.dtype]
+    ws = _ws.get(out0.device, L.hcir_ntxent_bank_workspace_bytes(n, k, d, dt, 0))
+    loss = torch.empty((), dtype=torch.float32, device=out0.device)
+    k_unit = torch.empty((n, d), dtype=torch.float32, device=out0.device)
+    lse = torch.empty(n, dtype=torch.float32, device=out0.device) if want_saved else None
+    pos = torch.empty(n, dtype=torch.float32, device=out0.device) if want_saved else None
+    check(L.hcir_ntxent_bank_fwd(out0.data_ptr(), out1.data_ptr(), bank.data_ptr(), n, k, d, dt, 1.0 / temperature,
+                                 loss.data_ptr(), None if lse is None else lse.data_ptr(),
+                                 None if pos is None else pos.data_ptr(), k_unit.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream(out0)), "hcir_ntxent_bank_fwd")
+    return (loss, k_unit, lse, pos) if want_saved else (loss, k_unit)
+
+
+def ntxent_bank_backward(out0, out1, bank, temperature, lse, pos, grad_out: float, want_dz1: bool = True):
+    """hcir_ntxent_bank_bwd: (dL/dout0, dL/dout1 or None) for the loss of ntxent_bank_forward on the same bank."""
+    n, d = out0.shape
+    k = bank.shape[0]
+    if k % 8:
+        raise HcirError("hcir_ntxent_bank_bwd needs a bank size that is a multiple of 8")
+    L = _lib.lib()
+    dt = _DT[out0.dtype]
+    ws = _ws.get(out0.device, L.hcir_ntxent_bank_workspace_bytes(n, k, d, dt, 1))
+    g0 = torch.empty_like(out0)
+    g1 = torch.empty_like(out1) if want_dz1 else None
+    check(L.hcir_ntxent_bank_bwd(out0.data_ptr(), out1.data_ptr(), bank.data_ptr(), n, k, d, dt, 1.0 / temperature,
+                                 lse.data_ptr(), pos.data_ptr(), float(grad_out), g0.data_ptr(),
+                                 None if g1 is None else g1.data_ptr(), ws.data_ptr(), ws.numel(), _stream(out0)),
+          "hcir_ntxent_bank_bwd")
+    return g0, g1
+
+
+class _NTXentBankFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out0, out1, bank, temperature):
+        out0, out1 = out0.contiguous(), out1.contiguous()
+        loss, k_unit, lse, pos = ntxent_bank_forward(out0, out1, bank, temperature, want_saved=True)
+        # the caller enqueues into `bank` right after this call: the backward needs the rows the loss was taken against
+        ctx.save_for_backward(out0, out1, bank.clone(), lse, pos)
+        ctx.temperature = temperature
+        ctx.mark_non_differentiable(k_unit)
+        return loss, k_unit
+
+    @staticmethod
+    def backward(ctx, grad, _grad_k_unit):
+        out0, out1, bank, lse, pos = ctx.saved_tensors
+        g0, g1 = ntxent_bank_backward(out0, out1, bank, ctx.temperature, lse, pos, float(grad),  # one host read of dL
+                                      want_dz1=ctx.needs_input_grad[1])
+        return g0, g1, None, None
+
+
+def bank_criterion(out0: torch.Tensor, out1: torch.Tensor, bank: torch.Tensor, temperature: float):
+    """(loss, k_unit) of NT-Xent against `bank`, differentiable in out0 / out1 where they require a gradient.  HIP
+    device only: there is no CPU path."""
+    if not out0.is_cuda:
+        raise HcirError(f"NTXentLoss got `out0` on {out0.device}; the loss runs on a HIP device only (no CPU fallback)")
+    if torch.is_grad_enabled() and (out0.requires_grad or out1.requires_grad):
+        if bank.shape[0] % 8:
+            raise HcirError("hcir_ntxent_bank_bwd needs a bank size that is a multiple of 8")
+        return _NTXentBankFn.apply(out0, out1, bank, temperature)
+    return ntxent_bank_forward(out0.contiguous(), out1.contiguous(), bank, temperature)
+
+
 class NTXentLoss(nn.Module):
-    """NTXentLoss(temperature=0.5, memory_bank_size=0, gather_distributed=False)."""
+    """NTXentLoss(temperature=0.5, memory_bank_size=0, gather_distributed=False).
+
+    memory_bank_size (K, D), or an int K with the width taken from the first call, adds lightly's memory bank (the two
+    criteria of the DenseCL step, HairPretraining/src/pretrain_engine.py:85-87): a non-persistent fp32 buffer `bank`
+    [K, D] of unit rows, initialised as F.normalize(torch.randn(K, D), dim=-1).  forward(out0, out1) is the
+    cross-entropy of [q_i.k_i, q_i.bank_0 ..] / T against the bank AS IT WAS BEFORE THE CALL (hcir_ntxent_bank_fwd /
+    _bwd); then, where out0 requires a gradient (lightly's `update`), the normalised rows of out1 are enqueued at
+    `bank_ptr`: if ptr + n >= K, bank[ptr:] = k[:K - ptr] and ptr = 0 (the rows that do not fit are dropped), else
+    bank[ptr:ptr + n] = k and ptr += n.  `bank_ptr` is a Python int: nothing is read back from the device."""
 
     def __init__(self, temperature: float = 0.5, memory_bank_size=0, gather_distributed: bool = False):
         super().__init__()
         if abs(temperature) < 1e-8:
             raise ValueError("Illegal temperature: abs({}) < 1e-8".format(temperature))
-        if memory_bank_size not in (0, (0, 0)):
-            raise NotImplementedError("memory bank is never enabled by the reference "
-                                      "(HP/src/pretrain_engine.py:74,93)")
         if gather_distributed:
             raise NotImplementedError("gather_distributed is never enabled by the reference "
                                       "(SURVEY.md §2.3)")
         self.temperature = temperature
+        self.bank_size = 0
+        self.bank_ptr = 0
+        self.register_buffer("bank", None, persistent=False)
+        if memory_bank_size not in (0, (0, 0)):
+            if isinstance(memory_bank_size, bool) or not isinstance(memory_bank_size, (int, tuple, list)):
+                raise ValueError(f"memory_bank_size must be an int K or a (K, D) pair, got {memory_bank_size!r}")
+            if isinstance(memory_bank_size, int):
+                size, dim = memory_bank_size, None
+            else:
+                if len(memory_bank_size) != 2 or not all(isinstance(v, int) and not isinstance(v, bool)
+                                                         for v in memory_bank_size):
+                    raise ValueError(f"memory_bank_size must be an int K or a (K, D) pair, got {memory_bank_size!r}")
+                size, dim = memory_bank_size
+            if size < 0 or (dim is not None and dim <= 0):
+                raise ValueError(f"Illegal memory bank size {memory_bank_size!r}")
+            self.bank_size = size
+            if dim is not None:
+                self._init_bank(dim, None)
+
+    def _init_bank(self, dim: int, device) -> None:
+        bank = torch.nn.functional.normalize(torch.randn(self.bank_size, dim), dim=-1)
+        self.bank = bank if device is None else bank.to(device)
+        self.bank_ptr = 0
+
+    def _enqueue(self, k_unit: torch.Tensor) -> None:
+        """lightly MemoryBankModule._dequeue_and_enqueue on rows (the bank is [K, D] here, [D, K] there)."""
+        n, size, ptr = k_unit.shape[0], self.bank_size, self.bank_ptr
+        with torch.no_grad():
+            if ptr + n >= size:
+                self.bank[ptr:] = k_unit[:size - ptr].detach()
+                self.bank_ptr = 0
+            else:
+                self.bank[ptr:ptr + n] = k_unit.detach()
+                self.bank_ptr = ptr + n
 
     def forward(self, out0: torch.Tensor, out1: torch.Tensor) -> torch.Tensor:
+        if self.bank_size:
+            if self.bank is None:
+                self._init_bank(out0.shape[-1], out0.device)
+            elif self.bank.device != out0.device:
+                self.bank = self.bank.to(out0.device)
+            loss, k_unit = bank_criterion(out0, out1, self.bank, self.temperature)
+            if out0.requires_grad:
+                self._enqueue(k_unit)
+            return loss
         if torch.is_grad_enabled() and (out0.requires_grad or out1.requires_grad):
             if out0.shape[0] % 4:
                 raise HcirError("hcir_ntxent_bwd needs a batch size that is a multiple of 4")

@@ -33,11 +33,13 @@ the hot path.
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, Optional
 
 import torch
 import torch.nn.functional as F
 
+from .dense import select_most_similar
 from .losses import NTXentLoss, SupConLoss
 from . import optim as hcir_optim
 from ._lib import HcirError
@@ -259,3 +261,66 @@ class SimMIMTrainStep:
             opt.step()
         opt.zero_grad()                                                                         # :530
         return {"loss": float(loss.detach())}
+
+
+def cosine_schedule(step: int, max_steps: int, start_value: float, end_value: float) -> float:
+    """lightly.utils.scheduler.cosine_schedule with its default period: the momentum of the DenseCL epoch,
+    cosine_schedule(epoch, epochs, 0.996, 1) (HairPretraining/src/pretrain_engine.py:283)."""
+    if step < 0 or max_steps < 1:
+        raise ValueError("cosine_schedule needs step >= 0 and max_steps >= 1")
+    if max_steps == 1:
+        return end_value
+    if step >= max_steps - 1:
+        return end_value
+    return end_value - (end_value - start_value) * (math.cos(math.pi * step / (max_steps - 1)) + 1) / 2
+
+
+class DenseCLTrainStep:
+    """The body of Trainer.train_one_epoch_densecl's batch loop (HairPretraining/src/pretrain_engine.py:284-315) for an
+    hcir.backbone.DenseCL model: the three update_momentum calls (hcir.momentum, one launch each), the query view
+    through the model and the key view through its momentum twins under fp16 autocast, the dense correspondence
+    (hcir.dense.select_most_similar, hcir_dense_match_f16), the two criteria NTXentLoss(temperature,
+    memory_bank_size=bank) on the [B, 512] global and the [B HW, 512] local rows (hcir_ntxent_bank_fwd / _bwd, each with
+    its own queue), loss = (1 - lam) global + lam local, then scaler.scale(loss).backward(); scaler.step; scaler.update;
+    zero_grad.  No gradient clipping: the reference does none here.  The caller supplies the epoch's `momentum`
+    (cosine_schedule(epoch, epochs, 0.996, 1)).  The optimizer is whatever it is given: the reference's DenseCL branch
+    (:109-115) names attributes this model does not have.  -> {"loss", "loss_global", "loss_local"}."""
+
+    def __init__(self, model, optimizer, scaler=None, temperature: float = 0.5, bank=(4096, 512), lam: float = 0.5):
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"lam weighs the local against the global loss and lies in [0, 1], got {lam}")
+        self.model = model
+        self.optimizer = optimizer
+        self.scaler = scaler
+        self.lam = lam
+        self.criterion_global = NTXentLoss(temperature=temperature, memory_bank_size=bank)      # :85
+        self.criterion_local = NTXentLoss(temperature=temperature, memory_bank_size=bank)       # :86
+
+    def __call__(self, batch: Dict[str, torch.Tensor], momentum: float = 0.996, **_loop_state) -> Dict[str, float]:
+        """One optimisation step on {'x_query', 'x_key'}: two views [B,3,H,W] of one image batch on the HIP device.
+        The loop variables SHAMTrainStep takes (epoch, batch_id, ...) are accepted and unused."""
+        model, opt, scaler = self.model, self.optimizer, self.scaler
+        model.train()                                                                           # :279
+        update_momentum(model.backbone, model.backbone_momentum, m=momentum)                    # :287-293
+        update_momentum(model.projection_head_global, model.projection_head_global_momentum, m=momentum)
+        update_momentum(model.projection_head_local, model.projection_head_local_momentum, m=momentum)
+        x_query, x_key = batch["x_query"], batch["x_key"]
+        with torch.autocast(device_type="cuda", dtype=torch.float16):                           # :285
+            query_features, query_global, query_local = model(x_query)                          # :297
+            key_features, key_global, key_local = model.forward_momentum(x_key)                 # :298
+        key_local = select_most_similar(query_features, key_features, key_local)                # :300
+        query_local = query_local.flatten(end_dim=1)                                            # :301-302
+        key_local = key_local.flatten(end_dim=1)
+        loss_global = self.criterion_global(query_global, key_global)                           # :304
+        loss_local = self.criterion_local(query_local, key_local)                               # :305
+        loss = (1 - self.lam) * loss_global + self.lam * loss_local                             # :306-307
+        if scaler is not None:                                                                  # :312-314
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
+        opt.zero_grad()                                                                         # :315
+        vals = torch.stack([loss.detach().float(), loss_global.detach(), loss_local.detach()]).tolist()   # one read
+        return dict(zip(("loss", "loss_global", "loss_local"), vals))

@@ -97,9 +97,17 @@ def build_model(args):
         if args.checkpoint_path:
             sd = load(args.checkpoint_path)     # a trainer dict, or the raw state_dict the reference's CLI loads
             model.load_state_dict(sd['model_state_dict'] if 'model_state_dict' in sd else sd)
+    elif args.mode == "DenseCL":
+        from torch import nn
+        from hcir import _tv_resnet
+        from hcir.backbone import DenseCL
+        resnet = _tv_resnet.resnet50(weights=None)                      # HP/knn_classification.py:165-171
+        model = DenseCL(nn.Sequential(*list(resnet.children())[:-2]))
+        if args.checkpoint_path:
+            model.load_state_dict(load(args.checkpoint_path)['model_state_dict'])
     else:
         raise SystemExit(f"--mode {args.mode}: this SSL baseline is outside the MI355X hot path "
-                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae, simMIM")
+                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae, simMIM, DenseCL")
     if args.checkpoint_path:
         print("Model weights loaded!")
     if getattr(args, "resnet_engine", "torch") == "hip" and hasattr(model, "hip_trunk"):

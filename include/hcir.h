@@ -185,6 +185,52 @@ int hcir_supcon_bwd(const void* feat, const int64_t* labels, int64_t b, int32_t 
                     float grad_out, void* dfeat, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * NT-Xent against a memory bank (lightly.loss.NTXentLoss(memory_bank_size=(K, D)); the two criteria of the DenseCL
+ * step, HairPretraining/src/pretrain_engine.py:85-87,309-312).
+ *   q_i = z0_i / max(||z0_i||, 1e-12),  k_i = z1_i / max(||z1_i||, 1e-12)                   i < N
+ *   logits_i = [ q_i.k_i , q_i.bank_0 , ... , q_i.bank_{K-1} ] * inv_t      bank rows as stored, not renormalised
+ *   loss = mean_i ( logsumexp(logits_i) - logits_i[0] )
+ * z0, z1 [N][D] in dtype; bank fp32 [K][D].  Outputs: loss (1 float); row_lse[N] and row_pos[N] (the positive logit),
+ * saved for the backward, either may be NULL; k_unit fp32 [N][D] (may be NULL): the normalised key rows, which are
+ * what a caller enqueues into the bank.  The N x (K + 1) logits are never materialised; no atomics, results are
+ * bit-identical from run to run.
+ * Backward: p_ij = exp(logit_ij - lse_i) (j = 0 the positive),
+ *   dq_i = grad_out * inv_t / N * (sum_j p_ij bank_j + (p_i0 - 1) k_i),  dk_i = grad_out * inv_t / N * (p_i0 - 1) q_i,
+ * through the normalisation's projection rn_i (g_i - (g_i.u_i) u_i); P is written once as fp16 [N][K] into the
+ * workspace and P.bank runs on hcir_gemm_f16.  dz1 may be NULL (a key without gradient): its work is skipped and dz0
+ * is the same bits.  The bank receives no gradient.
+ * hcir_ntxent_bank_workspace_bytes(..., backward): bytes for the forward (0) or the backward (1).
+ * Status: HCIR_ERR_INVALID for a null z0/z1/bank/loss (backward: z0/z1/bank/row_lse/row_pos/dz0), n, k, d <= 0,
+ * d % 8 != 0, n > 65535 * 128, inv_t == 0 or NaN, and for a backward with k % 8 != 0 (hcir_gemm_f16's rule for its
+ * inner dimension, which is the bank here; n is the GEMM's row count and is free); HCIR_ERR_UNSUPPORTED for a dtype other than HCIR_F32/F16/BF16; HCIR_ERR_WORKSPACE for a null or short
+ * workspace.  Nothing is written on an error.
+ * ------------------------------------------------------------------ */
+size_t hcir_ntxent_bank_workspace_bytes(int64_t n, int64_t k, int32_t d, int dtype, int backward);
+int hcir_ntxent_bank_fwd(const void* z0, const void* z1, const float* bank, int64_t n, int64_t k, int32_t d, int dtype,
+                         float inv_t, float* loss, float* row_lse, float* row_pos, float* k_unit, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int hcir_ntxent_bank_bwd(const void* z0, const void* z1, const float* bank, int64_t n, int64_t k, int32_t d, int dtype,
+                         float inv_t, const float* row_lse, const float* row_pos, float grad_out, void* dz0, void* dz1,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Dense matching (lightly.models.utils.select_most_similar; the DenseCL step,
+ * HairPretraining/src/pretrain_engine.py:304-306).  For image b and query position n:
+ *   j*(b, n) = argmax_m (x_bn . y_bm) / max(||y_bm||, 1e-12),   out[b][n] = y_values[b][j*(b, n)]
+ * x's own norm is a positive row constant and is not computed; a zero x row takes index 0.  On exact ties of the fp32
+ * scores the lowest m wins (torch.argmax).  x [B][N][C] and y [B][M][C] fp16 (a trunk's NHWC maps as they stand);
+ * y_values [B][M][Dv] in values_dtype (HCIR_F16 | HCIR_F32), may be NULL; idx int32 [B][N] is always written, out
+ * [B][N][Dv] in values_dtype when y_values is given.  Workspace: hcir_dense_match_workspace_bytes(b, m).
+ * Status: HCIR_ERR_INVALID for a null x/y/idx (or out with y_values), a size below 1, b > 65535;
+ * HCIR_ERR_UNSUPPORTED for n or m > 256, c % 8 != 0, dv % 8 != 0 or another values_dtype; HCIR_ERR_WORKSPACE for a
+ * null or short workspace.  Nothing is written on an error.
+ * ------------------------------------------------------------------ */
+size_t hcir_dense_match_workspace_bytes(int64_t b, int32_t m);
+int hcir_dense_match_f16(const void* x, const void* y, const void* y_values, int values_dtype, int64_t b, int32_t n,
+                         int32_t m, int32_t c, int32_t dv, int32_t* idx, void* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * ViT building blocks (fp16 MFMA, fp32 accumulate, fp32 residual stream).
  * ------------------------------------------------------------------ */
 

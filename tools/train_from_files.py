@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep, --mode simmim: SimMIMTrainStep) fed from an annotation CSV
-+ image directory, input on the device.
+"""An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep, --mode simmim: SimMIMTrainStep, --mode densecl:
+DenseCLTrainStep) fed from an annotation CSV + image directory, input on the device.
 
     python tools/train_from_files.py --csv data/data_train.csv --img-dir data/train --batch-size 1024
 
@@ -21,10 +21,12 @@ sys.path.insert(0, os.path.join(ROOT, "hair-centric-image-retrieval_amd"))
 
 
 def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, prev_margin_violations: float = 0.0,
-                on_step=None, with_labels: bool = False, view_kwargs=None):
+                on_step=None, with_labels: bool = False, view_kwargs=None, view_names=None, step_kwargs=None):
     """One pass over `loader` (batches are hcir.dataloader.TrainViewBatch).  -> list of the step's loss dicts.
     with_labels (--mode supcon): the batch's class labels travel with the views as views["labels"].
-    view_kwargs: keywords of hcir.views.simclr_views (min_scale, cj_prob, ...) for the batch's views."""
+    view_kwargs: keywords of hcir.views.simclr_views (min_scale, cj_prob, ...) for the batch's views.
+    view_names (--mode densecl): {"anchor": "x_query", "pos1": "x_key"} renames the two views for the step.
+    step_kwargs: further keywords of every step call (--mode densecl: the epoch's momentum)."""
     device = torch.device(device)
     side = torch.cuda.Stream(device=device)
     main = torch.cuda.current_stream(device)
@@ -32,6 +34,8 @@ def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, pre
     def produce(batch):   # enqueue only: nothing here waits for the device
         with torch.cuda.stream(side):
             views, check = batch.views(device, generator, defer_check=True, **(view_kwargs or {}))
+            if view_names:
+                views = {view_names.get(k, k): v for k, v in views.items()}
             if with_labels:
                 views["labels"] = batch.labels.to(device, non_blocking=True)
             return views, check
@@ -48,7 +52,8 @@ def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, pre
         nxt = next(it, None)
         pending = produce(nxt) if nxt is not None else None    # batch i + 1: runs beside the step below
         check()                               # batch i's decoder status (raises with the file names)
-        out = step(views, epoch=epoch, batch_id=batch_id, prev_margin_violations=prev_margin_violations)
+        out = step(views, epoch=epoch, batch_id=batch_id, prev_margin_violations=prev_margin_violations,
+                   **(step_kwargs or {}))
         results.append(out)
         if on_step is not None:
             on_step(batch_id, out)
@@ -66,14 +71,20 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--mode", choices=("sham", "supcon", "simmim"), default="sham",
+    ap.add_argument("--mode", choices=("sham", "supcon", "simmim", "densecl"), default="sham",
                     help="sham: the HSimCLR step (SHAMTrainStep).  supcon: the reference's simclr_supcon step "
                          "(SupConTrainStep) on the batch's class labels, with SHAM2(model) as encoder plus projection "
                          "head and SupConLoss(normalize=True); the reference's SupConResNet, a CIFAR-style trunk "
                          "(HairPretraining/src/backbone.py:276-358), is not built.  simmim: the reference's simMIM step "
                          "(SimMIMTrainStep) on SimMIM(vit_b_16), one view per image with lightly's MAETransform "
                          "settings (min_scale 0.2, flip, no colour jitter, grayscale or blur) on the device view "
-                         "kernel, which resamples bilinearly where MAETransform resamples bicubically")
+                         "kernel, which resamples bilinearly where MAETransform resamples bicubically.  densecl: the "
+                         "reference's DenseCL step (DenseCLTrainStep) on DenseCL(resnet50 trunk) - or the resnet18 "
+                         "trunk with --model resnet18 - with the two device SimCLR views as x_query / x_key; lightly's "
+                         "DenseCLTransform is not built")
+    ap.add_argument("--epoch", type=int, default=0, help="--mode densecl: the epoch of the momentum schedule")
+    ap.add_argument("--epochs", type=int, default=100,
+                    help="--mode densecl: momentum = cosine_schedule(epoch, epochs, 0.996, 1)")
     ap.add_argument("--max-steps", type=int, default=0)
     ap.add_argument("--hip-train", action="store_true",
                     help="ResNet models: body convolutions forward and backward on the HIP kernels (hcir.conv_train)")
@@ -93,7 +104,7 @@ def main():
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
-    from hcir.pretrain_engine import SHAMTrainStep, SimMIMTrainStep, SupConTrainStep
+    from hcir.pretrain_engine import DenseCLTrainStep, SHAMTrainStep, SimMIMTrainStep, SupConTrainStep, cosine_schedule
     torch.manual_seed(a.seed)
     ds = EncodedDataset(a.csv, a.img_dir, return_names=True)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, drop_last=True,
@@ -107,6 +118,22 @@ def main():
         from hcir._tv_vit import vit_b_16
         from hcir.backbone import SimMIM
         model = SimMIM(vit_b_16()).cuda()
+    elif a.mode == "densecl":
+        if a.model == "vit_b_16":
+            a.model = "resnet50"                  # the reference's DenseCL trunk (HP/mainpretrain.py:159-162)
+        if a.model not in ("resnet18", "resnet50"):
+            ap.error("--mode densecl trains a resnet18 or resnet50 trunk")
+        if a.fused_optim:
+            ap.error("--mode densecl steps with hcir.optim.Adam's plain step() under torch's GradScaler "
+                     "(DenseCLTrainStep: scaler.step / update); the fused tail is SHAMTrainStep's")
+        from torch import nn
+        from hcir import _tv_resnet
+        from hcir.backbone import DenseCL
+        trunk = nn.Sequential(*list(getattr(_tv_resnet, a.model)(weights=None).children())[:-2])
+        model = DenseCL(trunk, feature_dim=512 if a.model == "resnet18" else 2048).cuda()
+        model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
+        model.hip_train_norm = a.hip_train_norm
+        model.hip_train_stem = a.hip_train_stem
     else:
         model = SHAM2(a.model).cuda()
         model.hip_train = a.hip_train or a.hip_train_norm or a.hip_train_stem
@@ -115,12 +142,22 @@ def main():
     if a.fused_optim:
         from hcir import optim
         opt, scaler = optim.get_optimizer(model, a.lr, a.weight_decay, a.beta1, a.beta2), optim.GradScaler()
+    elif a.mode == "densecl":
+        # the reference's get_optimizer over the trainable parameters: hcir.optim.Adam, whose plain
+        # step() torch's GradScaler calls after its own unscale_; the frozen momentum twins are skipped
+        from hcir import optim
+        opt = optim.get_optimizer(model, a.lr, a.weight_decay, a.beta1, a.beta2)
+        scaler = torch.amp.GradScaler("cuda")
     else:
         opt, scaler = torch.optim.Adam(model.parameters(), lr=a.lr), torch.amp.GradScaler("cuda")
-    view_kwargs = None
+    view_kwargs = view_names = step_kwargs = None
     if a.mode == "simmim":
         step = SimMIMTrainStep(model, opt, scaler)
         view_kwargs = dict(min_scale=0.2, cj_prob=0.0, random_gray_scale=0.0, gaussian_blur=0.0)
+    elif a.mode == "densecl":
+        step = DenseCLTrainStep(model, opt, scaler)
+        view_names = {"anchor": "x_query", "pos1": "x_key"}
+        step_kwargs = dict(momentum=cosine_schedule(a.epoch, a.epochs, 0.996, 1))
     elif a.mode == "supcon":
         from hcir.losses import SupConLoss
         step = SupConTrainStep(model, opt, scaler, SupConLoss(normalize=True))
@@ -137,7 +174,8 @@ def main():
 
     try:
         train_epoch(step, loader, "cuda", torch.Generator().manual_seed(a.seed), on_step=report,
-                    with_labels=a.mode == "supcon", view_kwargs=view_kwargs)
+                    with_labels=a.mode == "supcon", view_kwargs=view_kwargs, view_names=view_names,
+                    step_kwargs=step_kwargs)
     except Stop:
         pass
 
