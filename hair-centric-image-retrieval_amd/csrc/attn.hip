@@ -20,7 +20,9 @@
 //                                     all waves.  Four waves (not one per query tile) keep two workgroups resident
 //                                     per CU, so one workgroup's K/V staging latency hides under the other's MFMAs.
 //   attn_fwd2_kernel                  head_dim 64, T in (192, 224], all query rows: persistent, double-buffered.
-//   attn_fwd_generic_kernel<HD, NKT>  any other head_dim: register-staged, plain images.
+//   attn_fwd_generic_kernel<HD, NKT>  any other head_dim: register-staged, plain images.  With head_dim 32 it also
+//                                     serves training (the MAE decoder): it writes the per-row log2-sum-exp in the
+//                                     layout and domain of the head_dim-64 kernels, behind the same row stores.
 // LDS images (KVImage): with head_dim 64, K rows are 128 B, 16-B slots XOR-swizzled with (key>>1)&7 (ds_read_b128
 // conflict-free); V rows are 128 B with the two 64-B halves swapped when key bit 1 is set (the 4-row x 32-col
 // transposed reads of a half-wave then cover all 64 banks).  The generic kernel's images are plain.
@@ -435,6 +437,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_generic_kernel(AttnArgs a) {
     attn_exp_pv<NKT, Img>(vs, sc, a.scale_log2e, mxs, grp, li, sum, oacc);
     sum += __shfl_xor(sum, 32);
     attn_store_rows_direct<HD>(attn_out_tile<HD>(a, b, head, q0), oacc, 1.0f / sum, r, h);
+    attn_store_lse(a, b, head, q0, r, h, mxs, sum);   // training (head_dim 32: the MAE decoder); a.lse is null otherwise
   }
 }
 
@@ -463,7 +466,9 @@ static int attn_fwd_launch(const void* qkv, int64_t b, int32_t t, int32_t h, int
   HCIR_ENTER();
   if (!qkv || !out || b <= 0 || t <= 0 || h <= 0 || nq <= 0 || nq > t) return HCIR_ERR_INVALID;
   if (t > 288) return HCIR_ERR_UNSUPPORTED;
-  if (hd != 64 && (lse || (hd != 32 && hd != 48 && hd != 80 && hd != 96 && hd != 128))) return HCIR_ERR_UNSUPPORTED;
+  // the log-sum-exp output exists where hcir_attn_bwd does: head_dim 64 and 32
+  if (hd != 64 && ((lse && hd != 32) || (hd != 32 && hd != 48 && hd != 80 && hd != 96 && hd != 128)))
+    return HCIR_ERR_UNSUPPORTED;
   if (b * h > 0x7fffffff) return HCIR_ERR_INVALID;
   AttnArgs a{static_cast<const _Float16*>(qkv), static_cast<_Float16*>(out), t, h, nq,
              scale * 1.44269504088896340736f, lse};

@@ -22,6 +22,8 @@
 // P is recomputed from the forward's per-row log2-sum-exp (hcir_attn_fwd_lse); D from dO and O at kernel start.
 // LDS: Q, dO, K images (3 x 32 KB), dS staging 16 KB, dQ slabs 4 x 8.3 KB, row constants 2 KB: 1 workgroup per CU.
 // The images carry the row-read swizzle only; transposed reads see some bank conflicts.
+// Both kernels here are head_dim 64; head_dim 32 (the MAE decoder) is attn_bwd32.hip, a separate kernel behind the
+// same entry point, so that these two keep the code and the registers they were measured with.
 #include <type_traits>
 
 #include "common.h"
@@ -670,8 +672,9 @@ extern "C" int hcir_attn_bwd(const void* qkv, const void* out, const void* d_out
                              int32_t t, int32_t h, int32_t hd, float scale, void* d_qkv, void* stream) {
   HCIR_ENTER();
   if (!qkv || !out || !d_out || !lse || !d_qkv || b <= 0 || t <= 0 || h <= 0) return HCIR_ERR_INVALID;
-  if (hd != 64 || t > kTP) return HCIR_ERR_UNSUPPORTED;
+  if ((hd != 64 && hd != 32) || t > kTP) return HCIR_ERR_UNSUPPORTED;
   if (b * h > 0x7fffffff) return HCIR_ERR_INVALID;
+  if (hd == 32) return hcir_attn_bwd32_launch(qkv, out, d_out, lse, b, t, h, scale, d_qkv, stream);   // attn_bwd32.hip
   AttnBwdArgs a{static_cast<const _Float16*>(qkv), static_cast<const _Float16*>(out),
                 static_cast<const _Float16*>(d_out), lse, static_cast<_Float16*>(d_qkv), t, h, scale,
                 scale * 1.44269504088896340736f};

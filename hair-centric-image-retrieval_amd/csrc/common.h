@@ -29,6 +29,11 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 static inline int64_t hcir_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// attn_bwd32.hip: the head_dim-32 arm of hcir_attn_bwd (its own translation unit; not part of the C ABI)
+__attribute__((visibility("hidden"))) int hcir_attn_bwd32_launch(const void* qkv, const void* out, const void* d_out,
+                                                                 const float* lse, int64_t b, int32_t t, int32_t h,
+                                                                 float scale, void* d_qkv, void* stream);
+
 // Row offset inside a 32x32 MFMA accumulator: register i of lane-half h holds
 // row (i&3) + 8*(i>>2) + 4*h, column lane&31 (cdna_hip_programming.md §3).
 __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }

@@ -9,21 +9,18 @@
 // All four are memory-bound passes.  No float atomics: partial sums go to a caller-provided workspace and are added in
 // a fixed order, so two runs give the same bits.  Every patch index read from device memory is range-checked before it
 // addresses the image; a row whose index is outside [1, t) is written as zero and adds nothing.
+#include "mim_patch.h"   // the image descriptor, the staged target patch, the workgroup sum (shared with mae.hip)
 #include "split_sum.h"
 
 namespace {
 
-constexpr int MIM_THREADS = 256;
 constexpr int MIM_BWD_ROWS = 64;       // fewest rows of one workgroup share of hcir_mim_mask_bwd
 constexpr int MIM_BWD_CHUNKS = 256;    // most shares
-constexpr int MIM_L1_BLOCKS = 1024;    // most workgroups of hcir_mim_l1_fwd
-constexpr int MIM_MAX_P = 12288;       // one patch in LDS: 48 KB
 
 __host__ __device__ inline int64_t mim_bwd_chunks(int64_t m) {
   const int64_t c = (m + MIM_BWD_ROWS - 1) / MIM_BWD_ROWS;
   return c < 1 ? 1 : (c > MIM_BWD_CHUNKS ? MIM_BWD_CHUNKS : c);
 }
-inline int64_t mim_l1_blocks(int64_t rows) { return rows < MIM_L1_BLOCKS ? rows : MIM_L1_BLOCKS; }
 
 // ---------------------------------------------------------------- mask tokens
 template <typename T>
@@ -119,34 +116,6 @@ __global__ __launch_bounds__(MIM_THREADS) void mim_mask_bwd_kernel(const float* 
 }
 
 // ---------------------------------------------------------------- patches of the image
-struct MimImage {
-  const float* img;
-  int c, h, w, ps, gw, npatch;   // gw: patches per image row; npatch = (h / ps) * gw
-};
-
-// Patch `p` (0-based) of image `bi` into LDS in lightly's element order: lds[(py * ps + px) * c + ch].  Image reads are
-// the ps contiguous floats of one patch row (64 B at ps = 16), 16 B per lane where ps % 4 == 0; the LDS writes have
-// stride c between lanes (conflict-free for c = 3).  The caller has checked p and puts barriers around the call.
-__device__ __forceinline__ void mim_stage_patch(const MimImage& im, int64_t bi, int p, float* lds) {
-  const int ps = im.ps, gy = p / im.gw, gx = p - gy * im.gw;
-  const float* base = im.img + (bi * im.c * im.h + (int64_t)gy * ps) * im.w + gx * ps;
-  if ((ps & 3) == 0) {
-    const int q4 = ps >> 2, per_c = ps * q4;
-    for (int u = threadIdx.x; u < im.c * per_c; u += MIM_THREADS) {
-      const int ch = u / per_c, rem = u - ch * per_c, py = rem / q4, px = (rem - py * q4) * 4;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(base + ((int64_t)ch * im.h + py) * im.w + px);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) lds[(py * ps + px + e) * im.c + ch] = v[e];
-    }
-  } else {
-    const int per_c = ps * ps;
-    for (int u = threadIdx.x; u < im.c * per_c; u += MIM_THREADS) {
-      const int ch = u / per_c, rem = u - ch * per_c, py = rem / ps, px = rem - py * ps;
-      lds[rem * im.c + ch] = base[((int64_t)ch * im.h + py) * im.w + px];
-    }
-  }
-}
-
 __global__ __launch_bounds__(MIM_THREADS) void mim_patch_targets_kernel(MimImage im, const int64_t* __restrict__ idx,
                                                                         int n, float* __restrict__ out) {
   extern __shared__ float lds[];
@@ -165,13 +134,6 @@ __global__ __launch_bounds__(MIM_THREADS) void mim_patch_targets_kernel(MimImage
 // Workgroup w takes the rows [w share, (w + 1) share).  A thread adds |pred - target| of its 8-element groups
 // (groups tid, tid + 256, ... of each row, elements in order, rows in order) into one fp32 accumulator; the 64 lanes of
 // a wave are added by the xor butterfly (offsets 32, 16, .., 1), the four waves in order; part[w] gets the sum.
-__device__ __forceinline__ float mim_block_sum(float v, float* wave_part) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
-}
-
 __global__ __launch_bounds__(MIM_THREADS) void mim_l1_kernel(const _Float16* __restrict__ pred, MimImage im,
                                                              const int64_t* __restrict__ idx, int n, int64_t rows,
                                                              int64_t share, _Float16* __restrict__ sgn,
@@ -208,25 +170,6 @@ __global__ __launch_bounds__(MIM_THREADS) void mim_l1_kernel(const _Float16* __r
   }
   const float tot = mim_block_sum(acc, wave_part);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-// loss = (sum of the parts) * inv_n: thread i adds the parts i, i + 256, ... in order, then the same block sum.
-__global__ __launch_bounds__(MIM_THREADS) void mim_l1_finish_kernel(const float* __restrict__ part, int nparts,
-                                                                    float inv_n, float* __restrict__ loss) {
-  __shared__ float wave_part[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nparts; i += MIM_THREADS) acc += part[i];
-  const float tot = mim_block_sum(acc, wave_part);
-  if (threadIdx.x == 0) *loss = tot * inv_n;
-}
-
-// shape rules shared by the two image readers: a status, and the image descriptor filled in
-int mim_image(const float* img, int64_t b, int32_t c, int32_t h, int32_t w, int32_t ps, int32_t n, MimImage* im) {
-  if (b <= 0 || c <= 0 || h <= 0 || w <= 0 || ps <= 0 || n <= 0 || h % ps || w % ps) return HCIR_ERR_INVALID;
-  const int64_t P = (int64_t)c * ps * ps, np = (int64_t)(h / ps) * (w / ps);
-  if (P % 8 || P > MIM_MAX_P || np >= (1 << 30) || b * n >= (int64_t)1 << 31) return HCIR_ERR_UNSUPPORTED;
-  *im = MimImage{img, c, h, w, ps, w / ps, (int)np};
-  return HCIR_OK;
 }
 
 }  // namespace

@@ -182,6 +182,14 @@ SIGNATURES = {
     "hcir_mim_l1_fwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
                                 c_vp]),
     "hcir_mim_l1_workspace_bytes": (c_sz, [c_i64]),
+    "hcir_mae_gather_rows": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "hcir_mae_scatter_rows": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "hcir_mae_decoder_input": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "hcir_mae_decoder_input_bwd": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_mae_decoder_input_bwd_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "hcir_mae_mse_fwd": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz,
+                                 c_vp]),
+    "hcir_mae_mse_workspace_bytes": (c_sz, [c_i64]),
 }
 
 

@@ -2,7 +2,9 @@
 with the reference's constructor signatures:
 
   SimCLR(model="resnet18")   HP/src/backbone.py:648-681  (the second definition, which wins)
-  MAE(vit)                   HP/src/backbone.py:462-525  (extract_features = encoder CLS)
+  MAE(vit)                   HP/src/backbone.py:462-525  (pre-training forward on the kept tokens + the head_dim-32
+                             decoder, fused masked-patch MSE loss, extract_features = encoder CLS; csrc/mae.hip,
+                             csrc/attn_bwd32.hip)
   vit_base_patch16_224()     timm ctor the CLI passes to MAE (HP/knn_classification.py:146-147)
   SimMIM(vit)                HP/src/backbone.py:549-601  (pre-training forward, fused masked-patch L1 loss and
                              extract_features; the torchvision vit_b_16 of hcir.vit_train / hcir.vit_engine with
@@ -20,6 +22,7 @@ from __future__ import annotations
 import copy
 from collections import OrderedDict
 from functools import partial
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -29,7 +32,8 @@ from . import conv_train
 from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper, deactivate_requires_grad
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
-from .vit_train import VitTrainer, vit_mim_l1_with_grad, vit_mim_with_grad
+from .vit_train import (MaeTrainer, VitTrainer, vit_mae_mse_with_grad, vit_mae_with_grad, vit_mim_l1_with_grad,
+                        vit_mim_with_grad)
 
 
 class SimCLR(HipTrunkSwitches, nn.Module):
@@ -104,19 +108,87 @@ class _MaskedViT(nn.Module):
         self.sequence_length = vit.patch_embed.num_patches + 1
 
 
-class MAE(nn.Module):
-    """MAE(vit): only the encoder half is on the hot path.  extract_features(images) ==
-    backbone.encode(images, idx_keep=None)[:, 0] (HP/src/backbone.py:523-525): timm forward
-    (patch_embed, cls, + pos_embed, blocks, final norm), CLS row.  The MAE decoder
-    (pre-training only) is not built; load checkpoints with strict=False."""
+class _MaeDecoder(nn.Module):
+    """lightly MAEDecoderTIMM, restated from its public sources (lightly is not installed: parity unpinned):
+    decoder_embed Linear(embed_dim, dd), mask_token [1, 1, dd], decoder_pos_embed [1, T, dd] (2-D sin-cos, class token
+    row zero, requires_grad=False), decoder_blocks = depth timm Blocks (qkv_bias, LayerNorm eps 1e-6), decoder_norm,
+    decoder_pred Linear(dd, patch_size^2 in_chans).  Initialisation as lightly's _initialize_weights: mask_token normal
+    std 0.02, Xavier-uniform Linear weights with zero biases, LayerNorm weights 1 and biases 0.  A parameter container:
+    the arithmetic is hcir.vit_train.MaeTrainer."""
 
-    def __init__(self, vit):
+    def __init__(self, num_patches, patch_size, in_chans=3, embed_dim=768, decoder_embed_dim=512, decoder_depth=8,
+                 decoder_num_heads=16, mlp_ratio=4.0):
+        super().__init__()
+        norm_layer = partial(nn.LayerNorm, eps=1e-6)
+        self.num_heads = decoder_num_heads
+        self.decoder_embed = nn.Linear(embed_dim, decoder_embed_dim, bias=True)
+        self.mask_token = nn.Parameter(torch.zeros(1, 1, decoder_embed_dim))
+        self.decoder_pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, decoder_embed_dim), requires_grad=False)
+        self.decoder_blocks = nn.Sequential(*[
+            models_vit.Block(decoder_embed_dim, decoder_num_heads, mlp_ratio, qkv_bias=True, norm_layer=norm_layer)
+            for _ in range(decoder_depth)])
+        self.decoder_norm = norm_layer(decoder_embed_dim)
+        self.decoder_pred = nn.Linear(decoder_embed_dim, patch_size ** 2 * in_chans, bias=True)
+        nn.init.normal_(self.mask_token, std=0.02)
+        side = int(round(num_patches ** 0.5))
+        if side * side == num_patches:
+            self.decoder_pos_embed.data.copy_(sincos_2d_pos_embed(decoder_embed_dim, side))
+        self.apply(self._init_weights)
+
+    @staticmethod
+    def _init_weights(m):
+        if isinstance(m, nn.Linear):
+            nn.init.xavier_uniform_(m.weight)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+
+def sincos_2d_pos_embed(dim: int, side: int) -> torch.Tensor:
+    """The fixed 2-D sine-cosine position table of MAE (lightly's initialize_2d_sine_cosine_positional_embedding with a
+    class token): [1, 1 + side^2, dim], row 0 zero; half the channels code one grid axis, half the other, each as
+    [sin(p w_i), cos(p w_i)] with w_i = 10000^(-i / (dim / 4))."""
+    if dim % 4:
+        raise ValueError("sin-cos position embedding needs dim % 4 == 0")
+    gh = torch.arange(side, dtype=torch.float64)
+    grid = torch.meshgrid(gh, gh, indexing="xy")          # grid[0]: the column of a patch, grid[1]: its row
+
+    def one_axis(pos):
+        omega = 1.0 / 10000 ** (torch.arange(dim // 4, dtype=torch.float64) / (dim / 4.0))
+        out = pos.reshape(-1)[:, None] * omega[None, :]
+        return torch.cat([out.sin(), out.cos()], 1)
+
+    emb = torch.cat([one_axis(grid[0]), one_axis(grid[1])], 1)
+    return torch.cat([torch.zeros(1, dim, dtype=torch.float64), emb], 0).unsqueeze(0).float()
+
+
+class MAE(nn.Module):
+    """MAE(vit) of HP/src/backbone.py:462-525 on the HIP path; `vit` is vit_base_patch16_224() (timm's layout).
+    State-dict keys are the reference's: backbone.vit.*, backbone.mask_token, decoder.* (lightly's MAEDecoderTIMM:
+    decoder_embed, mask_token, decoder_pos_embed, decoder_blocks.{i}.*, decoder_norm, decoder_pred).  The decoder
+    keywords are not reference arguments (it fixes 512 / 8 / 16); they let a test build a small model.
+
+      forward(images)          -> (x_pred [b, n, P], target [b, n, P]) as the reference (:505-521), differentiable
+      masked_loss(images)      -> nn.MSELoss()(x_pred, target) through hcir_mae_mse_fwd (the training step's path)
+      extract_features(images) -> backbone.encode(images, idx_keep=None)[:, 0] (:523-525): timm forward (patch_embed,
+                                  cls, + pos_embed, blocks, final norm), CLS row; inference-only
+    idx_keep / idx_mask (int64 [b, k] / [b, n], lightly's random_token_mask pair) may be passed to the first two; they
+    are validated here, on the host, before anything is launched: together they name every token of [0, T) once per
+    image, and token 0 is kept (the reference's idx_mask - 1 would wrap for a masked class token).
+    The encoder runs on the kept tokens only, the decoder (head_dim 32) on all of them: hcir.vit_train.MaeTrainer."""
+
+    def __init__(self, vit, decoder_dim=512, decoder_depth=8, decoder_num_heads=16):
         super().__init__()
         self.mask_ratio = 0.75
         self.patch_size = vit.patch_embed.patch_size[0]
         self.backbone = _MaskedViT(vit)
         self.sequence_length = self.backbone.sequence_length
         self._cache = EngineCache()
+        self.decoder = _MaeDecoder(num_patches=vit.patch_embed.num_patches, patch_size=self.patch_size,
+                                   embed_dim=vit.embed_dim, decoder_embed_dim=decoder_dim,
+                                   decoder_depth=decoder_depth, decoder_num_heads=decoder_num_heads, mlp_ratio=4.0)
 
     def _spec(self) -> VitSpec:
         vit = self.backbone.vit
@@ -124,8 +196,57 @@ class MAE(nn.Module):
         spec.final_ln_w, spec.final_ln_b = vit.norm.weight, vit.norm.bias
         return spec
 
-    def forward(self, images):
-        raise NotImplementedError("MAE pre-training (masking + decoder) is outside the retrieval hot path")
+    def _decoder_spec(self):
+        dec = self.decoder
+        layers = [VitLayer(ln1_w=blk.norm1.weight, ln1_b=blk.norm1.bias, qkv_w=blk.attn.qkv.weight,
+                           qkv_b=blk.attn.qkv.bias, proj_w=blk.attn.proj.weight, proj_b=blk.attn.proj.bias,
+                           ln2_w=blk.norm2.weight, ln2_b=blk.norm2.bias, fc1_w=blk.mlp.fc1.weight,
+                           fc1_b=blk.mlp.fc1.bias, fc2_w=blk.mlp.fc2.weight, fc2_b=blk.mlp.fc2.bias)
+                  for blk in dec.decoder_blocks]
+        return SimpleNamespace(embed_w=dec.decoder_embed.weight, embed_b=dec.decoder_embed.bias,
+                               mask_token=dec.mask_token, pos=dec.decoder_pos_embed, layers=layers,
+                               heads=dec.num_heads, eps=dec.decoder_norm.eps, norm_w=dec.decoder_norm.weight,
+                               norm_b=dec.decoder_norm.bias, pred_w=dec.decoder_pred.weight,
+                               pred_b=dec.decoder_pred.bias)
+
+    def trainer(self, device: torch.device) -> MaeTrainer:
+        tr = getattr(self, "_trainer", None)
+        if tr is None or tr.device != device:
+            tr = MaeTrainer(self._spec(), self._decoder_spec(), device)
+            self._trainer = tr
+        return tr
+
+    def _indices(self, images, idx_keep, idx_mask):
+        """The index pair of a call: drawn here (trusted), or the caller's, checked on the host."""
+        b, seq = images.shape[0], self.sequence_length
+        if idx_keep is None and idx_mask is None:
+            keep, mask = random_token_mask((b, seq), self.mask_ratio, device=images.device)
+            return keep.contiguous(), mask.contiguous()
+        for name, idx in (("idx_keep", idx_keep), ("idx_mask", idx_mask)):
+            if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != b:
+                raise ValueError(f"{name} must be an int64 tensor [{b}, k] (pass both or neither)")
+        if idx_mask.shape[1] == 0:
+            raise ValueError("no masked token: the loss over zero elements is undefined")
+        both = torch.cat([idx_keep, idx_mask.to(idx_keep.device)], 1)
+        if both.shape[1] != seq or not bool((both.sort(dim=1).values == torch.arange(seq, device=both.device)).all()):
+            raise ValueError(f"idx_keep and idx_mask must together name every token of [0, {seq}) once per image")
+        if not bool((idx_keep == 0).any(dim=1).all()):
+            raise ValueError("token 0 (the class token) must be in idx_keep: it has no target patch")
+        return idx_keep.to(images.device).contiguous(), idx_mask.to(images.device).contiguous()
+
+    def forward(self, images, idx_keep=None, idx_mask=None):
+        idx_keep, idx_mask = self._indices(images, idx_keep, idx_mask)                            # :507-511
+        images = images.float().contiguous()
+        x_pred = vit_mae_with_grad(self.trainer(images.device), images, idx_keep, idx_mask)      # :512-515
+        b, n = idx_mask.shape
+        target = train_ops.mim_patch_targets(images, idx_mask, self.patch_size).view(b, n, -1)   # :518-520
+        return x_pred, target
+
+    def masked_loss(self, images, idx_keep=None, idx_mask=None):
+        """criterion(*model(images)) of the reference's step (nn.MSELoss, HP/src/pretrain_engine.py:330-331) as one
+        differentiable 0-d loss: the target is never stored, the backward runs on the differences."""
+        idx_keep, idx_mask = self._indices(images, idx_keep, idx_mask)
+        return vit_mae_mse_with_grad(self.trainer(images.device), images, idx_keep, idx_mask)
 
     def extract_features(self, images):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -263,6 +263,36 @@ class SimMIMTrainStep:
         return {"loss": float(loss.detach())}
 
 
+class MAETrainStep:
+    """The body of Trainer.train_one_epoch_mae's batch loop (HairPretraining/src/pretrain_engine.py:323-338) for an
+    hcir.backbone.MAE model: one view per image, `predictions, targets = model(images)` and
+    `criterion(predictions, targets)` (nn.MSELoss) as the model's fused masked_loss (the masked-encoder / decoder walk,
+    then hcir_mae_mse_fwd; the backward runs on the differences), then scaler.scale(loss).backward(); scaler.step;
+    scaler.update; zero_grad.  No gradient clipping: the reference does none here.  -> {"loss": float}."""
+
+    def __init__(self, model, optimizer, scaler=None):
+        self.model = model
+        self.optimizer = optimizer
+        self.scaler = scaler
+
+    def __call__(self, batch, **_loop_state) -> Dict[str, float]:
+        """One optimisation step on an image batch [B,3,H,W] on the HIP device, or on a dict of views whose 'anchor'
+        is that batch.  The loop variables SHAMTrainStep takes (epoch, batch_id, ...) are accepted and unused."""
+        model, opt, scaler = self.model, self.optimizer, self.scaler
+        model.train()
+        images = batch["anchor"] if isinstance(batch, dict) else batch                          # :328-329
+        loss = model.masked_loss(images)                                                        # :330-331
+        if scaler is not None:                                                                  # :334-337
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
+        opt.zero_grad()                                                                         # :338
+        return {"loss": float(loss.detach())}
+
+
 def cosine_schedule(step: int, max_steps: int, start_value: float, end_value: float) -> float:
     """lightly.utils.scheduler.cosine_schedule with its default period: the momentum of the DenseCL epoch,
     cosine_schedule(epoch, epochs, 0.996, 1) (HairPretraining/src/pretrain_engine.py:283)."""

@@ -178,30 +178,38 @@ def gemm_tn(a16: torch.Tensor, b16: torch.Tensor, dw: torch.Tensor, accumulate: 
           "hcir_gemm_f16_tn")
 
 
+def _head_dim(qkv: torch.Tensor, heads: int) -> int:
+    """Head dim of a packed [rows, 3 * heads * hd] (or [b, t, 3 * heads * hd]) qkv buffer: its last axis; the C entry
+    points decide which they support (64 and, for the full-row pair, 32)."""
+    return qkv.shape[-1] // (3 * heads)
+
+
 def attn_fwd_lse(qkv: torch.Tensor, b: int, t: int, heads: int, scale: float, out: torch.Tensor,
                  lse: torch.Tensor) -> None:
-    check(_lib.lib().hcir_attn_fwd_lse(qkv.data_ptr(), b, t, heads, 64, float(scale), out.data_ptr(), lse.data_ptr(),
-                                       _stream(qkv)), "hcir_attn_fwd_lse")
+    check(_lib.lib().hcir_attn_fwd_lse(qkv.data_ptr(), b, t, heads, _head_dim(qkv, heads), float(scale),
+                                       out.data_ptr(), lse.data_ptr(), _stream(qkv)), "hcir_attn_fwd_lse")
 
 
 def attn_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, lse: torch.Tensor, b: int, t: int, heads: int,
              scale: float, d_qkv: torch.Tensor) -> None:
-    check(_lib.lib().hcir_attn_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), b, t, heads, 64,
-                                   float(scale), d_qkv.data_ptr(), _stream(qkv)), "hcir_attn_bwd")
+    check(_lib.lib().hcir_attn_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), b, t, heads,
+                                   _head_dim(qkv, heads), float(scale), d_qkv.data_ptr(), _stream(qkv)),
+          "hcir_attn_bwd")
 
 
 def attn_cls_fwd_lse(qkv: torch.Tensor, b: int, t: int, heads: int, scale: float, out: torch.Tensor,
                      lse: torch.Tensor) -> None:
     """attn_fwd_lse for the class-token query of every image: out [b, heads*64], lse [b, heads]."""
-    check(_lib.lib().hcir_attn_cls_fwd_lse(qkv.data_ptr(), b, t, heads, 64, float(scale), out.data_ptr(),
-                                           lse.data_ptr(), _stream(qkv)), "hcir_attn_cls_fwd_lse")
+    check(_lib.lib().hcir_attn_cls_fwd_lse(qkv.data_ptr(), b, t, heads, _head_dim(qkv, heads), float(scale),
+                                           out.data_ptr(), lse.data_ptr(), _stream(qkv)), "hcir_attn_cls_fwd_lse")
 
 
 def attn_cls_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tensor, lse: torch.Tensor, b: int, t: int,
                  heads: int, scale: float, d_qkv: torch.Tensor) -> None:
     """Its backward: d_qkv gets dK, dV of every token, dQ of token 0 and zero for the other tokens' dQ."""
     check(_lib.lib().hcir_attn_cls_bwd(qkv.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(), b, t, heads,
-                                       64, float(scale), d_qkv.data_ptr(), _stream(qkv)), "hcir_attn_cls_bwd")
+                                       _head_dim(qkv, heads), float(scale), d_qkv.data_ptr(), _stream(qkv)),
+          "hcir_attn_cls_bwd")
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -271,6 +279,89 @@ def mim_l1_fwd(pred: torch.Tensor, img: torch.Tensor, idx: torch.Tensor, ps: int
     check(L.hcir_mim_l1_fwd(pred.data_ptr(), img.data_ptr(), b, c, h, w, ps, idx.data_ptr(), n, loss.data_ptr(),
                             sgn.data_ptr(), ws.data_ptr(), ws.numel(), _stream(img)), "hcir_mim_l1_fwd")
     return loss, sgn
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# MAE (csrc/mae.hip): the token kernels of the masked-encoder / decoder walk and the masked-patch MSE loss
+# ---------------------------------------------------------------------------------------------------------------
+def _mae_idx(idx: torch.Tensor, b: int, name: str) -> int:
+    _dev(idx, name)
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != b or not idx.is_contiguous():
+        raise HcirError(f"{name}: contiguous int64 [b, k]")
+    return idx.shape[1]
+
+
+def mae_gather_rows(tok: torch.Tensor, b: int, t: int, idx: torch.Tensor, out: torch.Tensor) -> None:
+    """out[i k + j] = tok[i t + idx[i][j]] for fp16 tok [>= b t, d] -> fp16 out [pad64(b k), d], pad rows zero."""
+    _dev(tok, "tok")
+    _dev(out, "out")
+    k, d = _mae_idx(idx, b, "idx"), tok.shape[1]
+    if tok.dtype != torch.float16 or out.dtype != torch.float16 or tok.shape[0] < b * t \
+            or tuple(out.shape) != ((b * k + 63) // 64 * 64, d):
+        raise HcirError("mae_gather_rows: fp16 tok [>= b t, d] and fp16 out [pad64(b k), d]")
+    check(_lib.lib().hcir_mae_gather_rows(tok.data_ptr(), b, t, d, idx.data_ptr(), k, out.data_ptr(), _stream(tok)),
+          "hcir_mae_gather_rows")
+
+
+def mae_scatter_rows(comp: torch.Tensor, b: int, t: int, idx: torch.Tensor, dtok: torch.Tensor) -> None:
+    """dtok[i t + idx[i][j]] = comp[i k + j], every other row of the first b t of dtok zero (fp32, both)."""
+    _dev(comp, "comp")
+    _dev(dtok, "dtok")
+    k, d = _mae_idx(idx, b, "idx"), comp.shape[1]
+    if comp.dtype != torch.float32 or dtok.dtype != torch.float32 or comp.shape[0] < b * k or dtok.shape[0] < b * t \
+            or dtok.shape[1] != d:
+        raise HcirError("mae_scatter_rows: fp32 comp [>= b k, d] and fp32 dtok [>= b t, d]")
+    check(_lib.lib().hcir_mae_scatter_rows(comp.data_ptr(), b, t, d, idx.data_ptr(), k, dtok.data_ptr(),
+                                           _stream(comp)), "hcir_mae_scatter_rows")
+
+
+def mae_decoder_input(embed: torch.Tensor, b: int, t: int, idx_keep: torch.Tensor, mask_token: torch.Tensor,
+                      pos: torch.Tensor, x: torch.Tensor) -> None:
+    """x[i t + tok] = fp16((tok kept at j ? embed[i k + j] : mask_token) + pos[tok]) for every token of every image."""
+    for v, nm in ((embed, "embed"), (mask_token, "mask_token"), (pos, "pos"), (x, "x")):
+        _dev(v, nm)
+    k, d = _mae_idx(idx_keep, b, "idx_keep"), mask_token.numel()
+    if embed.dtype != torch.float16 or x.dtype != torch.float16 or mask_token.dtype != torch.float32 \
+            or pos.dtype != torch.float32 or embed.shape[0] < b * k or x.shape[0] < b * t or pos.numel() != t * d \
+            or embed.shape[1] != d or x.shape[1] != d:
+        raise HcirError("mae_decoder_input: fp16 embed [>= b k, d], fp32 mask_token [d] and pos [t, d], fp16 x [>= b t, d]")
+    check(_lib.lib().hcir_mae_decoder_input(embed.data_ptr(), b, t, d, idx_keep.data_ptr(), k, mask_token.data_ptr(),
+                                            pos.data_ptr(), x.data_ptr(), _stream(x)), "hcir_mae_decoder_input")
+
+
+def mae_decoder_input_bwd(dres: torch.Tensor, b: int, t: int, idx_keep: torch.Tensor, d_embed: torch.Tensor,
+                          g_mask_token: torch.Tensor) -> None:
+    """d_embed[i k + j] = fp16(dres[i t + idx_keep[i][j]]) (rows past b k untouched); g_mask_token[d] = the sum of the
+    rows of dres (fp32 [>= b t, d]) whose token is not kept."""
+    for v, nm in ((dres, "dres"), (d_embed, "d_embed"), (g_mask_token, "g_mask_token")):
+        _dev(v, nm)
+    k, d = _mae_idx(idx_keep, b, "idx_keep"), g_mask_token.numel()
+    if dres.dtype != torch.float32 or d_embed.dtype != torch.float16 or g_mask_token.dtype != torch.float32 \
+            or dres.shape[0] < b * t or d_embed.shape[0] < b * k or dres.shape[1] != d or d_embed.shape[1] != d:
+        raise HcirError("mae_decoder_input_bwd: fp32 dres [>= b t, d], fp16 d_embed [>= b k, d], fp32 g_mask_token [d]")
+    L = _lib.lib()
+    ws = _ws.get(dres.device, L.hcir_mae_decoder_input_bwd_workspace_bytes(b, d))
+    check(L.hcir_mae_decoder_input_bwd(dres.data_ptr(), b, t, d, idx_keep.data_ptr(), k, d_embed.data_ptr(),
+                                       g_mask_token.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dres)),
+          "hcir_mae_decoder_input_bwd")
+
+
+def mae_mse_fwd(pred: torch.Tensor, img: torch.Tensor, idx: torch.Tensor, ps: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean (pred - patchify(img)[idx - 1])^2 as a 0-d fp32 tensor, fp16(pred - target) as [pad64(b n), P] with zero
+    pad rows: the operand the backward walk takes); pred fp16, at least b n rows of P."""
+    (b, c, h, w), n = _mim_image_args(img, idx)
+    _dev(pred, "pred")
+    p = c * ps * ps
+    if pred.dtype != torch.float16 or pred.dim() != 2 or pred.shape[1] != p or pred.shape[0] < b * n:
+        raise HcirError(f"mae_mse_fwd: pred fp16 [>= {b * n}, {p}], got {tuple(pred.shape)} {pred.dtype}")
+    loss = torch.empty((), dtype=torch.float32, device=img.device)
+    diff = torch.empty(((b * n + 63) // 64 * 64, p), dtype=torch.float16, device=img.device)
+    diff[b * n:].zero_()
+    L = _lib.lib()
+    ws = _ws.get(img.device, L.hcir_mae_mse_workspace_bytes(b * n))
+    check(L.hcir_mae_mse_fwd(pred.data_ptr(), img.data_ptr(), b, c, h, w, ps, idx.data_ptr(), n, loss.data_ptr(),
+                             diff.data_ptr(), ws.data_ptr(), ws.numel(), _stream(img)), "hcir_mae_mse_fwd")
+    return loss, diff
 
 
 # ---------------------------------------------------------------------------------------------------------------

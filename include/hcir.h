@@ -602,15 +602,19 @@ int hcir_gemm_f16_tn(const void* a, int64_t lda, const void* b, int64_t ldb, int
 
 /* Training forward of the attention: hcir_attn_fwd for all T query rows that also writes, per (b, head, query),
  * lse[b][h][q] = log2 sum_k exp2((s_qk - max) scale log2e) + max scale log2e  (log2 domain), from which the
- * backward recomputes P = exp2(s scale log2e - lse). */
+ * backward recomputes P = exp2(s scale log2e - lse).  hd == 64, or hd == 32 (the MAE decoder, 512 / 16 heads:
+ * HairPretraining/src/backbone.py:472-482) on the generic kernel, whose `out` is bit-equal to hcir_attn_fwd's; any
+ * other head_dim: HCIR_ERR_UNSUPPORTED. */
 int hcir_attn_fwd_lse(const void* qkv, int64_t b, int32_t t, int32_t h, int32_t hd, float scale, void* out,
                       float* lse, void* stream);
 
-/* Backward of hcir_attn_fwd over packed qkv [B][T][3][H][64] (fp16): given the forward output `out` [B][T][H*64],
- * its gradient d_out (fp16) and lse, writes d_qkv [B][T][3][H][64] (fp16):
+/* Backward of hcir_attn_fwd over packed qkv [B][T][3][H][hd] (fp16): given the forward output `out` [B][T][H*hd],
+ * its gradient d_out (fp16) and lse, writes d_qkv [B][T][3][H][hd] (fp16):
  *   P = softmax(scale q k^T);  dV = P^T dO;  dP = dO V^T;  dS = P o (dP - rowsum(dO o O));
  *   dQ = scale dS K;  dK = scale dS^T Q.
- * Requirements: hd == 64, T <= 256.  (HP/src/models_vit.py:69-78; nn.MultiheadAttention.) */
+ * Requirements: hd == 64 or hd == 32, T <= 256.  (HP/src/models_vit.py:69-78; nn.MultiheadAttention; hd 32: the timm
+ * blocks of lightly's MAEDecoderTIMM, HairPretraining/src/backbone.py:472-482, a separate kernel - attn_bwd32.hip.)
+ * No atomics, fixed summation orders: two runs give the same bits. */
 int hcir_attn_bwd(const void* qkv, const void* out, const void* d_out, const float* lse, int64_t b, int32_t t,
                   int32_t h, int32_t hd, float scale, void* d_qkv, void* stream);
 
@@ -1118,6 +1122,50 @@ int hcir_mim_l1_fwd(const void* pred, const float* img, int64_t b, int32_t c, in
                     void* stream);
 /* HOST.  blocks * 4 bytes for rows = b n. */
 size_t hcir_mim_l1_workspace_bytes(int64_t rows);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * MAE pre-training (csrc/mae.hip; HairPretraining/src/backbone.py:462-525, src/pretrain_engine.py:323-338).  Token
+ * indices are int64 [b][k], distinct per image, in [0, t); a compact buffer has row i k + j for (image i, idx[i][j]).
+ * Shapes: d % 8 == 0, t <= 1024, 1 <= k <= t (else HCIR_ERR_UNSUPPORTED / HCIR_ERR_INVALID).  An index outside [0, t)
+ * addresses nothing: its compact row is written as zero / ignored.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* out[i k + j][:] = tok[i][idx[i][j]][:] for fp16 tok [b t][d] -> fp16 out [pad64(b k)][d], pad rows written as zero.
+ * A copy: bit-exact.  lightly's get_at_index: MaskedVisionTransformerTIMM.encode(images, idx_keep), which
+ * backbone.py:484-486 calls, and get_at_index(x_decoded, idx_mask) at backbone.py:501. */
+int hcir_mae_gather_rows(const void* tok, int64_t b, int32_t t, int32_t d, const int64_t* idx, int32_t k, void* out,
+                         void* stream);
+/* Its backward: dtok[i][tok][:] = comp[i k + j][:] where idx[i][j] == tok, 0 for every other token; fp32 comp
+ * [>= b k][d] -> fp32 dtok [b t][d].  EVERY row of dtok is written (no fill in front).  Bit-exact.  (autograd through
+ * the two get_at_index calls above, pretrain_engine.py:334.) */
+int hcir_mae_scatter_rows(const float* comp, int64_t b, int32_t t, int32_t d, const int64_t* idx, int32_t k,
+                          float* dtok, void* stream);
+/* x[i][tok][:] = fp16((tok in idx_keep[i] at j ? fp32(embed[i k + j][:]) : mask_token[:]) + pos[tok][:]): the decoder's
+ * input, built in one pass.  embed fp16 [>= b k][d] (decoder_embed of the encoder output), mask_token fp32 [d], pos fp32
+ * [t][d] (decoder_pos_embed), x fp16 [b t][d].  One fp32 add and one rounding to fp16 per element.
+ * (repeat_token / set_at_index at backbone.py:492-495 and MAEDecoderTIMM.decode's position add behind :498.) */
+int hcir_mae_decoder_input(const void* embed, int64_t b, int32_t t, int32_t d, const int64_t* idx_keep, int32_t k,
+                           const float* mask_token, const float* pos, void* x, void* stream);
+/* Its backward, from the fp32 gradient dres [b t][d] of x: d_embed[i k + j][:] = fp16(dres[i][idx_keep[i][j]][:]) (rows
+ * past b k are not touched) and g_mask_token[:] = the sum of the rows whose token is not in idx_keep, in a fixed order:
+ * chunks = min(b, 256) shares of ceil(b / chunks) consecutive images; inside a share 8 row lanes (token % 8) add their
+ * rows image by image in order, the lanes are added in order, then the shares in order.  decoder_pos_embed takes no
+ * gradient (requires_grad=False in lightly).  workspace: hcir_mae_decoder_input_bwd_workspace_bytes. */
+int hcir_mae_decoder_input_bwd(const float* dres, int64_t b, int32_t t, int32_t d, const int64_t* idx_keep, int32_t k,
+                               void* d_embed, float* g_mask_token, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* HOST.  chunks * d * 4 bytes; 0 for a shape without a kernel. */
+size_t hcir_mae_decoder_input_bwd_workspace_bytes(int64_t b, int32_t d);
+/* loss = mean over all b n P elements of (pred - target)^2 (fp32 device scalar; nn.MSELoss, the criterion of
+ * train_one_epoch_mae, pretrain_engine.py:331) and diff = fp16(pred - target) (fp16 [b n][P]), target =
+ * patchify(img)[idx - 1] as hcir_mim_patch_targets writes it (backbone.py:518-520), read from the image and never
+ * stored.  pred fp16 [b n][P].  The difference is one fp32 subtraction, the sum takes it by fma (the square is not
+ * rounded); plan and summation order are hcir_mim_l1_fwd's.  The gradient of the loss is 2 grad_out / (b n P) * diff:
+ * there is no backward kernel. */
+int hcir_mae_mse_fwd(const void* pred, const float* img, int64_t b, int32_t c, int32_t h, int32_t w, int32_t ps,
+                     const int64_t* idx, int32_t n, float* loss, void* diff, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* HOST.  blocks * 4 bytes for rows = b n. */
+size_t hcir_mae_mse_workspace_bytes(int64_t rows);
 
 #ifdef __cplusplus
 }

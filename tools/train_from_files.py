@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep, --mode simmim: SimMIMTrainStep, --mode densecl:
-DenseCLTrainStep) fed from an annotation CSV + image directory, input on the device.
+DenseCLTrainStep, --mode mae: MAETrainStep) fed from an annotation CSV + image directory, input on the device.
 
     python tools/train_from_files.py --csv data/data_train.csv --img-dir data/train --batch-size 1024
 
@@ -61,7 +61,7 @@ def train_epoch(step, loader, device="cuda", generator=None, epoch: int = 0, pre
     return results
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--csv", required=True)
     ap.add_argument("--img-dir", required=True)
@@ -71,7 +71,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--mode", choices=("sham", "supcon", "simmim", "densecl"), default="sham",
+    ap.add_argument("--mode", choices=("sham", "supcon", "simmim", "densecl", "mae"), default="sham",
                     help="sham: the HSimCLR step (SHAMTrainStep).  supcon: the reference's simclr_supcon step "
                          "(SupConTrainStep) on the batch's class labels, with SHAM2(model) as encoder plus projection "
                          "head and SupConLoss(normalize=True); the reference's SupConResNet, a CIFAR-style trunk "
@@ -81,7 +81,9 @@ def main():
                          "kernel, which resamples bilinearly where MAETransform resamples bicubically.  densecl: the "
                          "reference's DenseCL step (DenseCLTrainStep) on DenseCL(resnet50 trunk) - or the resnet18 "
                          "trunk with --model resnet18 - with the two device SimCLR views as x_query / x_key; lightly's "
-                         "DenseCLTransform is not built")
+                         "DenseCLTransform is not built.  mae: the reference's mae step (MAETrainStep) on "
+                         "MAE(vit_base_patch16_224()), one view per image exactly as --mode simmim gives it (the device "
+                         "view kernel stands in for lightly's MAETransform)")
     ap.add_argument("--epoch", type=int, default=0, help="--mode densecl: the epoch of the momentum schedule")
     ap.add_argument("--epochs", type=int, default=100,
                     help="--mode densecl: momentum = cosine_schedule(epoch, epochs, 0.996, 1)")
@@ -101,10 +103,16 @@ def main():
     ap.add_argument("--weight-decay", type=float, default=1e-4, help="with --fused-optim (reference default)")
     ap.add_argument("--beta1", type=float, default=0.9, help="with --fused-optim (reference default)")
     ap.add_argument("--beta2", type=float, default=0.999, help="with --fused-optim (reference default)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
-    from hcir.pretrain_engine import DenseCLTrainStep, SHAMTrainStep, SimMIMTrainStep, SupConTrainStep, cosine_schedule
+    from hcir.pretrain_engine import (DenseCLTrainStep, MAETrainStep, SHAMTrainStep, SimMIMTrainStep, SupConTrainStep,
+                                      cosine_schedule)
     torch.manual_seed(a.seed)
     ds = EncodedDataset(a.csv, a.img_dir, return_names=True)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, drop_last=True,
@@ -118,6 +126,13 @@ def main():
         from hcir._tv_vit import vit_b_16
         from hcir.backbone import SimMIM
         model = SimMIM(vit_b_16()).cuda()
+    elif a.mode == "mae":
+        if a.model not in ("vit_b_16", "vit_base_patch16_224"):
+            ap.error("--mode mae trains the timm vit_base_patch16_224 (HairPretraining/mainpretrain.py)")
+        if a.fused_optim:
+            ap.error("--mode mae steps with torch's Adam and GradScaler (MAETrainStep: scaler.step / update)")
+        from hcir.backbone import MAE, vit_base_patch16_224
+        model = MAE(vit_base_patch16_224()).cuda()
     elif a.mode == "densecl":
         if a.model == "vit_b_16":
             a.model = "resnet50"                  # the reference's DenseCL trunk (HP/mainpretrain.py:159-162)
@@ -153,6 +168,9 @@ def main():
     view_kwargs = view_names = step_kwargs = None
     if a.mode == "simmim":
         step = SimMIMTrainStep(model, opt, scaler)
+        view_kwargs = dict(min_scale=0.2, cj_prob=0.0, random_gray_scale=0.0, gaussian_blur=0.0)
+    elif a.mode == "mae":
+        step = MAETrainStep(model, opt, scaler)
         view_kwargs = dict(min_scale=0.2, cj_prob=0.0, random_gray_scale=0.0, gaussian_blur=0.0)
     elif a.mode == "densecl":
         step = DenseCLTrainStep(model, opt, scaler)
