@@ -61,6 +61,12 @@ SIGNATURES = {
                                      c_sz, c_vp]),
     "hcir_ntxent_bank_bwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_int, c_f32, c_vp, c_vp, c_f32, c_vp, c_vp,
                                      c_vp, c_sz, c_vp]),
+    "hcir_msn_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32, c_int, c_int]),
+    "hcir_msn_targets": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_int, c_f32, c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "hcir_msn_fwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_int, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp,
+                             c_vp, c_sz, c_vp]),
+    "hcir_msn_bwd": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_int, c_f32, c_f32, c_vp, c_vp, c_f32, c_vp,
+                             c_vp, c_sz, c_vp]),
     "hcir_dense_match_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "hcir_dense_match_f16": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz,
                                      c_vp]),

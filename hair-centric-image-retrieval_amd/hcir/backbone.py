@@ -14,7 +14,12 @@ with the reference's constructor signatures:
                              momentum twins; the trunk on hcir.conv_train.train_trunk_map / hcir.resnet_engine behind the
                              HipTrunkSwitches; the step's losses and matching are hcir.losses / hcir.dense)
 
-The other SSL baselines of that file (MSN, BYOL, DINO, DINOv2, SiameseIMViT)
+  MSN(vit)                   HP/src/backbone.py:87-121   (target branch on the inference engine, anchor branch on the
+                             kept tokens of hcir.vit_train's class-token exit with the position table interpolated for
+                             focal views, MSNProjectionHead twins, prototypes; the criterion is hcir.losses.MSNLoss,
+                             csrc/msn.hip)
+
+The other SSL baselines of that file (BYOL, DINO, DINOv2, SiameseIMViT)
 are comparison methods outside the hot path and are not built.
 """
 from __future__ import annotations
@@ -32,8 +37,8 @@ from . import conv_train
 from .main_backbone import HipTrunkSwitches, SimCLRProjectionHead, ViTWrapper, deactivate_requires_grad
 from .resnet_engine import ResNetEngineCache, hip_trunk_active
 from .vit_engine import EngineCache, VitLayer, VitSpec
-from .vit_train import (MaeTrainer, VitTrainer, vit_mae_mse_with_grad, vit_mae_with_grad, vit_mim_l1_with_grad,
-                        vit_mim_with_grad)
+from .vit_train import (MaeTrainer, VitTrainer, vit_cls_with_grad, vit_mae_mse_with_grad, vit_mae_with_grad,
+                        vit_mim_l1_with_grad, vit_mim_with_grad)
 
 
 class SimCLR(HipTrunkSwitches, nn.Module):
@@ -391,6 +396,126 @@ class SimMIM(nn.Module):
             mask.scatter_(1, idx_mask, 1)
         tok = eng.forward_tokens(images, cls_only_last=True, token_mask=mask, mask_token=self.backbone.mask_token)
         return eng.cls_embedding(tok, final_norm=True, l2_normalize=False)
+
+
+def _tv_spec(vit) -> VitSpec:
+    """The VitSpec of a torchvision-layout container as lightly's masked wrapper runs it: the position added once."""
+    layers = []
+    for blk in vit.encoder.layers:
+        mha = blk.self_attention
+        layers.append(VitLayer(
+            ln1_w=blk.ln_1.weight, ln1_b=blk.ln_1.bias, qkv_w=mha.in_proj_weight, qkv_b=mha.in_proj_bias,
+            proj_w=mha.out_proj.weight, proj_b=mha.out_proj.bias, ln2_w=blk.ln_2.weight, ln2_b=blk.ln_2.bias,
+            fc1_w=blk.mlp[0].weight, fc1_b=blk.mlp[0].bias, fc2_w=blk.mlp[3].weight, fc2_b=blk.mlp[3].bias))
+    return VitSpec(patch=vit.patch_size, dim=vit.hidden_dim, heads=vit.num_heads, eps=1e-6, pos_mult=1.0,
+                   conv_w=vit.conv_proj.weight, conv_b=vit.conv_proj.bias, cls=vit.class_token,
+                   pos=vit.encoder.pos_embedding, layers=layers, final_ln_w=vit.encoder.ln.weight,
+                   final_ln_b=vit.encoder.ln.bias)
+
+
+class MSNProjectionHead(nn.Module):
+    """lightly.models.modules.MSNProjectionHead(input_dim=768, hidden_dim=2048, output_dim=256): Linear (no bias) -
+    BatchNorm1d - GELU - Linear (no bias) - BatchNorm1d - GELU - Linear (bias); keys layers.{0,3}.weight,
+    layers.{1,4}.{weight,bias,running_mean,running_var,num_batches_tracked}, layers.6.{weight,bias}.  A torch module,
+    as DenseCL's heads are."""
+
+    def __init__(self, input_dim: int = 768, hidden_dim: int = 2048, output_dim: int = 256):
+        super().__init__()
+        self.layers = nn.Sequential(
+            nn.Linear(input_dim, hidden_dim, bias=False), nn.BatchNorm1d(hidden_dim), nn.GELU(),
+            nn.Linear(hidden_dim, hidden_dim, bias=False), nn.BatchNorm1d(hidden_dim), nn.GELU(),
+            nn.Linear(hidden_dim, output_dim, bias=True))
+
+    def forward(self, x):
+        return self.layers(x)
+
+
+class MSN(nn.Module):
+    """MSN(vit) of HP/src/backbone.py:87-121 on the HIP path; `vit` is hcir._tv_vit.vit_b_16() (torchvision's layout).
+    State-dict keys are the reference's: backbone.vit.* (with heads.head.{weight,bias}, as SimMIM), backbone.mask_token,
+    projection_head.layers.*, their anchor_backbone / anchor_projection_head twins, prototypes [1024, 256].  As in the
+    reference the TARGET pair (backbone, projection_head) has requires_grad off and follows the anchor pair by
+    update_momentum; the prototypes are a parameter the reference's step never gives a gradient (it passes
+    prototypes.data to the criterion).  `hidden_dim` / `output_dim` / `num_prototypes` are not reference arguments
+    (2048 / 256 / 1024 there); they let a test build a small model.
+
+      forward(images)                 -> projection_head(backbone(images)): the target branch, no gradient, on the
+                                         inference engine (hcir.vit_engine)
+      forward_masked(images, idx_keep=None) -> anchor_projection_head(anchor_backbone(images, idx_keep)),
+                                         differentiable: the blocks run on the kept tokens only
+                                         (hcir.vit_train.vit_cls_with_grad), the position table is interpolated for
+                                         an image whose patch grid differs from the stored one (focal views)
+      extract_features(x)             -> backbone(x): the target branch's class token, under no_grad
+    The reference draws the mask over (width // patch) ** 2 positions - the patch count, without the class token's
+    slot - and applies the indices to the 1 + patches tokens: token 0 is always kept, the last patch never is, 166 of
+    197 tokens are kept at 224 x 224 and 30 of 37 at 96 x 96.  Kept as it is.  A caller's idx_keep (int64
+    [b, k], distinct token indices per image) is validated here, on the host, before anything is launched."""
+
+    def __init__(self, vit, hidden_dim: int = 2048, output_dim: int = 256, num_prototypes: int = 1024):
+        super().__init__()
+        self.mask_ratio = 0.15
+        if not hasattr(vit, "heads"):       # the container omits torchvision's classification head; the checkpoints have it
+            head = nn.Linear(vit.hidden_dim, 1000)
+            nn.init.zeros_(head.weight)
+            nn.init.zeros_(head.bias)
+            vit.heads = nn.Sequential(OrderedDict([("head", head)]))
+        self.backbone = _MaskedTVViT(vit)
+        self.projection_head = MSNProjectionHead(vit.hidden_dim, hidden_dim, output_dim)
+
+        self.anchor_backbone = copy.deepcopy(self.backbone)
+        self.anchor_projection_head = copy.deepcopy(self.projection_head)
+
+        deactivate_requires_grad(self.backbone)
+        deactivate_requires_grad(self.projection_head)
+
+        self.prototypes = nn.Linear(output_dim, num_prototypes, bias=False).weight
+        self._cache = EngineCache()
+
+    def trainer(self, device: torch.device) -> VitTrainer:
+        """The anchor branch's training walk (class-token exit, last block on the class-token rows)."""
+        tr = getattr(self, "_trainer", None)
+        if tr is None or tr.device != device:
+            tr = VitTrainer(_tv_spec(self.anchor_backbone.vit), device, cls_only_last=True)
+            self._trainer = tr
+        return tr
+
+    def _target_cls(self, images):
+        vit = self.backbone.vit
+        eng = self._cache.get(list(vit.parameters()), lambda: _tv_spec(vit), images.device)
+        tok = eng.forward_tokens(images, cls_only_last=True)
+        return eng.cls_embedding(tok, final_norm=True, l2_normalize=False)
+
+    @torch.no_grad()
+    def forward(self, images):
+        return self.projection_head(self._target_cls(images))
+
+    def _idx_keep(self, images, idx_keep):
+        b, _, _, width = images.shape
+        patch = self.anchor_backbone.vit.patch_size
+        if idx_keep is None:
+            seq_length = (width // patch) ** 2            # the reference's: no slot for the class token
+            return random_token_mask((b, seq_length), self.mask_ratio, device=images.device)[0].contiguous()
+        tokens = (images.shape[2] // patch) * (width // patch) + 1
+        if not torch.is_tensor(idx_keep) or idx_keep.dtype != torch.int64 or idx_keep.dim() != 2 \
+                or idx_keep.shape[0] != b or idx_keep.shape[1] == 0:
+            raise ValueError(f"idx_keep must be an int64 tensor [{b}, k] with k >= 1")
+        lo, hi = int(idx_keep.min()), int(idx_keep.max())
+        if lo < 0 or hi >= tokens:
+            raise ValueError(f"idx_keep holds token indices in [0, {tokens}); got {lo}..{hi}")
+        srt = idx_keep.sort(dim=1).values
+        if bool((srt[:, 1:] == srt[:, :-1]).any()):
+            raise ValueError("idx_keep names a token twice in one image")
+        return idx_keep.to(images.device).contiguous()
+
+    def forward_masked(self, images, idx_keep=None):
+        idx_keep = self._idx_keep(images, idx_keep)
+        out = vit_cls_with_grad(self.trainer(images.device), images.float().contiguous(), idx_keep,
+                                interpolate_pos=True)
+        return self.anchor_projection_head(out)
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self._target_cls(x)
 
 
 class DenseCLProjectionHead(nn.Module):

@@ -9,6 +9,9 @@ module keeps lightly's queue.
 
 SupConLoss with the constructor/forward signature of the reference's class (HairPretraining/utils/losses.py:8-101; call
 sites HairPretraining/src/pretrain_engine.py:76,390), computed by hcir_supcon_fwd / hcir_supcon_bwd the same way.
+
+MSNLoss with lightly's constructor/forward signature (lightly.loss.MSNLoss; the criterion of the MSN step,
+HairPretraining/src/pretrain_engine.py:91,262), computed by hcir_msn_targets / hcir_msn_fwd / hcir_msn_bwd.
 """
 from __future__ import annotations
 
@@ -330,3 +333,140 @@ class NTXentLoss(nn.Module):
                 raise HcirError("hcir_ntxent_bwd needs a batch size that is a multiple of 4")
             return _NTXentFn.apply(out0, out1, self.temperature)
         return ntxent_forward(out0.contiguous(), out1.contiguous(), self.temperature)
+
+
+def _msn_check(anchors: torch.Tensor, targets: torch.Tensor, prototypes: torch.Tensor) -> None:
+    for t, name in ((anchors, "anchors"), (targets, "targets"), (prototypes, "prototypes")):
+        _dev(t, name)
+    if anchors.dim() != 2 or targets.dim() != 2 or prototypes.dim() != 2 or anchors.dtype != targets.dtype \
+            or not (anchors.shape[1] == targets.shape[1] == prototypes.shape[1]):
+        raise HcirError(f"MSNLoss expects anchors [N, D] and targets [B, D] of one dtype and prototypes [K, D], got "
+                        f"{tuple(anchors.shape)} {anchors.dtype} / {tuple(targets.shape)} {targets.dtype} / "
+                        f"{tuple(prototypes.shape)}")
+    if anchors.dtype not in _DT:
+        raise HcirError(f"unsupported dtype {anchors.dtype}")
+    if prototypes.dtype != torch.float32 or not prototypes.is_contiguous():
+        raise HcirError(f"MSNLoss prototypes must be a contiguous fp32 [K, D] tensor, got {prototypes.dtype}")
+
+
+def msn_targets(targets: torch.Tensor, prototypes: torch.Tensor, temperature: float, sinkhorn_iterations: int = 3
+                ) -> torch.Tensor:
+    """hcir_msn_targets: fp32 [B, K] target probabilities, softmax_k(t_j.c_k / temperature) followed by
+    `sinkhorn_iterations` Sinkhorn rounds.  `temperature` is the product T * Ts of the sharpened softmax."""
+    b, d = targets.shape
+    k = prototypes.shape[0]
+    L = _lib.lib()
+    dt = _DT[targets.dtype]
+    ws = _ws.get(targets.device, L.hcir_msn_workspace_bytes(b, k, d, dt, 0))
+    q = torch.empty((b, k), dtype=torch.float32, device=targets.device)
+    check(L.hcir_msn_targets(targets.data_ptr(), prototypes.data_ptr(), b, k, d, dt, 1.0 / temperature,
+                             int(sinkhorn_iterations), q.data_ptr(), ws.data_ptr(), ws.numel(), _stream(targets)),
+          "hcir_msn_targets")
+    return q
+
+
+def msn_forward(anchors: torch.Tensor, prototypes: torch.Tensor, q: torch.Tensor, temperature: float,
+                regularization_weight: float, want_saved: bool = False):
+    """hcir_msn_fwd on contiguous anchors [N, D], fp32 prototypes [K, D] and the targets' q [B, K].  Returns the loss,
+    or (loss, parts, row_lse, pbar) with want_saved; parts = (cross-entropy, regulariser without its weight)."""
+    n, d = anchors.shape
+    b, k = q.shape
+    L = _lib.lib()
+    dt = _DT[anchors.dtype]
+    ws = _ws.get(anchors.device, L.hcir_msn_workspace_bytes(n, k, d, dt, 1))
+    dev = anchors.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    parts = torch.empty(2, dtype=torch.float32, device=dev) if want_saved else None
+    lse = torch.empty(n, dtype=torch.float32, device=dev) if want_saved else None
+    pbar = torch.empty(k, dtype=torch.float32, device=dev) if want_saved else None
+    check(L.hcir_msn_fwd(anchors.data_ptr(), prototypes.data_ptr(), q.data_ptr(), n, b, k, d, dt, 1.0 / temperature,
+                         float(regularization_weight), loss.data_ptr(), None if parts is None else parts.data_ptr(),
+                         None if lse is None else lse.data_ptr(), None if pbar is None else pbar.data_ptr(),
+                         ws.data_ptr(), ws.numel(), _stream(anchors)), "hcir_msn_fwd")
+    return (loss, parts, lse, pbar) if want_saved else loss
+
+
+def msn_backward(anchors, prototypes, q, temperature, regularization_weight, lse, pbar, grad_out: float):
+    """hcir_msn_bwd: dL/danchors for the loss of msn_forward on the same prototypes and q."""
+    n, d = anchors.shape
+    b, k = q.shape
+    if k % 8:
+        raise HcirError("hcir_msn_bwd needs a number of prototypes that is a multiple of 8")
+    L = _lib.lib()
+    dt = _DT[anchors.dtype]
+    ws = _ws.get(anchors.device, L.hcir_msn_workspace_bytes(n, k, d, dt, 2))
+    grad = torch.empty_like(anchors)
+    check(L.hcir_msn_bwd(anchors.data_ptr(), prototypes.data_ptr(), q.data_ptr(), n, b, k, d, dt, 1.0 / temperature,
+                         float(regularization_weight), lse.data_ptr(), pbar.data_ptr(), float(grad_out),
+                         grad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(anchors)), "hcir_msn_bwd")
+    return grad
+
+
+class _MSNFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchors, targets, prototypes, temperature, sharpen, iterations, weight):
+        anchors, targets = anchors.contiguous(), targets.contiguous()
+        q = msn_targets(targets, prototypes, temperature * sharpen, iterations)
+        loss, _parts, lse, pbar = msn_forward(anchors, prototypes, q, temperature, weight, want_saved=True)
+        # the caller may step the prototypes' owner before the backward: keep the rows the loss was taken against
+        ctx.save_for_backward(anchors, prototypes.clone(), q, lse, pbar)
+        ctx.cfg = (temperature, weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        anchors, prototypes, q, lse, pbar = ctx.saved_tensors
+        g = msn_backward(anchors, prototypes, q, *ctx.cfg, lse, pbar, float(grad))  # one host read of dL
+        return g, None, None, None, None, None, None
+
+
+class MSNLoss(nn.Module):
+    """MSNLoss(temperature=0.1, sinkhorn_iterations=3, regularization_weight=1.0, gather_distributed=False) of lightly
+    (the criterion of the MSN step, HairPretraining/src/pretrain_engine.py:91,262).
+    forward(anchors [N, D], targets [B, D], prototypes [K, D], target_sharpen_temperature=0.25): the cross-entropy of
+    the anchors' prototype softmax against the targets' sharpened, Sinkhorn-normalised one (row i of the anchors pairs
+    with target i mod B) plus `regularization_weight` times the mean-entropy regulariser.  The gradient reaches the
+    anchors only: the reference hands over `model.prototypes.data`."""
+
+    def __init__(self, temperature: float = 0.1, sinkhorn_iterations: int = 3, regularization_weight: float = 1.0,
+                 gather_distributed: bool = False):
+        super().__init__()
+        if temperature <= 0:
+            raise ValueError(f"temperature must be in (0, inf) but is {temperature}.")
+        if sinkhorn_iterations < 0:
+            raise ValueError(f"sinkhorn_iterations must be >= 0 but is {sinkhorn_iterations}.")
+        if gather_distributed:
+            raise NotImplementedError("gather_distributed is never enabled by the reference "
+                                      "(SURVEY.md §2.3)")
+        self.temperature = temperature
+        self.sinkhorn_iterations = sinkhorn_iterations
+        self.regularization_weight = regularization_weight
+        self.gather_distributed = False
+
+    def forward(self, anchors: torch.Tensor, targets: torch.Tensor, prototypes: torch.Tensor,
+                target_sharpen_temperature: float = 0.25) -> torch.Tensor:
+        if prototypes.requires_grad:
+            raise NotImplementedError("a gradient to the prototypes is never used by the reference (its one call site, "
+                                      "HairPretraining/src/pretrain_engine.py:262, passes model.prototypes.data); pass "
+                                      "prototypes.data or a detached tensor")
+        if targets.shape[0] == 0 or anchors.shape[0] % targets.shape[0]:
+            raise ValueError(f"the number of anchors ({anchors.shape[0]}) must be a multiple of the number of targets "
+                             f"({targets.shape[0]})")
+        if not anchors.is_cuda:
+            raise HcirError(f"MSNLoss got `anchors` on {anchors.device}; the loss runs on a HIP device only "
+                            "(no CPU fallback)")
+        targets = targets.detach()
+        if targets.dtype != anchors.dtype:
+            targets = targets.to(anchors.dtype)
+        prototypes = prototypes.detach()
+        if prototypes.dtype != torch.float32 or not prototypes.is_contiguous():
+            prototypes = prototypes.float().contiguous()
+        _msn_check(anchors, targets, prototypes)
+        if torch.is_grad_enabled() and anchors.requires_grad:
+            if prototypes.shape[0] % 8:
+                raise HcirError("hcir_msn_bwd needs a number of prototypes that is a multiple of 8")
+            return _MSNFn.apply(anchors, targets, prototypes, self.temperature, target_sharpen_temperature,
+                                self.sinkhorn_iterations, self.regularization_weight)
+        q = msn_targets(targets.contiguous(), prototypes, self.temperature * target_sharpen_temperature,
+                        self.sinkhorn_iterations)
+        return msn_forward(anchors.contiguous(), prototypes, q, self.temperature, self.regularization_weight)

@@ -40,7 +40,7 @@ import torch
 import torch.nn.functional as F
 
 from .dense import select_most_similar
-from .losses import NTXentLoss, SupConLoss
+from .losses import MSNLoss, NTXentLoss, SupConLoss
 from . import optim as hcir_optim
 from ._lib import HcirError
 from .momentum import update_momentum
@@ -354,3 +354,57 @@ class DenseCLTrainStep:
         opt.zero_grad()                                                                         # :315
         vals = torch.stack([loss.detach().float(), loss_global.detach(), loss_local.detach()]).tolist()   # one read
         return dict(zip(("loss", "loss_global", "loss_local"), vals))
+
+
+class MSNTrainStep:
+    """The body of Trainer.train_one_epoch_msn's batch loop (HairPretraining/src/pretrain_engine.py:246-270) for an
+    hcir.backbone.MSN model: the two update_momentum calls at 0.996 (anchor -> target, hcir.momentum), views[0] through
+    the target branch (no gradient, the inference engine), views[1] through forward_masked, views[2:] concatenated
+    through a second forward_masked call (its own mask draw, its own BatchNorm batch statistics, the position table
+    interpolated for the focal size), the criterion (hcir.losses.MSNLoss, hcir_msn_targets / _fwd / _bwd) on
+    model.prototypes.data, then scaler.scale(loss).backward(); scaler.step; scaler.update; zero_grad.  The heads run
+    under fp16 autocast as in the reference; the criterion sees fp32 rows, as in the other steps.  No gradient
+    clipping: the reference does none here.  With no focal views the second call is skipped (the reference's
+    torch.concat of an empty list would raise).  -> {"loss": float}."""
+
+    def __init__(self, model, optimizer, scaler=None, criterion=None, momentum: float = 0.996):
+        self.model = model
+        self.optimizer = optimizer
+        self.scaler = scaler
+        self.momentum = momentum
+        self.criterion = criterion if criterion is not None else MSNLoss()                       # :89
+
+    @staticmethod
+    def _views(batch):
+        if isinstance(batch, dict):
+            return [batch["anchor"], batch["pos1"]] + list(batch.get("focal", ()))
+        views = list(batch)
+        if len(views) < 2:
+            raise ValueError("the MSN step needs a target view and an anchor view")
+        return views
+
+    def __call__(self, batch, **_loop_state) -> Dict[str, float]:
+        """One optimisation step on a list of view batches [B,3,H,W] on the HIP device - views[0] the targets,
+        views[1] the anchors, views[2:] the focal anchors, all of one size - or on a dict {'anchor', 'pos1'} (target,
+        anchor) with an optional 'focal' list.  The loop variables SHAMTrainStep takes are accepted and unused."""
+        model, opt, scaler = self.model, self.optimizer, self.scaler
+        model.train()                                                                           # :243
+        views = self._views(batch)
+        update_momentum(model.anchor_backbone, model.backbone, m=self.momentum)                 # :248
+        update_momentum(model.anchor_projection_head, model.projection_head, m=self.momentum)   # :249-251
+        with torch.autocast(device_type="cuda", dtype=torch.float16):                           # :246
+            targets_out = model(views[0])                                                       # :258-259
+            anchors_out = model.forward_masked(views[1])                                        # :260
+            if len(views) > 2:
+                anchors_focal_out = model.forward_masked(torch.cat(views[2:], dim=0))           # :256,261
+                anchors_out = torch.cat([anchors_out, anchors_focal_out], dim=0)                # :262
+        loss = self.criterion(anchors_out.float(), targets_out.float(), model.prototypes.data)  # :264
+        if scaler is not None:                                                                  # :267-269
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
+        opt.zero_grad()                                                                         # :270
+        return {"loss": float(loss.detach())}

@@ -43,9 +43,18 @@ GEMM on compact rows as the SimMIM exit does.  Its backward mirrors that: ops.ma
 `backward_blocks` (which leaves dL / d(input stream)), ops.mae_decoder_input_bwd, the encoder's final LayerNorm and
 blocks, the scatter of the compact residual gradient into the [b t, d] stream and the patch-embedding tail.
 `vit_mae_with_grad` / `vit_mae_mse_with_grad` wrap it; tests/test_mae_host.py is the wiring test.
+The class-token exit takes the kept-rows stream as well (MSN's anchors, hcir.backbone.MSN; lightly's
+MaskedVisionTransformerTorchvision.forward(images, idx_keep)): `forward(x, keep=)` gathers the kept rows behind the
+position add, runs the blocks on b * t_keep rows - the last one, under `cls_only_last`, on the b first rows, which the
+class-token attention pair serves at any t <= 256 - and `backward` scatters the stream gradient back before the
+patch-embedding tail.  With `interpolate_pos` an image whose patch grid differs from the stored one takes the position
+table `interpolate_pos_encoding` makes for its grid (torch, once per parameter version and grid: a few kilobytes) and
+returns the position gradient through the same linear map (torch.autograd.grad on that graph); without it the token
+count must be the stored one, as before.
 """
 from __future__ import annotations
 
+import math
 from collections import namedtuple
 from types import SimpleNamespace
 from typing import List
@@ -73,7 +82,8 @@ class _Block:
 
 class _Saved:
     """Activations of one training forward (device buffers; rows padded to a multiple of 64 with zeros)."""
-    __slots__ = ("b", "t", "m", "patches", "blocks", "last", "x_out", "mim", "keep", "tb")   # tb: tokens the blocks saw
+    __slots__ = ("b", "t", "m", "patches", "blocks", "last", "x_out", "mim", "keep", "tb",   # tb: tokens the blocks saw
+                 "npatch")   # patches per image where the position table was interpolated for them, else None
 
 
 class BlockStack:
@@ -279,6 +289,24 @@ class BlockStack:
         return g, fc2_b_next
 
 
+def interpolate_pos_encoding(pos: torch.Tensor, npatch: int) -> torch.Tensor:
+    """lightly's MaskedVisionTransformerTorchvision.interpolate_pos_encoding: the [1, 1 + N0, d] table for an image of
+    `npatch` patches.  The class row as it is; the [1, d, g0, g0] patch grid through
+    F.interpolate(scale_factor=sqrt(npatch / N0), mode="bicubic").  Differentiable in `pos`."""
+    n0 = pos.shape[1] - 1
+    if npatch == n0:
+        return pos
+    g0, d = int(math.sqrt(n0)), pos.shape[-1]
+    if g0 * g0 != n0:
+        raise HcirError(f"the stored position table has {n0} patch rows, which is no square grid")
+    grid = pos[:, 1:].reshape(1, g0, g0, d).permute(0, 3, 1, 2)
+    grid = torch.nn.functional.interpolate(grid, scale_factor=math.sqrt(npatch / n0), mode="bicubic")
+    grid = grid.permute(0, 2, 3, 1).reshape(1, -1, d)
+    if grid.shape[1] != npatch:
+        raise HcirError(f"interpolating the {g0} x {g0} position grid gives {grid.shape[1]} rows for {npatch} patches")
+    return torch.cat((pos[:, :1], grid), dim=1)
+
+
 class VitTrainer(BlockStack):
     """fp16 operand copies of a ViT's weights (as stored and transposed) + the training forward / backward."""
 
@@ -327,11 +355,32 @@ class VitTrainer(BlockStack):
         if self.mim is not None:
             mt, dw, db = self.mim
             self.mask_token, self.dec_w, self.dec_wt, self.dec_b = f32(mt.reshape(-1)), f16(dw), f16t(dw), f32(db)
+        self._pos_grids = {}                              # npatch -> interpolated table, of this parameter version
         self._key = key
 
+    def _pos_for(self, npatch: int) -> torch.Tensor:
+        """The fp32 [1 + npatch, d] position table of an image with another patch grid than the stored one."""
+        tab = self._pos_grids.get(npatch)
+        if tab is None:
+            with torch.no_grad():
+                tab = interpolate_pos_encoding(self.spec.pos.detach().to(self.ops.ACC), npatch)
+            tab = _to(tab.reshape(-1, self.dim), self.device, self.ops.ACC)
+            self._pos_grids[npatch] = tab
+        return tab
+
+    def _pos_grad(self, g_tab: torch.Tensor, npatch: int) -> torch.Tensor:
+        """dL / d(stored table) from dL / d(interpolated table): the transpose of the same linear map."""
+        with torch.enable_grad():
+            p = self.spec.pos.detach().to(self.ops.ACC).requires_grad_(True)
+            tab = interpolate_pos_encoding(p, npatch)
+            g = torch.autograd.grad(tab, p, grad_outputs=g_tab.reshape(tab.shape).to(device=p.device, dtype=tab.dtype))[0]
+        return g.to(self.device)
+
     # -- forward ------------------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor):
-        sv, cur = self._forward_blocks(x, None, self.cls_only_last)
+    def forward(self, x: torch.Tensor, keep=None, interpolate_pos: bool = False):
+        """The class token behind the final LayerNorm.  `keep` (int64 [b, t_keep], lightly's idx_keep): the blocks run
+        on those rows only and the class token is the first of them."""
+        sv, cur = self._forward_blocks(x, None, self.cls_only_last, keep=keep, interpolate_pos=interpolate_pos)
         cls = self._acc(sv.b, self.dim)
         self.ops.cls_head(cur, sv.b, sv.last.nq, self.fln_w, self.fln_b, self.eps, cls)
         return cls, sv
@@ -358,7 +407,7 @@ class VitTrainer(BlockStack):
         sv.mim = SimpleNamespace(mask=mask, flat=flat, rows=rows, xc=xc, ln=ln)
         return pred, sv
 
-    def _forward_blocks(self, x: torch.Tensor, mask, cls_only_last: bool, keep=None):
+    def _forward_blocks(self, x: torch.Tensor, mask, cls_only_last: bool, keep=None, interpolate_pos: bool = False):
         """patch_embed, the mask tokens where `mask` (uint8 [b, t]) is given, and every block - on every token, or,
         where `keep` (int64 [b, t_keep], MAE's idx_keep) is given, on the kept rows gathered into a compact stream."""
         ops = self.ops
@@ -373,19 +422,25 @@ class VitTrainer(BlockStack):
         t = (hh // ps) * (ww // ps) + 1
         if t > 256:
             raise HcirError("hcir_attn_bwd supports up to 256 tokens")
+        pos, npatch = self.pos, None
         if t != self.pos.shape[0]:
-            raise HcirError(f"image gives {t} tokens but pos_embedding has {self.pos.shape[0]}")
+            if not interpolate_pos or mask is not None:
+                raise HcirError(f"image gives {t} tokens but pos_embedding has {self.pos.shape[0]}")
+            if hh != ww:
+                raise HcirError("the position table is interpolated for square images only")
+            npatch = t - 1
+            pos = self._pos_for(npatch)
         if self.conv_w.shape[1] % 64:
             raise HcirError("C*P*P must be a multiple of 64")
         m = b * t
         sv = _Saved()
-        sv.b, sv.t, sv.m, sv.mim, sv.keep, sv.tb = b, t, m, None, keep, t
+        sv.b, sv.t, sv.m, sv.mim, sv.keep, sv.tb, sv.npatch = b, t, m, None, keep, t, npatch
         # im2col of the patches in (c, ky, kx) order: the weight gradient of conv_proj needs it (data movement only)
         gh, gw = hh // ps, ww // ps
         sv.patches = self._act(b * gh * gw, c * ps * ps)
         sv.patches[: b * gh * gw] = x.reshape(b, c, gh, ps, gw, ps).permute(0, 2, 4, 1, 3, 5).reshape(b * gh * gw, -1)
         cur = self._act(m, d)
-        ops.patch_embed(x, ps, self.conv_w, self.conv_b, self.cls, self.pos, self.pos_mult, cur)
+        ops.patch_embed(x, ps, self.conv_w, self.conv_b, self.cls, pos, self.pos_mult, cur)
         if mask is not None:
             # lightly's mask_at_index stands before the position add; patch_embed has added the position already
             ops.mim_mask_tokens(cur, b, t, mask, self.mask_token, self.pos, self.pos_mult)
@@ -457,6 +512,8 @@ class VitTrainer(BlockStack):
         else:                                             # a masked class token is the mask token, not cls
             g_cls = (dtok[:, 0] * (mm.mask[:, :1] == 0).to(dtok.dtype)).sum(0)
         g_pos = dtok.sum(0) * self.pos_mult
+        if sv.npatch is not None:
+            g_pos = self._pos_grad(g_pos, sv.npatch)
         npat = b * (t - 1)
         dpatch = self._act(npat, d)
         if mm is None:
@@ -482,8 +539,8 @@ class _VitClsFn(torch.autograd.Function):
     """cls = LN_final(ViT(x))[:, 0] with gradients for every backbone parameter (none for the images)."""
 
     @staticmethod
-    def forward(ctx, trainer: VitTrainer, x: torch.Tensor, *params):
-        cls, saved = trainer.forward(x)
+    def forward(ctx, trainer: VitTrainer, x: torch.Tensor, keep, interpolate_pos: bool, *params):
+        cls, saved = trainer.forward(x, keep=keep, interpolate_pos=interpolate_pos)
         ctx.trainer, ctx.saved = trainer, saved
         ctx.mask = [p.requires_grad for p in params]
         return cls
@@ -494,7 +551,7 @@ class _VitClsFn(torch.autograd.Function):
         grads = ctx.trainer.backward(ctx.saved, d_cls * up)
         ctx.saved = None
         torch._foreach_mul_(grads, down)
-        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.mask))
+        return (None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.mask))
 
 
 def _pow2_renorm(grad: torch.Tensor):
@@ -511,8 +568,10 @@ def _pow2_renorm(grad: torch.Tensor):
     return torch.exp2(k), torch.exp2(-k)
 
 
-def vit_cls_with_grad(trainer: VitTrainer, x: torch.Tensor) -> torch.Tensor:
-    return _VitClsFn.apply(trainer, x, *trainer.params())
+def vit_cls_with_grad(trainer: VitTrainer, x: torch.Tensor, idx_keep=None, interpolate_pos: bool = False) -> torch.Tensor:
+    """idx_keep (int64 [b, t_keep] on x's device, lightly's): the blocks run on those tokens only; the caller has
+    validated it.  interpolate_pos: accept an image whose patch grid differs from the stored position table's."""
+    return _VitClsFn.apply(trainer, x, idx_keep, bool(interpolate_pos), *trainer.params())
 
 
 class _VitMimFn(torch.autograd.Function):

@@ -4,9 +4,10 @@ MI355X hot path.  Same flags (HP/knn_classification.py:47-67) and the same outpu
 `<save_path>/<mode>_<model>[_<SHAM_mode>]/knn_evaluation_results.txt`.
 
 Modes on the hot path: SHAM (resnet18 / resnet50 / vit_b_16), simclr, mae, simMIM (whose embedding is the class
-token of a forward with a fresh random 75 % mask, as in the reference), DenseCL.  Training on the HIP
-path is built for SHAM, simclr_supcon, simMIM, DenseCL and mae (hcir.pretrain_engine; tools/train_from_files.py
---mode sham / supcon / simmim / densecl / mae); this CLI evaluates their checkpoints.  The other --mode
+token of a forward with a fresh random 75 % mask, as in the reference), DenseCL, MSN (the class token
+of the target branch).  Training on the HIP
+path is built for SHAM, simclr_supcon, simMIM, DenseCL, mae and MSN (hcir.pretrain_engine; tools/train_from_files.py
+--mode sham / supcon / simmim / densecl / mae / msn); this CLI evaluates their checkpoints.  The other --mode
 values name SSL baselines that are out of scope: accepted by argparse,
 rejected with a clear error.  --eval_type knn, linear_prob (`linear_probe_results.txt`: the L-BFGS fit of
 hcir.linear_probe on the device) and inter_intra_distance (`variance_analysis_both.txt`) are built;
@@ -107,9 +108,15 @@ def build_model(args):
         model = DenseCL(nn.Sequential(*list(resnet.children())[:-2]))
         if args.checkpoint_path:
             model.load_state_dict(load(args.checkpoint_path)['model_state_dict'])
+    elif args.mode == "MSN":
+        from hcir._tv_vit import vit_b_16
+        from hcir.backbone import MSN
+        model = MSN(vit_b_16())                                         # HP/knn_classification.py:173-178
+        if args.checkpoint_path:
+            model.load_state_dict(load(args.checkpoint_path)['model_state_dict'])
     else:
         raise SystemExit(f"--mode {args.mode}: this SSL baseline is outside the MI355X hot path "
-                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae, simMIM, DenseCL")
+                         "(SURVEY.md §2.1 row 4); built modes: SHAM, simclr, mae, simMIM, DenseCL, MSN")
     if args.checkpoint_path:
         print("Model weights loaded!")
     if getattr(args, "resnet_engine", "torch") == "hip" and hasattr(model, "hip_trunk"):

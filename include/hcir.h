@@ -214,6 +214,41 @@ int hcir_ntxent_bank_bwd(const void* z0, const void* z1, const float* bank, int6
                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * MSN criterion (lightly.loss.MSNLoss; the MSN step, HairPretraining/src/pretrain_engine.py:242-275).  Row i of the
+ * anchors pairs with target i mod B; N % B == 0.
+ *   a_i = anchors_i / max(||anchors_i||, 1e-12), t_j and c_k (prototypes) likewise
+ *   p_ik = softmax_k(a_i.c_k * inv_t)
+ *   q_jk = softmax_k(t_j.c_k * inv_t_sharp)        inv_t_sharp = 1 / (T * Ts): softmax(./T) ** (1/Ts), renormalised
+ *   Sinkhorn (iterations > 0): v = 1; repeat u_k = 1 / (K sum_j q_jk v_j), v_j = 1 / (B sum_k u_k q_jk);
+ *                              q_jk <- u_k q_jk / sum_k u_k q_jk
+ *   loss = mean_i sum_k -q_(i mod B)k log p_ik + reg_weight * (sum_k pbar_k log pbar_k + log K),  pbar_k = mean_i p_ik
+ * hcir_msn_targets: targets [B][D] in dtype, prototypes fp32 [K][D] (normalised here, not by the caller) -> q fp32
+ * [B][K]; iterations == 0 leaves the sharpened softmax.
+ * hcir_msn_fwd: anchors [N][D] in dtype -> loss (1 float); loss_parts[2] = {cross-entropy, regulariser without its
+ * weight}, row_lse[N], pbar[K]: each may be NULL; the backward needs row_lse and pbar.  No [N][K] matrix is stored.
+ * hcir_msn_bwd: G_ik = p_ik (sum_k q_ik + reg_weight (log pbar_k - e_i)) - q_ik, e_i = sum_k p_ik log pbar_k, written
+ * once as fp16 [N][K] into the workspace (1 / N and grad_out stay out of that image); g = G.c on hcir_gemm_f16;
+ * danchors_i = grad_out * inv_t / N * rn_i (g_i - (g_i.a_i) a_i), [N][D] in dtype.  The targets and the prototypes
+ * receive no gradient.
+ * No atomics, every sum in a fixed order: results are bit-identical from run to run.
+ * hcir_msn_workspace_bytes(n, k, d, dtype, stage): stage 0 = targets (n is B), 1 = forward, 2 = backward.
+ * Status: HCIR_ERR_INVALID for a null required pointer, n, b, k, d <= 0, d % 8 != 0, n % b != 0, n > 65535 * 128,
+ * a temperature factor that is 0 or NaN, iterations < 0, and for a backward with k % 8 != 0 (hcir_gemm_f16's rule for
+ * its inner dimension); HCIR_ERR_UNSUPPORTED for a dtype other than HCIR_F32/F16/BF16; HCIR_ERR_WORKSPACE for a null
+ * or short workspace.  Nothing is written on an error.
+ * ------------------------------------------------------------------ */
+size_t hcir_msn_workspace_bytes(int64_t n, int64_t k, int32_t d, int dtype, int stage);
+int hcir_msn_targets(const void* targets, const float* prototypes, int64_t b, int64_t k, int32_t d, int dtype,
+                     float inv_t_sharp, int32_t iterations, float* q, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int hcir_msn_fwd(const void* anchors, const float* prototypes, const float* q, int64_t n, int64_t b, int64_t k,
+                 int32_t d, int dtype, float inv_t, float reg_weight, float* loss, float* loss_parts, float* row_lse,
+                 float* pbar, void* workspace, size_t workspace_bytes, void* stream);
+int hcir_msn_bwd(const void* anchors, const float* prototypes, const float* q, int64_t n, int64_t b, int64_t k,
+                 int32_t d, int dtype, float inv_t, float reg_weight, const float* row_lse, const float* pbar,
+                 float grad_out, void* danchors, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Dense matching (lightly.models.utils.select_most_similar; the DenseCL step,
  * HairPretraining/src/pretrain_engine.py:304-306).  For image b and query position n:
  *   j*(b, n) = argmax_m (x_bn . y_bm) / max(||y_bm||, 1e-12),   out[b][n] = y_values[b][j*(b, n)]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """An epoch of SHAMTrainStep (--mode supcon: SupConTrainStep, --mode simmim: SimMIMTrainStep, --mode densecl:
-DenseCLTrainStep, --mode mae: MAETrainStep) fed from an annotation CSV + image directory, input on the device.
+DenseCLTrainStep, --mode mae: MAETrainStep, --mode msn: MSNTrainStep) fed from an annotation CSV + image directory, input on the device.
 
     python tools/train_from_files.py --csv data/data_train.csv --img-dir data/train --batch-size 1024
 
@@ -71,7 +71,7 @@ def build_parser():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--warm-up-epochs", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--mode", choices=("sham", "supcon", "simmim", "densecl", "mae"), default="sham",
+    ap.add_argument("--mode", choices=("sham", "supcon", "simmim", "densecl", "mae", "msn"), default="sham",
                     help="sham: the HSimCLR step (SHAMTrainStep).  supcon: the reference's simclr_supcon step "
                          "(SupConTrainStep) on the batch's class labels, with SHAM2(model) as encoder plus projection "
                          "head and SupConLoss(normalize=True); the reference's SupConResNet, a CIFAR-style trunk "
@@ -83,7 +83,10 @@ def build_parser():
                          "trunk with --model resnet18 - with the two device SimCLR views as x_query / x_key; lightly's "
                          "DenseCLTransform is not built.  mae: the reference's mae step (MAETrainStep) on "
                          "MAE(vit_base_patch16_224()), one view per image exactly as --mode simmim gives it (the device "
-                         "view kernel stands in for lightly's MAETransform)")
+                         "view kernel stands in for lightly's MAETransform).  msn: the reference's MSN step (MSNTrainStep) on "
+                         "MSN(vit_b_16()) with the two device SimCLR views as target ('anchor') and anchor ('pos1'); "
+                         "lightly's MSNTransform is not built and the device view kernel produces 224 x 224 only, so no "
+                         "focal views are passed (the step itself accepts them)")
     ap.add_argument("--epoch", type=int, default=0, help="--mode densecl: the epoch of the momentum schedule")
     ap.add_argument("--epochs", type=int, default=100,
                     help="--mode densecl: momentum = cosine_schedule(epoch, epochs, 0.996, 1)")
@@ -111,8 +114,8 @@ def main():
     a = ap.parse_args()
     from hcir.dataloader import EncodedDataset, collate_train_views
     from hcir.main_backbone import SHAM2
-    from hcir.pretrain_engine import (DenseCLTrainStep, MAETrainStep, SHAMTrainStep, SimMIMTrainStep, SupConTrainStep,
-                                      cosine_schedule)
+    from hcir.pretrain_engine import (DenseCLTrainStep, MAETrainStep, MSNTrainStep, SHAMTrainStep, SimMIMTrainStep,
+                                      SupConTrainStep, cosine_schedule)
     torch.manual_seed(a.seed)
     ds = EncodedDataset(a.csv, a.img_dir, return_names=True)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, drop_last=True,
@@ -133,6 +136,14 @@ def main():
             ap.error("--mode mae steps with torch's Adam and GradScaler (MAETrainStep: scaler.step / update)")
         from hcir.backbone import MAE, vit_base_patch16_224
         model = MAE(vit_base_patch16_224()).cuda()
+    elif a.mode == "msn":
+        if a.model != "vit_b_16":
+            ap.error("--mode msn trains the torchvision vit_b_16")
+        if a.fused_optim:
+            ap.error("--mode msn steps with torch's Adam and GradScaler (MSNTrainStep: scaler.step / update)")
+        from hcir._tv_vit import vit_b_16
+        from hcir.backbone import MSN
+        model = MSN(vit_b_16()).cuda()
     elif a.mode == "densecl":
         if a.model == "vit_b_16":
             a.model = "resnet50"                  # the reference's DenseCL trunk (HP/mainpretrain.py:159-162)
@@ -172,6 +183,8 @@ def main():
     elif a.mode == "mae":
         step = MAETrainStep(model, opt, scaler)
         view_kwargs = dict(min_scale=0.2, cj_prob=0.0, random_gray_scale=0.0, gaussian_blur=0.0)
+    elif a.mode == "msn":
+        step = MSNTrainStep(model, opt, scaler)
     elif a.mode == "densecl":
         step = DenseCLTrainStep(model, opt, scaler)
         view_names = {"anchor": "x_query", "pos1": "x_key"}
