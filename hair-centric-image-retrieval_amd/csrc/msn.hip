@@ -48,23 +48,13 @@ __global__ __launch_bounds__(256) void msn_prep(const T* __restrict__ x, int64_t
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n + kp) return;
-  float ss = 0.f;
   if (row < n) {
-    for (int k = lane; k < d; k += 64) {
-      const float v = (float)x[row * d + k];
-      ss = __builtin_fmaf(v, v, ss);
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) rinv[row] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    const float inv = pair_row_inv_norm(x + row * d, d, lane);
+    if (lane == 0) rinv[row] = inv;
     return;
   }
   const int64_t j = row - n;
-  for (int k = lane; k < d; k += 64) {
-    const float v = protos[j * d + k];
-    ss = __builtin_fmaf(v, v, ss);
-  }
-  ss = wave_sum(ss);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+  const float inv = pair_row_inv_norm(protos + j * d, d, lane);
   for (int k = lane; k < d; k += 64) {
     const float v = protos[j * d + k] * inv;
     cn[j * d + k] = (T)v;
@@ -108,7 +98,6 @@ __global__ __launch_bounds__(256, 2) void msn_tiles(MsnArgs a) {
   f32x16 acc[2][2];
   pair_tile_products<T, GLDS>(acc, lds, static_cast<const T*>(a.cols), c0, a.kp, static_cast<const T*>(a.rows), r0,
                               a.n, a.d, tid, lane, wave_c, wave_r);
-  float* red = reinterpret_cast<float*>(lds);
   const float ninf = -__builtin_huge_valf();
 
   if constexpr (MODE == MSN_LOGITS) {
@@ -121,13 +110,12 @@ __global__ __launch_bounds__(256, 2) void msn_tiles(MsnArgs a) {
       for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int64_t col = c0 + wave_c * 64 + ct * 32 + acc_row(i, h);
+          const int64_t col = pair_col(c0, wave_c, ct, i, h);
           if (col < a.kp) a.xout[row * a.kp + col] = acc[ct][rt][i] * sc;
         }
     }
   } else if constexpr (MODE == MSN_LSE || MODE == MSN_E) {
-    // per row and prototype tile: LSE (m, l, sum tgt x, sum tgt); E (sum p log pbar, sum tgt).  The four
-    // (wave_c, lane-half) partials of a row meet in LDS: [128 rows][4 src][4]
+    // per row and prototype tile: LSE (m, l, sum tgt x, sum tgt); E (-, -, sum p log pbar, sum tgt)
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
       int64_t row = r0 + wave_r * 64 + rt * 32 + r;
@@ -140,64 +128,33 @@ __global__ __launch_bounds__(256, 2) void msn_tiles(MsnArgs a) {
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) {
         float x[16];
-        float tm = ninf;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int64_t col = c0 + wave_c * 64 + ct * 32 + acc_row(i, h);
+          const int64_t col = pair_col(c0, wave_c, ct, i, h);
           const bool in = col < a.kp;
           const float xv = acc[ct][rt][i] * sc;
           const float t = in ? qrow[col] : 0.f;
           tq += t;
           if constexpr (MODE == MSN_LSE) {
             x[i] = in ? xv : ninf;
-            tm = fmaxf(tm, x[i]);
             ts = __builtin_fmaf(t, in ? xv : 0.f, ts);
           } else {
             const float p = in ? __builtin_amdgcn_exp2f(xv - lrow) : 0.f;
             ts = __builtin_fmaf(p, in ? msn_log_pbar(a.pbar[col]) : 0.f, ts);
           }
         }
-        if constexpr (MODE == MSN_LSE) {
-          if (tm > ninf) {
-            const float mn = fmaxf(m, tm);
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(x[i] - mn);
-            l = l * __builtin_amdgcn_exp2f(m - mn) + sum;
-            m = mn;
-          }
-        }
+        if constexpr (MODE == MSN_LSE) pair_fold16(m, l, x);
       }
-      const int rl = wave_r * 64 + rt * 32 + r, src = wave_c * 2 + h;
-      float* o = red + (rl * 4 + src) * 4;
-      o[0] = m;
-      o[1] = l;
-      o[2] = ts;
-      o[3] = tq;
+      pair_meet_put(lds, wave_c, wave_r, rt, lane, {m, l, ts, tq});
     }
-    __syncthreads();
-    if (tid < 128 && r0 + tid < a.n) {
-      const float* p = red + tid * 16;
-      float m = ninf, l = 0.f, ts = 0.f, tq = 0.f;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {  // fixed order: deterministic
-        if constexpr (MODE == MSN_LSE) pair_lse_merge(m, l, p[s * 4], p[s * 4 + 1]);
-        ts += p[s * 4 + 2];
-        tq += p[s * 4 + 3];
-      }
-      const int64_t o = (int64_t)blockIdx.x * a.n + r0 + tid;
-      if constexpr (MODE == MSN_LSE) {
-        a.pm[o] = m;
-        a.pl[o] = l;
-        a.pts[o] = ts;
-      } else {
-        a.pe[o] = ts;
-      }
-      a.ptq[o] = tq;
-    }
+    if constexpr (MODE == MSN_LSE)
+      pair_meet_store<4>(lds, tid, r0, a.n, 0.f, PairSum(), {a.pm, a.pl, a.pts, a.ptq});
+    else
+      pair_meet_store<4, false>(lds, tid, r0, a.n, 0.f, PairSum(), {nullptr, nullptr, a.pe, a.ptq});
   } else if constexpr (MODE == MSN_PBAR) {
     // column sums of p over this block's rows: the two row tiles in the lane, the 32 rows of a lane half by a fixed
     // butterfly, the two row waves in LDS
+    float* red = reinterpret_cast<float*>(lds);
     float s[2][16];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -228,12 +185,8 @@ __global__ __launch_bounds__(256, 2) void msn_tiles(MsnArgs a) {
     __syncthreads();
     if (tid < 128 && c0 + tid < a.kp) a.pbar_part[(int64_t)blockIdx.y * a.kp + c0 + tid] = red[tid] + red[128 + tid];
   } else {
-    // G: the lane's 16 registers per MFMA tile are 4 groups of 4 consecutive columns -> 8-byte fp16 stores.  1 / N and
-    // grad_out stay out of the fp16 image (p / N would be an fp16 subnormal at the workload's N)
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      const int64_t row = r0 + wave_r * 64 + rt * 32 + r;
-      if (row >= a.n) continue;
+    // G.  1 / N and grad_out stay out of the fp16 image (p / N would be an fp16 subnormal at the workload's N)
+    pair_write_image(acc, a.gmat, c0, a.kp, r0, a.n, wave_c, wave_r, lane, [&](int64_t row) {
       const float sc = a.rinv[row] * a.scale_log2;
       const float lrow = a.row_lse[row] * kLog2e;
       const float* qrow = a.q + (row % a.b) * a.kp;
@@ -242,24 +195,18 @@ __global__ __launch_bounds__(256, 2) void msn_tiles(MsnArgs a) {
         tq += a.ptq[(int64_t)p * a.n + row];
         e += a.pe[(int64_t)p * a.n + row];
       }
+      return [=](int64_t col0, f32x4 dot) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(qrow + col0);
+        const f32x4 pb = *reinterpret_cast<const f32x4*>(a.pbar + col0);
+        f32x4 g;
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-          const int64_t col0 = c0 + wave_c * 64 + ct * 32 + 8 * grp + 4 * h;
-          if (col0 >= a.kp) continue;  // K is a multiple of 8: a group of 4 is inside or outside
-          const f32x4 t = *reinterpret_cast<const f32x4*>(qrow + col0);
-          const f32x4 pb = *reinterpret_cast<const f32x4*>(a.pbar + col0);
-          f16x4 o;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float p = __builtin_amdgcn_exp2f(acc[ct][rt][4 * grp + k] * sc - lrow);
-            o[k] = (_Float16)(p * (tq + a.w * (msn_log_pbar(pb[k]) - e)) - t[k]);
-          }
-          *reinterpret_cast<f16x4*>(a.gmat + row * a.kp + col0) = o;
+        for (int k = 0; k < 4; ++k) {
+          const float p = __builtin_amdgcn_exp2f(dot[k] * sc - lrow);
+          g[k] = p * (tq + a.w * (msn_log_pbar(pb[k]) - e)) - t[k];
         }
-      }
-    }
+        return g;
+      };
+    });
   }
 }
 
@@ -320,18 +267,11 @@ __global__ __launch_bounds__(256) void msn_rows(const float* __restrict__ pm, co
                                                 float* __restrict__ row_ce) {
   const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n) return;
-  float m = -__builtin_huge_valf(), l = 0.f, ts = 0.f, tq = 0.f;
-  for (int p = 0; p < nparts; ++p) {
-    const int64_t o = (int64_t)p * n + row;
-    const float mp = pm[o], lp = pl[o];
-    if (lp > 0.f) {
-      const float mn = fmaxf(m, mp);
-      l = l * exp2f(m - mn) + lp * exp2f(mp - mn);
-      m = mn;
-    }
+  float m, l, ts = 0.f, tq = 0.f;
+  pair_merge_tiles(m, l, pm, pl, n, nparts, row, [&](int64_t o) {
     ts += pts[o];
     tq += ptq[o];
-  }
+  });
   const float lse2 = m + log2f(l);  // log2 domain
   row_lse[row] = lse2 * kLn2;
   row_ce[row] = (lse2 * tq - ts) * kLn2;  // sum_k -tgt_k (x_k - lse)
@@ -382,11 +322,8 @@ __global__ __launch_bounds__(256) void msn_bwd_finish(const float* __restrict__ 
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const float rn = rinv[row];
-  float gu = 0.f;
-  for (int k = lane; k < d; k += 64) gu = __builtin_fmaf(g[row * d + k], (float)x[row * d + k] * rn, gu);
-  gu = wave_sum(gu);
-  for (int k = lane; k < d; k += 64)
-    dx[row * d + k] = (T)(coef * rn * (g[row * d + k] - gu * ((float)x[row * d + k] * rn)));
+  pair_project_row(dx + row * d, d, lane, coef * rn, [&](int k) { return g[row * d + k]; },
+                   [&](int k) { return (float)x[row * d + k] * rn; });
 }
 
 enum { WS_TARGETS = 0, WS_FWD = 1, WS_BWD = 2 };
@@ -402,50 +339,40 @@ struct MsnWorkspace {
   size_t bytes;
 };
 
-MsnWorkspace msn_carve(void* base, int64_t n, int64_t kp, int d, int dtype, int stage) {
+MsnWorkspace msn_carve(void* base, int64_t n64, int64_t kp64, int d, int dtype, int stage) {
   MsnWorkspace w = {};
-  char* c = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = c ? c + off : nullptr;
-    off += (bytes + 255) & ~size_t(255);
-    return r;
-  };
-  auto takef = [&](size_t count) { return reinterpret_cast<float*>(take(count * 4)); };
-  const size_t es = dtype == HCIR_F32 ? 4 : 2;
-  const int64_t nct = hcir_cdiv(kp, 128), nrb = hcir_cdiv(n, 128);
-  w.cn = take((size_t)kp * d * es);
-  w.rinv = takef((size_t)n);
+  WsCarver c(base);
+  const size_t n = (size_t)n64, kp = (size_t)kp64;
+  const size_t nct = (size_t)hcir_cdiv(kp64, 128), nrb = (size_t)hcir_cdiv(n64, 128);
+  w.cn = c.take(kp * d * hcir_dtype_bytes(dtype));
+  w.rinv = c.take<float>(n);
   if (stage == WS_TARGETS) {
-    w.u = takef((size_t)kp);
-    w.v = takef((size_t)n);
+    w.u = c.take<float>(kp);
+    w.v = c.take<float>(n);
   } else if (stage == WS_FWD) {
-    w.pm = takef((size_t)nct * n);
-    w.pl = takef((size_t)nct * n);
-    w.pts = takef((size_t)nct * n);
-    w.ptq = takef((size_t)nct * n);
-    w.row_ce = takef((size_t)n);
-    w.pbar_part = takef((size_t)nrb * kp);
-    w.row_lse = takef((size_t)n);
-    w.pbar = takef((size_t)kp);
+    w.pm = c.take<float>(nct * n);
+    w.pl = c.take<float>(nct * n);
+    w.pts = c.take<float>(nct * n);
+    w.ptq = c.take<float>(nct * n);
+    w.row_ce = c.take<float>(n);
+    w.pbar_part = c.take<float>(nrb * kp);
+    w.row_lse = c.take<float>(n);
+    w.pbar = c.take<float>(kp);
   } else {
-    w.ptq = takef((size_t)nct * n);
-    w.pe = takef((size_t)nct * n);
-    w.ct = reinterpret_cast<_Float16*>(take((size_t)kp * d * 2));
-    w.gmat = reinterpret_cast<_Float16*>(take((size_t)n * kp * 2));
-    w.g = takef((size_t)n * d);
+    w.ptq = c.take<float>(nct * n);
+    w.pe = c.take<float>(nct * n);
+    w.ct = c.take<_Float16>(kp * d);
+    w.gmat = c.take<_Float16>(n * kp);
+    w.g = c.take<float>(n * d);
   }
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
 template <typename T, int MODE>
 void msn_launch_tiles(const MsnArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)hcir_cdiv(a.kp, 128), (unsigned)hcir_cdiv(a.n, 128));
-  if (a.d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((msn_tiles<T, true, MODE>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((msn_tiles<T, false, MODE>), grid, dim3(256), 0, st, a);
+  pair_launch_tiles<T>(msn_tiles<T, true, MODE>, msn_tiles<T, false, MODE>, grid, a, st);
 }
 
 template <typename T>
@@ -564,14 +491,6 @@ int msn_run_bwd(const void* anchors, const float* protos, const float* q, int64_
   return HCIR_OK;
 }
 
-// 128-row blocks ride on grid.y (<= 65535); the prototypes' pitch and the GEMM's K are 32-bit
-bool msn_shape_ok(int64_t n, int64_t kp, int32_t d, float inv_t) {
-  if (n <= 0 || kp <= 0 || d <= 0 || (d & 7) || n > 65535 * (int64_t)128 || kp > 0x7fffffff) return false;
-  return inv_t == inv_t && inv_t != 0.f;
-}
-
-bool msn_dtype_ok(int dtype) { return dtype == HCIR_F32 || dtype == HCIR_F16 || dtype == HCIR_BF16; }
-
 }  // namespace
 
 extern "C" {
@@ -585,57 +504,43 @@ int hcir_msn_targets(const void* targets, const float* prototypes, int64_t b, in
                      float inv_t_sharp, int32_t iterations, float* q, void* workspace, size_t workspace_bytes,
                      void* stream) {
   HCIR_ENTER();
-  if (!targets || !prototypes || !q || !msn_shape_ok(b, k, d, inv_t_sharp) || iterations < 0) return HCIR_ERR_INVALID;
-  if (!msn_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
+  if (!targets || !prototypes || !q || !pair_rows_cols_shape_ok(b, k, d, inv_t_sharp) || iterations < 0)
+    return HCIR_ERR_INVALID;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const MsnWorkspace w = msn_carve(workspace, b, k, d, dtype, WS_TARGETS);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32) return msn_run_targets<float>(targets, prototypes, b, k, d, inv_t_sharp, iterations, q, w, st);
-  if (dtype == HCIR_F16)
-    return msn_run_targets<_Float16>(targets, prototypes, b, k, d, inv_t_sharp, iterations, q, w, st);
-  return msn_run_targets<__bf16>(targets, prototypes, b, k, d, inv_t_sharp, iterations, q, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, msn_run_targets, targets, prototypes, b, k, d, inv_t_sharp, iterations, q, w, st);
 }
 
 int hcir_msn_fwd(const void* anchors, const float* prototypes, const float* q, int64_t n, int64_t b, int64_t k,
                  int32_t d, int dtype, float inv_t, float reg_weight, float* loss, float* loss_parts, float* row_lse,
                  float* pbar, void* workspace, size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
-  if (!anchors || !prototypes || !q || !loss || !msn_shape_ok(n, k, d, inv_t) || b <= 0 || n % b ||
+  if (!anchors || !prototypes || !q || !loss || !pair_rows_cols_shape_ok(n, k, d, inv_t) || b <= 0 || n % b ||
       reg_weight != reg_weight)
     return HCIR_ERR_INVALID;
-  if (!msn_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const MsnWorkspace w = msn_carve(workspace, n, k, d, dtype, WS_FWD);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32)
-    return msn_run_fwd<float>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, loss, loss_parts, row_lse, pbar, w,
-                              st);
-  if (dtype == HCIR_F16)
-    return msn_run_fwd<_Float16>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, loss, loss_parts, row_lse, pbar,
-                                 w, st);
-  return msn_run_fwd<__bf16>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, loss, loss_parts, row_lse, pbar, w,
-                             st);
+  return HCIR_DISPATCH_DTYPE(dtype, msn_run_fwd, anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, loss,
+                             loss_parts, row_lse, pbar, w, st);
 }
 
 int hcir_msn_bwd(const void* anchors, const float* prototypes, const float* q, int64_t n, int64_t b, int64_t k,
                  int32_t d, int dtype, float inv_t, float reg_weight, const float* row_lse, const float* pbar,
                  float grad_out, void* danchors, void* workspace, size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
-  if (!anchors || !prototypes || !q || !row_lse || !pbar || !danchors || !msn_shape_ok(n, k, d, inv_t) || (k & 7) ||
-      b <= 0 || n % b || reg_weight != reg_weight)
+  if (!anchors || !prototypes || !q || !row_lse || !pbar || !danchors || !pair_rows_cols_shape_ok(n, k, d, inv_t) ||
+      (k & 7) || b <= 0 || n % b || reg_weight != reg_weight)
     return HCIR_ERR_INVALID;
-  if (!msn_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const MsnWorkspace w = msn_carve(workspace, n, k, d, dtype, WS_BWD);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32)
-    return msn_run_bwd<float>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, row_lse, pbar, grad_out, danchors,
-                              w, st);
-  if (dtype == HCIR_F16)
-    return msn_run_bwd<_Float16>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, row_lse, pbar, grad_out,
-                                 danchors, w, st);
-  return msn_run_bwd<__bf16>(anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, row_lse, pbar, grad_out, danchors, w,
-                             st);
+  return HCIR_DISPATCH_DTYPE(dtype, msn_run_bwd, anchors, prototypes, q, n, b, k, d, inv_t, reg_weight, row_lse, pbar,
+                             grad_out, danchors, w, st);
 }
 
 }  // extern "C"

@@ -12,10 +12,12 @@
 //   ntxent_tiles  : sim_core.h tile engine; workgroup (x = column tile of 128, y = row block of
 //                   128); a lane owns one logits ROW and folds its 16 scores per MFMA tile
 //                   into an online (max, sum-of-exp2) pair; diagonal skipped, positive captured.
+//                   BWD = true: the same products, written as W in fp16 [2B, 2B].
 //   ntxent_rows   : one thread per row merges the per-column-tile partials in tile order
 //                   (deterministic), writes row_lse and the row's loss term.
 //   pair_mean_reduce (pair_tiles.h): one workgroup sums the 2B loss terms in a fixed tree -> mean loss.
-// The tile main loop and the online merge are pair_tiles.h, shared with supcon.hip.
+// The main loop, the fold, the meeting of a row's partials, the image writer, the merges and the row helpers are
+// pair_tiles.h, shared with supcon.hip, ntxent_bank.hip and msn.hip; here is what is NT-Xent's own.
 #include "pair_tiles.h"
 
 namespace {
@@ -27,13 +29,7 @@ __global__ __launch_bounds__(256) void ntxent_prep(const T* __restrict__ z0, con
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= 2 * b) return;
   const T* p = row < b ? z0 + row * d : z1 + (row - b) * d;
-  float s = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float v = (float)p[k];
-    s = __builtin_fmaf(v, v, s);
-  }
-  s = wave_sum(s);
-  const float inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+  const float inv = pair_row_inv_norm(p, d, lane);
   for (int k = lane; k < d; k += 64) zn[row * d + k] = (T)((float)p[k] * inv);
 }
 
@@ -57,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void ntxent_tiles(NtArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_c = wave >> 1, wave_r = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
+  const int h = lane >> 5;
   const T* zn = static_cast<const T*>(a.zn);
   const int64_t c0 = (int64_t)blockIdx.x * 128, r0 = (int64_t)blockIdx.y * 128;
 
@@ -66,88 +62,46 @@ __global__ __launch_bounds__(256, 2) void ntxent_tiles(NtArgs a) {
 
   const float ninf = -__builtin_huge_valf();
   if constexpr (BWD) {
-    // ---- backward tile: the lane owns logits row `row`; its 16 registers per MFMA tile are 4 groups
-    //      of 4 consecutive columns -> 8-byte fp16 stores into W[row][col..col+3]
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      const int64_t row = r0 + wave_r * 64 + rt * 32 + r;
-      if (row >= a.n) continue;
+    pair_write_image(acc, a.wmat, c0, a.n, r0, a.n, wave_c, wave_r, lane, [&](int64_t row) {
       const int64_t pos = row < a.b ? row + a.b : row - a.b;
       const float lrow = a.lse2[row];
+      return [=](int64_t col0, f32x4 dot) {
+        const f32x4 lcol = *reinterpret_cast<const f32x4*>(a.lse2 + col0);
+        f32x4 w;
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-          const int64_t col0 = c0 + wave_c * 64 + ct * 32 + 8 * grp + 4 * h;
-          if (col0 >= a.n) continue;  // n is a multiple of 8: a group of 4 is inside or outside
-          const f32x4 lcol = *reinterpret_cast<const f32x4*>(a.lse2 + col0);
-          f16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int64_t col = col0 + e;
-            const float x = acc[ct][rt][4 * grp + e] * a.scale_log2;
-            float w = __builtin_amdgcn_exp2f(x - lrow) + __builtin_amdgcn_exp2f(x - lcol[e]);
-            w = (col == pos) ? w - 2.0f : w;
-            w = (col == row) ? 0.f : w;
-            o[e] = (_Float16)w;
-          }
-          *reinterpret_cast<f16x4*>(a.wmat + row * a.n + col0) = o;
+        for (int e = 0; e < 4; ++e) {
+          const int64_t col = col0 + e;
+          const float x = dot[e] * a.scale_log2;
+          w[e] = __builtin_amdgcn_exp2f(x - lrow) + __builtin_amdgcn_exp2f(x - lcol[e]);
+          w[e] = (col == pos) ? w[e] - 2.0f : w[e];
+          w[e] = (col == row) ? 0.f : w[e];
         }
-      }
-    }
+        return w;
+      };
+    });
     return;
   }
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) {
-    const int64_t row = r0 + wave_r * 64 + rt * 32 + r;
+    const int64_t row = r0 + wave_r * 64 + rt * 32 + (lane & 31);
     const int64_t pos = row < a.b ? row + a.b : row - a.b;
     float m = ninf, l = 0.f, pv = ninf;
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       float x[16];
-      float tm = ninf;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int64_t col = c0 + wave_c * 64 + ct * 32 + acc_row(i, h);
+        const int64_t col = pair_col(c0, wave_c, ct, i, h);
         const float v = acc[ct][rt][i] * a.scale_log2;
         const bool live = col < a.n && col != row;
         x[i] = live ? v : ninf;
         pv = (col == pos) ? v : pv;
-        tm = fmaxf(tm, x[i]);
       }
-      if (tm > ninf) {
-        const float mn = fmaxf(m, tm);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(x[i] - mn);
-        l = l * __builtin_amdgcn_exp2f(m - mn) + sum;
-        m = mn;
-      }
+      pair_fold16(m, l, x);
     }
-    // the four (wave_c, lane-half) partials of a row meet in LDS: [128 rows][4 src][m, l, p]
-    {
-      float* red = reinterpret_cast<float*>(lds);
-      const int rl = wave_r * 64 + rt * 32 + r, src = wave_c * 2 + h;
-      red[(rl * 4 + src) * 3 + 0] = m;
-      red[(rl * 4 + src) * 3 + 1] = l;
-      red[(rl * 4 + src) * 3 + 2] = pv;
-    }
+    pair_meet_put(lds, wave_c, wave_r, rt, lane, {m, l, pv});
   }
-  __syncthreads();
-  if (tid < 128 && r0 + tid < a.n) {
-    const float* red = reinterpret_cast<const float*>(lds) + tid * 12;
-    float m = ninf, l = 0.f, pv = ninf;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {  // fixed order: deterministic
-      const float mp = red[s * 3], lp = red[s * 3 + 1];
-      pv = fmaxf(pv, red[s * 3 + 2]);
-      pair_lse_merge(m, l, mp, lp);
-    }
-    const int64_t o = (int64_t)blockIdx.x * a.n + r0 + tid;
-    a.pm[o] = m;
-    a.pl[o] = l;
-    a.pp[o] = pv;
-  }
+  pair_meet_store<3>(lds, tid, r0, a.n, ninf, [](float x, float y) { return fmaxf(x, y); }, {a.pm, a.pl, a.pp});
 }
 
 // one thread per logits row: merge the per-column-tile partials in tile order, write
@@ -159,33 +113,19 @@ __global__ __launch_bounds__(256) void ntxent_rows(const float* __restrict__ pm,
                                                    float* __restrict__ row_lse) {
   const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n) return;
-  float m = -__builtin_huge_valf(), l = 0.f, pv = -__builtin_huge_valf();
-  for (int p = 0; p < nparts; ++p) {
-    const float mp = pm[(int64_t)p * n + row], lp = pl[(int64_t)p * n + row];
-    pv = fmaxf(pv, pp[(int64_t)p * n + row]);
-    if (lp > 0.f) {
-      const float mn = fmaxf(m, mp);
-      l = l * exp2f(m - mn) + lp * exp2f(mp - mn);
-      m = mn;
-    }
-  }
+  float m, l, pv = -__builtin_huge_valf();
+  pair_merge_tiles(m, l, pm, pl, n, nparts, row, [&](int64_t o) { pv = fmaxf(pv, pp[o]); });
   const float lse2 = m + log2f(l);  // log2 domain
   if (row_lse) row_lse[row] = lse2 * kLn2;
   row_loss[row] = (lse2 - pv) * kLn2;
 }
 
-// zt[k][i] = zn[i][k] as fp16 (the "weight" operand of dU = W . U on hcir_gemm_f16), and lse -> log2 domain
-template <typename T>
-__global__ void ntxent_bwd_prep(const T* __restrict__ zn, const float* __restrict__ row_lse, int64_t n, int d,
-                                _Float16* __restrict__ zt, float* __restrict__ lse2) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) lse2[t] = row_lse[t] * kLog2e;
-  if (t < n * d) {
-    const int64_t i = t / d;
-    const int k = (int)(t - i * d);
-    zt[(int64_t)k * n + i] = (_Float16)(float)zn[t];
-  }
-}
+// the backward tile's per-row scalar: lse -> log2 domain
+struct NtRowScalars {
+  const float* row_lse;
+  float* lse2;
+  __device__ void operator()(int64_t i) const { lse2[i] = row_lse[i] * kLog2e; }
+};
 
 // dx_i = coef * rn_i * (g_i - (g_i . u_i) u_i), one wave per row; g = W.U (fp32), u = normalised row
 template <typename T>
@@ -198,17 +138,9 @@ __global__ __launch_bounds__(256) void ntxent_bwd_finish(const float* __restrict
   if (row >= 2 * b) return;
   const T* x = row < b ? z0 + row * d : z1 + (row - b) * d;
   T* dx = row < b ? dz0 + row * d : dz1 + (row - b) * d;
-  float ss = 0.f, gu = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float xv = (float)x[k];
-    ss = __builtin_fmaf(xv, xv, ss);
-    gu = __builtin_fmaf(g[row * d + k], (float)zn[row * d + k], gu);
-  }
-  ss = wave_sum(ss);
-  gu = wave_sum(gu);
-  const float rn = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-  for (int k = lane; k < d; k += 64)
-    dx[k] = (T)(coef * rn * (g[row * d + k] - gu * (float)zn[row * d + k]));
+  const float rn = pair_row_inv_norm(x, d, lane);
+  pair_project_row(dx, d, lane, coef * rn, [&](int k) { return g[row * d + k]; },
+                   [&](int k) { return (float)zn[row * d + k]; });
 }
 
 struct NtWorkspace {
@@ -221,31 +153,21 @@ struct NtWorkspace {
 };
 
 NtWorkspace nt_carve(void* base, int64_t b, int d, int dtype, bool bwd = false) {
-  NtWorkspace w;
-  char* c = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    char* r = c ? c + off : nullptr;
-    off += (n + 255) & ~size_t(255);
-    return r;
-  };
-  const int64_t n = 2 * b;
-  const int64_t nct = hcir_cdiv(n, 128);
-  w.zn = take((size_t)n * d * (dtype == HCIR_F32 ? 4 : 2));
-  w.pm = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-  w.pl = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-  w.pp = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-  w.row_loss = reinterpret_cast<float*>(take((size_t)n * 4));
-  w.wmat = nullptr;
-  w.zt = nullptr;
-  w.lse2 = w.g = nullptr;
+  NtWorkspace w = {};
+  WsCarver c(base);
+  const size_t n = 2 * (size_t)b, nct = (size_t)hcir_cdiv(2 * b, 128);
+  w.zn = c.take(n * d * hcir_dtype_bytes(dtype));
+  w.pm = c.take<float>(nct * n);
+  w.pl = c.take<float>(nct * n);
+  w.pp = c.take<float>(nct * n);
+  w.row_loss = c.take<float>(n);
   if (bwd) {
-    w.wmat = reinterpret_cast<_Float16*>(take((size_t)n * n * 2));
-    w.zt = reinterpret_cast<_Float16*>(take((size_t)n * d * 2));
-    w.lse2 = reinterpret_cast<float*>(take((size_t)n * 4));
-    w.g = reinterpret_cast<float*>(take((size_t)n * d * 4));
+    w.wmat = c.take<_Float16>(n * n);
+    w.zt = c.take<_Float16>(n * d);
+    w.lse2 = c.take<float>(n);
+    w.g = c.take<float>(n * d);
   }
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
@@ -258,10 +180,7 @@ int nt_run(const void* z0, const void* z1, int64_t b, int d, float inv_t, float*
                      static_cast<const T*>(z0), static_cast<const T*>(z1), b, d, static_cast<T*>(w.zn));
   HCIR_LAUNCH_CHECK();
   NtArgs a{w.zn, w.pm, w.pl, w.pp, n, b, d, inv_t * kLog2e, nullptr, nullptr};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((ntxent_tiles<T, true>), dim3(nct, nct), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((ntxent_tiles<T, false>), dim3(nct, nct), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(ntxent_tiles<T, true>, ntxent_tiles<T, false>, dim3(nct, nct), a, st);
   HCIR_LAUNCH_CHECK();
   hipLaunchKernelGGL(ntxent_rows, dim3((unsigned)hcir_cdiv(n, 256)), dim3(256), 0, st, w.pm, w.pl, w.pp, n,
                      nct, w.row_loss, row_lse);
@@ -279,14 +198,11 @@ int nt_run_bwd(const void* z0, const void* z1, int64_t b, int d, float inv_t, co
   hipLaunchKernelGGL(ntxent_prep<T>, dim3((unsigned)hcir_cdiv(n, 4)), dim3(256), 0, st,
                      static_cast<const T*>(z0), static_cast<const T*>(z1), b, d, static_cast<T*>(w.zn));
   HCIR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ntxent_bwd_prep<T>, dim3((unsigned)hcir_cdiv(n * d, 256)), dim3(256), 0, st,
-                     static_cast<const T*>(w.zn), row_lse, n, d, w.zt, w.lse2);
+  hipLaunchKernelGGL((pair_transpose_f16<T, NtRowScalars>), dim3((unsigned)hcir_cdiv(n * d, 256)), dim3(256), 0, st,
+                     static_cast<const T*>(w.zn), n, d, w.zt, NtRowScalars{row_lse, w.lse2});
   HCIR_LAUNCH_CHECK();
   NtArgs a{w.zn, w.pm, w.pl, w.pp, n, b, d, inv_t * kLog2e, w.lse2, w.wmat};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((ntxent_tiles<T, true, true>), dim3(nct, nct), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((ntxent_tiles<T, false, true>), dim3(nct, nct), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(ntxent_tiles<T, true, true>, ntxent_tiles<T, false, true>, dim3(nct, nct), a, st);
   HCIR_LAUNCH_CHECK();
   // g[2B][D] = W[2B][2B] . U[2B][D]  ==  hcir_gemm_f16(A = W, "weights" = U^T [D][2B])
   const int rc = hcir_gemm_f16(w.wmat, n, w.zt, n, nullptr, nullptr, n, d, (int32_t)n, HCIR_EPI_BIAS_F32,
@@ -313,14 +229,12 @@ int hcir_ntxent_bwd(const void* z0, const void* z1, int64_t b, int32_t d, int dt
                     size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
   if (!z0 || !z1 || !row_lse || !dz0 || !dz1 || b <= 0 || d <= 0 || (d & 7) || (b & 3)) return HCIR_ERR_INVALID;
-  if (!(inv_t == inv_t) || inv_t == 0.f) return HCIR_ERR_INVALID;  // as hcir_ntxent_fwd: no gradient of a loss it refuses
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_inv_t_ok(inv_t)) return HCIR_ERR_INVALID;  // as hcir_ntxent_fwd: no gradient of a loss it refuses
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const NtWorkspace w = nt_carve(workspace, b, d, dtype, true);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32) return nt_run_bwd<float>(z0, z1, b, d, inv_t, row_lse, grad_out, dz0, dz1, w, st);
-  if (dtype == HCIR_F16) return nt_run_bwd<_Float16>(z0, z1, b, d, inv_t, row_lse, grad_out, dz0, dz1, w, st);
-  return nt_run_bwd<__bf16>(z0, z1, b, d, inv_t, row_lse, grad_out, dz0, dz1, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, nt_run_bwd, z0, z1, b, d, inv_t, row_lse, grad_out, dz0, dz1, w, st);
 }
 
 size_t hcir_ntxent_workspace_bytes(int64_t b, int32_t d, int dtype) {
@@ -333,14 +247,12 @@ int hcir_ntxent_fwd(const void* z0, const void* z1, int64_t b, int32_t d, int dt
                     void* stream) {
   HCIR_ENTER();
   if (!z0 || !z1 || !loss || b <= 0 || d <= 0 || (d & 7)) return HCIR_ERR_INVALID;
-  if (!(inv_t == inv_t) || inv_t == 0.f) return HCIR_ERR_INVALID;
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_inv_t_ok(inv_t)) return HCIR_ERR_INVALID;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const NtWorkspace w = nt_carve(workspace, b, d, dtype);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32) return nt_run<float>(z0, z1, b, d, inv_t, loss, row_lse, w, st);
-  if (dtype == HCIR_F16) return nt_run<_Float16>(z0, z1, b, d, inv_t, loss, row_lse, w, st);
-  return nt_run<__bf16>(z0, z1, b, d, inv_t, loss, row_lse, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, nt_run, z0, z1, b, d, inv_t, loss, row_lse, w, st);
 }
 
 }  // extern "C"

@@ -49,16 +49,9 @@ __global__ __launch_bounds__(256) void bank_prep(const T* __restrict__ z0, const
   }
   const T* p0 = z0 + row * d;
   const T* p1 = z1 + row * d;
-  float s0 = 0.f, s1 = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float a = (float)p0[k], b = (float)p1[k];
-    s0 = __builtin_fmaf(a, a, s0);
-    s1 = __builtin_fmaf(b, b, s1);
-  }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  const float inv0 = 1.0f / fmaxf(sqrtf(s0), 1e-12f);
-  const float inv1 = 1.0f / fmaxf(sqrtf(s1), 1e-12f);
+  float inv[2];
+  pair_rows_inv_norm<2, T>({p0, p1}, d, lane, inv);
+  const float inv0 = inv[0], inv1 = inv[1];
   float dot = 0.f;
   for (int k = lane; k < d; k += 64) {
     const float ku = (float)p1[k] * inv1;
@@ -92,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void bank_tiles(BkArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_c = wave >> 1, wave_r = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
+  const int h = lane >> 5;
   const int64_t c0 = (int64_t)blockIdx.x * 128, r0 = (int64_t)blockIdx.y * 128;
 
   f32x16 acc[2][2];
@@ -101,27 +94,15 @@ __global__ __launch_bounds__(256, 2) void bank_tiles(BkArgs a) {
 
   const float ninf = -__builtin_huge_valf();
   if constexpr (BWD) {
-    // the lane owns logits row `row`; its 16 registers per MFMA tile are 4 groups of 4 consecutive columns -> 8-byte
-    // fp16 stores into P[row][col..col+3]
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      const int64_t row = r0 + wave_r * 64 + rt * 32 + r;
-      if (row >= a.n) continue;
+    pair_write_image(acc, a.pmat, c0, a.kb, r0, a.n, wave_c, wave_r, lane, [&](int64_t row) {
       const float lrow = a.row_lse[row] * kLog2e;
+      return [=](int64_t, f32x4 dot) {
+        f32x4 p;
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-          const int64_t col0 = c0 + wave_c * 64 + ct * 32 + 8 * grp + 4 * h;
-          if (col0 >= a.kb) continue;  // K is a multiple of 8: a group of 4 is inside or outside
-          f16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            o[e] = (_Float16)__builtin_amdgcn_exp2f(acc[ct][rt][4 * grp + e] * a.scale_log2 - lrow);
-          *reinterpret_cast<f16x4*>(a.pmat + row * a.kb + col0) = o;
-        }
-      }
-    }
+        for (int e = 0; e < 4; ++e) p[e] = __builtin_amdgcn_exp2f(dot[e] * a.scale_log2 - lrow);
+        return p;
+      };
+    });
     return;
   }
 #pragma unroll
@@ -130,38 +111,14 @@ __global__ __launch_bounds__(256, 2) void bank_tiles(BkArgs a) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       float x[16];
-      float tm = ninf;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int64_t col = c0 + wave_c * 64 + ct * 32 + acc_row(i, h);
-        x[i] = col < a.kb ? acc[ct][rt][i] * a.scale_log2 : ninf;
-        tm = fmaxf(tm, x[i]);
-      }
-      if (tm > ninf) {
-        const float mn = fmaxf(m, tm);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(x[i] - mn);
-        l = l * __builtin_amdgcn_exp2f(m - mn) + sum;
-        m = mn;
-      }
+      for (int i = 0; i < 16; ++i)
+        x[i] = pair_col(c0, wave_c, ct, i, h) < a.kb ? acc[ct][rt][i] * a.scale_log2 : ninf;
+      pair_fold16(m, l, x);
     }
-    // the four (wave_c, lane-half) partials of a row meet in LDS: [128 rows][4 src][m, l]
-    float* red = reinterpret_cast<float*>(lds);
-    const int rl = wave_r * 64 + rt * 32 + r, src = wave_c * 2 + h;
-    red[(rl * 4 + src) * 2 + 0] = m;
-    red[(rl * 4 + src) * 2 + 1] = l;
+    pair_meet_put(lds, wave_c, wave_r, rt, lane, {m, l});
   }
-  __syncthreads();
-  if (tid < 128 && r0 + tid < a.n) {
-    const float* red = reinterpret_cast<const float*>(lds) + tid * 8;
-    float m = ninf, l = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) pair_lse_merge(m, l, red[s * 2], red[s * 2 + 1]);  // fixed order: deterministic
-    const int64_t o = (int64_t)blockIdx.x * a.n + r0 + tid;
-    a.pm[o] = m;
-    a.pl[o] = l;
-  }
+  pair_meet_store<2>(lds, tid, r0, a.n, 0.f, PairSum(), {a.pm, a.pl});
 }
 
 // one thread per logits row: merge the per-bank-tile partials in tile order, then the positive as one more term
@@ -171,17 +128,11 @@ __global__ __launch_bounds__(256) void bank_rows(const float* __restrict__ pm, c
                                                  float* __restrict__ row_lse, float* __restrict__ row_pos) {
   const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n) return;
-  float m = -__builtin_huge_valf(), l = 0.f;
-  for (int p = 0; p < nparts; ++p) {
-    const float mp = pm[(int64_t)p * n + row], lp = pl[(int64_t)p * n + row];
-    if (lp > 0.f) {
-      const float mn = fmaxf(m, mp);
-      l = l * exp2f(m - mn) + lp * exp2f(mp - mn);
-      m = mn;
-    }
-  }
+  float m, l;
+  pair_merge_tiles(m, l, pm, pl, n, nparts, row, [](int64_t) {});
   const float pv = pos[row] * scale_log2;
-  {
+  {  // not pair_lse_merge<true>(m, l, pv, 1): that one is compiled without contraction, this term is compiled with it
+     // (pv - mn and the sum are fused), and the results are pinned to the bit
     const float mn = fmaxf(m, pv);
     l = l * exp2f(m - mn) + exp2f(pv - mn);
     m = mn;
@@ -204,33 +155,14 @@ __global__ __launch_bounds__(256) void bank_bwd_finish(const float* __restrict__
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const float c0 = __builtin_amdgcn_exp2f((row_pos[row] - row_lse[row]) * kLog2e) - 1.0f;
-  float ss0 = 0.f, ss1 = 0.f, gu = 0.f, qk = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float a = (float)z0[row * d + k];
-    const float q = (float)qn[row * d + k], kk = (float)kn[row * d + k];
-    ss0 = __builtin_fmaf(a, a, ss0);
-    gu = __builtin_fmaf(__builtin_fmaf(c0, kk, g[row * d + k]), q, gu);
-    if (dz1) {  // the key's norm and q.k are the key's gradient's alone
-      const float b = (float)z1[row * d + k];
-      ss1 = __builtin_fmaf(b, b, ss1);
-      qk = __builtin_fmaf(q, kk, qk);
-    }
-  }
-  ss0 = wave_sum(ss0);
-  gu = wave_sum(gu);
-  const float rn0 = 1.0f / fmaxf(sqrtf(ss0), 1e-12f);
-  for (int k = lane; k < d; k += 64) {
-    const float q = (float)qn[row * d + k], kk = (float)kn[row * d + k];
-    dz0[row * d + k] = (T)(coef * rn0 * (__builtin_fmaf(c0, kk, g[row * d + k]) - gu * q));
-  }
-  if (!dz1) return;
-  ss1 = wave_sum(ss1);
-  qk = wave_sum(qk);
-  const float rn1 = 1.0f / fmaxf(sqrtf(ss1), 1e-12f);
-  for (int k = lane; k < d; k += 64) {
-    const float q = (float)qn[row * d + k], kk = (float)kn[row * d + k];
-    dz1[row * d + k] = (T)(coef * rn1 * c0 * (q - qk * kk));
-  }
+  const auto q = [&](int k) { return (float)qn[row * d + k]; };
+  const auto kk = [&](int k) { return (float)kn[row * d + k]; };
+  const float rn0 = pair_row_inv_norm(z0 + row * d, d, lane);
+  pair_project_row(dz0 + row * d, d, lane, coef * rn0,
+                   [&](int k) { return __builtin_fmaf(c0, kk(k), g[row * d + k]); }, q);
+  if (!dz1) return;  // the key's norm and q.k are the key's gradient's alone
+  const float rn1 = pair_row_inv_norm(z1 + row * d, d, lane);
+  pair_project_row(dz1 + row * d, d, lane, coef * rn1 * c0, q, kk);
 }
 
 struct BkWorkspace {
@@ -242,34 +174,24 @@ struct BkWorkspace {
   size_t bytes;
 };
 
-BkWorkspace bk_carve(void* base, int64_t n, int64_t kb, int d, int dtype, bool bwd) {
-  BkWorkspace w;
-  char* c = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = c ? c + off : nullptr;
-    off += (bytes + 255) & ~size_t(255);
-    return r;
-  };
-  const size_t es = dtype == HCIR_F32 ? 4 : 2;
-  const int64_t nct = hcir_cdiv(kb, 128);
-  w.qn = take((size_t)n * d * es);
-  w.kn = take((size_t)n * d * es);
-  w.bankc = take((size_t)kb * d * es);
-  w.pos = reinterpret_cast<float*>(take((size_t)n * 4));
-  w.pm = w.pl = w.row_loss = nullptr;
-  w.pmat = w.bt = nullptr;
-  w.g = nullptr;
+BkWorkspace bk_carve(void* base, int64_t n64, int64_t kb64, int d, int dtype, bool bwd) {
+  BkWorkspace w = {};
+  WsCarver c(base);
+  const size_t n = (size_t)n64, kb = (size_t)kb64, es = hcir_dtype_bytes(dtype), nct = (size_t)hcir_cdiv(kb64, 128);
+  w.qn = c.take(n * d * es);
+  w.kn = c.take(n * d * es);
+  w.bankc = c.take(kb * d * es);
+  w.pos = c.take<float>(n);
   if (bwd) {
-    w.pmat = reinterpret_cast<_Float16*>(take((size_t)n * kb * 2));
-    w.bt = reinterpret_cast<_Float16*>(take((size_t)kb * d * 2));
-    w.g = reinterpret_cast<float*>(take((size_t)n * d * 4));
+    w.pmat = c.take<_Float16>(n * kb);
+    w.bt = c.take<_Float16>(kb * d);
+    w.g = c.take<float>(n * d);
   } else {
-    w.pm = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.pl = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.row_loss = reinterpret_cast<float*>(take((size_t)n * 4));
+    w.pm = c.take<float>(nct * n);
+    w.pl = c.take<float>(nct * n);
+    w.row_loss = c.take<float>(n);
   }
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
@@ -288,10 +210,7 @@ int bk_run(const void* z0, const void* z1, const float* bank, int64_t n, int64_t
   bk_launch_prep<T>(z0, z1, bank, n, kb, d, w, k_unit, st);
   HCIR_LAUNCH_CHECK();
   BkArgs a{w.qn, w.bankc, w.pm, w.pl, n, kb, d, inv_t * kLog2e, nullptr, nullptr};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((bank_tiles<T, true>), dim3(nct, nrb), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((bank_tiles<T, false>), dim3(nct, nrb), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(bank_tiles<T, true>, bank_tiles<T, false>, dim3(nct, nrb), a, st);
   HCIR_LAUNCH_CHECK();
   hipLaunchKernelGGL(bank_rows, dim3((unsigned)hcir_cdiv(n, 256)), dim3(256), 0, st, w.pm, w.pl, w.pos, n, nct, inv_t,
                      inv_t * kLog2e, w.row_loss, row_lse, row_pos);
@@ -309,10 +228,7 @@ int bk_run_bwd(const void* z0, const void* z1, const float* bank, int64_t n, int
   bk_launch_prep<T>(z0, z1, bank, n, kb, d, w, nullptr, st);
   HCIR_LAUNCH_CHECK();
   BkArgs a{w.qn, w.bankc, nullptr, nullptr, n, kb, d, inv_t * kLog2e, row_lse, w.pmat};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((bank_tiles<T, true, true>), dim3(nct, nrb), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((bank_tiles<T, false, true>), dim3(nct, nrb), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(bank_tiles<T, true, true>, bank_tiles<T, false, true>, dim3(nct, nrb), a, st);
   HCIR_LAUNCH_CHECK();
   // g[N][D] = P[N][K] . bank[K][D]  ==  hcir_gemm_f16(A = P, "weights" = bank^T [D][K])
   const int rc = hcir_gemm_f16(w.pmat, kb, w.bt, kb, nullptr, nullptr, n, d, (int32_t)kb, HCIR_EPI_BIAS_F32, w.g, d, st);
@@ -323,12 +239,6 @@ int bk_run_bwd(const void* z0, const void* z1, const float* bank, int64_t n, int
                      static_cast<T*>(dz0), static_cast<T*>(dz1));
   HCIR_LAUNCH_CHECK();
   return HCIR_OK;
-}
-
-// 128-row blocks ride on grid.y (<= 65535); the bank's pitch and the GEMM's K are 32-bit
-bool bk_shape_ok(int64_t n, int64_t kb, int32_t d, float inv_t) {
-  if (n <= 0 || kb <= 0 || d <= 0 || (d & 7) || n > 65535 * (int64_t)128 || kb > 0x7fffffff) return false;
-  return inv_t == inv_t && inv_t != 0.f;
 }
 
 }  // namespace
@@ -344,31 +254,26 @@ int hcir_ntxent_bank_fwd(const void* z0, const void* z1, const float* bank, int6
                          float inv_t, float* loss, float* row_lse, float* row_pos, float* k_unit, void* workspace,
                          size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
-  if (!z0 || !z1 || !bank || !loss || !bk_shape_ok(n, k, d, inv_t)) return HCIR_ERR_INVALID;
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!z0 || !z1 || !bank || !loss || !pair_rows_cols_shape_ok(n, k, d, inv_t)) return HCIR_ERR_INVALID;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const BkWorkspace w = bk_carve(workspace, n, k, d, dtype, false);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32) return bk_run<float>(z0, z1, bank, n, k, d, inv_t, loss, row_lse, row_pos, k_unit, w, st);
-  if (dtype == HCIR_F16) return bk_run<_Float16>(z0, z1, bank, n, k, d, inv_t, loss, row_lse, row_pos, k_unit, w, st);
-  return bk_run<__bf16>(z0, z1, bank, n, k, d, inv_t, loss, row_lse, row_pos, k_unit, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, bk_run, z0, z1, bank, n, k, d, inv_t, loss, row_lse, row_pos, k_unit, w, st);
 }
 
 int hcir_ntxent_bank_bwd(const void* z0, const void* z1, const float* bank, int64_t n, int64_t k, int32_t d, int dtype,
                          float inv_t, const float* row_lse, const float* row_pos, float grad_out, void* dz0, void* dz1,
                          void* workspace, size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
-  if (!z0 || !z1 || !bank || !row_lse || !row_pos || !dz0 || !bk_shape_ok(n, k, d, inv_t) || (k & 7))
+  if (!z0 || !z1 || !bank || !row_lse || !row_pos || !dz0 || !pair_rows_cols_shape_ok(n, k, d, inv_t) || (k & 7))
     return HCIR_ERR_INVALID;
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const BkWorkspace w = bk_carve(workspace, n, k, d, dtype, true);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32)
-    return bk_run_bwd<float>(z0, z1, bank, n, k, d, inv_t, row_lse, row_pos, grad_out, dz0, dz1, w, st);
-  if (dtype == HCIR_F16)
-    return bk_run_bwd<_Float16>(z0, z1, bank, n, k, d, inv_t, row_lse, row_pos, grad_out, dz0, dz1, w, st);
-  return bk_run_bwd<__bf16>(z0, z1, bank, n, k, d, inv_t, row_lse, row_pos, grad_out, dz0, dz1, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, bk_run_bwd, z0, z1, bank, n, k, d, inv_t, row_lse, row_pos, grad_out, dz0, dz1, w,
+                             st);
 }
 
 }  // extern "C"

@@ -20,8 +20,8 @@
 //   supcon_rows       : one thread per row merges the per-column-tile partials in tile order (deterministic), writes
 //                       row_lse, row_npos and the row's loss term.
 //   pair_mean_reduce  : (pair_tiles.h) fixed-tree mean of the N loss terms.
-//   supcon_bwd_prep   : x^T as fp16 for hcir_gemm_f16, lse -> log2 domain (+inf for a row without positives, so
-//                       that its softmax terms vanish), 2 / n_i.
+//   pair_transpose_f16: (pair_tiles.h) x^T as fp16 for hcir_gemm_f16; with it ScRowScalars: lse -> log2 domain (+inf
+//                       for a row without positives, so that its softmax terms vanish), 2 / n_i.
 //   supcon_bwd_finish : scale (and projection), scatter back to [B, V, D] in the input dtype.
 // No atomics anywhere: the results are deterministic from run to run.
 #include "pair_tiles.h"
@@ -37,15 +37,8 @@ __global__ __launch_bounds__(256) void supcon_prep(const T* __restrict__ feat, c
   if (row >= b * v) return;
   const int64_t view = row / b, i = row - view * b;
   const T* p = feat + (i * v + view) * d;
-  float inv = 1.0f;
   if (normalize) {
-    float s = 0.f;
-    for (int k = lane; k < d; k += 64) {
-      const float x = (float)p[k];
-      s = __builtin_fmaf(x, x, s);
-    }
-    s = wave_sum(s);
-    inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+    const float inv = pair_row_inv_norm(p, d, lane);
     for (int k = lane; k < d; k += 64) xn[row * d + k] = (T)((float)p[k] * inv);
   } else {
     for (int k = lane; k < d; k += 64) xn[row * d + k] = p[k];
@@ -69,7 +62,7 @@ struct ScArgs {
   _Float16* wmat;
 };
 
-constexpr int kRedBytes = 128 * 4 * 4 * 4;  // [128 rows][4 src][m, l, ps, pc]; the column labels follow
+constexpr int kRedBytes = 128 * 4 * 4 * 4;  // pair_meet's [128 rows][4 src][m, l, ps, pc]; the column labels follow
 
 template <typename T, bool GLDS, bool BWD = false>
 __global__ __launch_bounds__(256, 2) void supcon_tiles(ScArgs a) {
@@ -99,37 +92,24 @@ __global__ __launch_bounds__(256, 2) void supcon_tiles(ScArgs a) {
 
   const float ninf = -__builtin_huge_valf();
   if constexpr (BWD) {
-    // ---- backward tile: the lane owns logits row `row`; its 16 registers per MFMA tile are 4 groups
-    //      of 4 consecutive columns -> 8-byte fp16 stores into W[row][col..col+3]
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-      const int64_t row = r0 + wave_r * 64 + rt * 32 + r;
-      if (row >= a.n) continue;
+    pair_write_image(acc, a.wmat, c0, a.n, r0, a.n, wave_c, wave_r, lane, [&](int64_t row) {
       const int64_t yrow = a.y[row];
       const float lrow = a.lse2[row], tw = a.twon[row];
+      return [=](int64_t col0, f32x4 dot) {
+        const f32x4 lcol = *reinterpret_cast<const f32x4*>(a.lse2 + col0);
+        const int cl = (int)(col0 - c0);
+        f32x4 w;
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-          const int cl = wave_c * 64 + ct * 32 + 8 * grp + 4 * h;
-          const int64_t col0 = c0 + cl;
-          if (col0 >= a.n) continue;  // n is a multiple of 8: a group of 4 is inside or outside
-          const f32x4 lcol = *reinterpret_cast<const f32x4*>(a.lse2 + col0);
-          f16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int64_t col = col0 + e;
-            const float x = acc[ct][rt][4 * grp + e] * a.scale_log2;
-            // lse2 = +inf for a row without positives: its exp2 is 0
-            float w = __builtin_amdgcn_exp2f(x - lrow) + __builtin_amdgcn_exp2f(x - lcol[e]);
-            w = (lab[cl + e] == yrow) ? w - tw : w;  // same class: n_col == n_row
-            w = (col == row) ? 0.f : w;
-            o[e] = (_Float16)w;
-          }
-          *reinterpret_cast<f16x4*>(a.wmat + row * a.n + col0) = o;
+        for (int e = 0; e < 4; ++e) {
+          const float x = dot[e] * a.scale_log2;
+          // lse2 = +inf for a row without positives: its exp2 is 0
+          w[e] = __builtin_amdgcn_exp2f(x - lrow) + __builtin_amdgcn_exp2f(x - lcol[e]);
+          w[e] = (lab[cl + e] == yrow) ? w[e] - tw : w[e];  // same class: n_col == n_row
+          w[e] = (col0 + e == row) ? 0.f : w[e];
         }
-      }
-    }
+        return w;
+      };
+    });
     return;
   }
 #pragma unroll
@@ -141,7 +121,6 @@ __global__ __launch_bounds__(256, 2) void supcon_tiles(ScArgs a) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
       float x[16];
-      float tm = ninf;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int cl = wave_c * 64 + ct * 32 + acc_row(i, h);
@@ -152,41 +131,12 @@ __global__ __launch_bounds__(256, 2) void supcon_tiles(ScArgs a) {
         x[i] = live ? v : ninf;
         ps += posm ? v : 0.f;
         pc += posm ? 1 : 0;
-        tm = fmaxf(tm, x[i]);
       }
-      if (tm > ninf) {
-        const float mn = fmaxf(m, tm);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(x[i] - mn);
-        l = l * __builtin_amdgcn_exp2f(m - mn) + sum;
-        m = mn;
-      }
+      pair_fold16(m, l, x);
     }
-    // the four (wave_c, lane-half) partials of a row meet in LDS: [128 rows][4 src][m, l, ps, pc]
-    {
-      const int rl = wave_r * 64 + rt * 32 + r, src = wave_c * 2 + h;
-      const f32x4 part = {m, l, ps, (float)pc};
-      *reinterpret_cast<f32x4*>(lds + (rl * 4 + src) * 16) = part;
-    }
+    pair_meet_put(lds, wave_c, wave_r, rt, lane, {m, l, ps, (float)pc});
   }
-  __syncthreads();
-  if (tid < 128 && r0 + tid < a.n) {
-    const f32x4* red = reinterpret_cast<const f32x4*>(lds) + tid * 4;
-    float m = ninf, l = 0.f, ps = 0.f, pc = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {  // fixed order: deterministic
-      const f32x4 part = red[s];
-      pair_lse_merge(m, l, part[0], part[1]);
-      ps += part[2];
-      pc += part[3];
-    }
-    const int64_t o = (int64_t)blockIdx.x * a.n + r0 + tid;
-    a.pm[o] = m;
-    a.pl[o] = l;
-    a.ps[o] = ps;
-    a.pc[o] = pc;
-  }
+  pair_meet_store<4>(lds, tid, r0, a.n, 0.f, PairSum(), {a.pm, a.pl, a.ps, a.pc});
 }
 
 // one thread per logits row: merge the per-column-tile partials in tile order, write row_lse, row_npos and the
@@ -198,42 +148,29 @@ __global__ __launch_bounds__(256) void supcon_rows(const float* __restrict__ pm,
                                                    int32_t* __restrict__ row_npos) {
   const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n) return;
-  float m = -__builtin_huge_valf(), l = 0.f, psum = 0.f;
+  float m, l, psum = 0.f;
   int32_t npos = 0;
-  for (int p = 0; p < nparts; ++p) {
-    const float mp = pm[(int64_t)p * n + row], lp = pl[(int64_t)p * n + row];
-    psum += ps[(int64_t)p * n + row];
-    npos += (int32_t)pc[(int64_t)p * n + row];
-    if (lp > 0.f) {
-      const float mn = fmaxf(m, mp);
-      l = l * exp2f(m - mn) + lp * exp2f(mp - mn);
-      m = mn;
-    }
-  }
+  pair_merge_tiles(m, l, pm, pl, n, nparts, row, [&](int64_t o) {
+    psum += ps[o];
+    npos += (int32_t)pc[o];
+  });
   const float lse2 = m + log2f(l);  // log2 domain; N >= 2: every row has a live column
   if (row_lse) row_lse[row] = lse2 * kLn2;
   if (row_npos) row_npos[row] = npos;
   row_loss[row] = npos > 0 ? t_over_base * ((lse2 - psum / (float)npos) * kLn2) : 0.f;
 }
 
-// zt[k][i] = xn[i][k] as fp16 (the "weight" operand of g = W . X on hcir_gemm_f16); lse -> log2 domain, +inf for a
-// row without positives; 2 / n_i
-template <typename T>
-__global__ void supcon_bwd_prep(const T* __restrict__ xn, const float* __restrict__ row_lse,
-                                const int32_t* __restrict__ row_npos, int64_t n, int d, _Float16* __restrict__ zt,
-                                float* __restrict__ lse2, float* __restrict__ twon) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) {
-    const int32_t np = row_npos[t];
-    lse2[t] = np > 0 ? row_lse[t] * kLog2e : __builtin_huge_valf();
-    twon[t] = np > 0 ? 2.0f / (float)np : 0.f;
+// the backward tile's per-row scalars: lse -> log2 domain, +inf for a row without positives; 2 / n_i
+struct ScRowScalars {
+  const float* row_lse;
+  const int32_t* row_npos;
+  float *lse2, *twon;
+  __device__ void operator()(int64_t i) const {
+    const int32_t np = row_npos[i];
+    lse2[i] = np > 0 ? row_lse[i] * kLog2e : __builtin_huge_valf();
+    twon[i] = np > 0 ? 2.0f / (float)np : 0.f;
   }
-  if (t < n * d) {
-    const int64_t i = t / d;
-    const int k = (int)(t - i * d);
-    zt[(int64_t)k * n + i] = (_Float16)(float)xn[t];
-  }
-}
+};
 
 // dx_i = coef * g_i, or with `normalize` coef * rn_i * (g_i - (g_i . u_i) u_i); one wave per row, scattered back to
 // [B, V, D]; g = W.X (fp32), u = normalised row
@@ -251,17 +188,9 @@ __global__ __launch_bounds__(256) void supcon_bwd_finish(const float* __restrict
     for (int k = lane; k < d; k += 64) dx[k] = (T)(coef * g[row * d + k]);
     return;
   }
-  float ss = 0.f, gu = 0.f;
-  for (int k = lane; k < d; k += 64) {
-    const float xv = (float)x[k];
-    ss = __builtin_fmaf(xv, xv, ss);
-    gu = __builtin_fmaf(g[row * d + k], (float)xn[row * d + k], gu);
-  }
-  ss = wave_sum(ss);
-  gu = wave_sum(gu);
-  const float rn = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-  for (int k = lane; k < d; k += 64)
-    dx[k] = (T)(coef * rn * (g[row * d + k] - gu * (float)xn[row * d + k]));
+  const float rn = pair_row_inv_norm(x, d, lane);
+  pair_project_row(dx, d, lane, coef * rn, [&](int k) { return g[row * d + k]; },
+                   [&](int k) { return (float)xn[row * d + k]; });
 }
 
 struct ScWorkspace {
@@ -274,32 +203,26 @@ struct ScWorkspace {
   size_t bytes;
 };
 
-ScWorkspace sc_carve(void* base, int64_t n, int d, int dtype, bool bwd) {
+ScWorkspace sc_carve(void* base, int64_t n64, int d, int dtype, bool bwd) {
   ScWorkspace w{};
-  char* c = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* r = c ? c + off : nullptr;
-    off += (bytes + 255) & ~size_t(255);
-    return r;
-  };
-  const int64_t nct = hcir_cdiv(n, 128);
-  w.xn = take((size_t)n * d * (dtype == HCIR_F32 ? 4 : 2));
-  w.y = reinterpret_cast<int64_t*>(take((size_t)n * 8));
+  WsCarver c(base);
+  const size_t n = (size_t)n64, nct = (size_t)hcir_cdiv(n64, 128);
+  w.xn = c.take(n * d * hcir_dtype_bytes(dtype));
+  w.y = c.take<int64_t>(n);
   if (!bwd) {
-    w.pm = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.pl = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.ps = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.pc = reinterpret_cast<float*>(take((size_t)nct * n * 4));
-    w.row_loss = reinterpret_cast<float*>(take((size_t)n * 4));
+    w.pm = c.take<float>(nct * n);
+    w.pl = c.take<float>(nct * n);
+    w.ps = c.take<float>(nct * n);
+    w.pc = c.take<float>(nct * n);
+    w.row_loss = c.take<float>(n);
   } else {
-    w.wmat = reinterpret_cast<_Float16*>(take((size_t)n * n * 2));
-    w.zt = reinterpret_cast<_Float16*>(take((size_t)n * d * 2));
-    w.lse2 = reinterpret_cast<float*>(take((size_t)n * 4));
-    w.twon = reinterpret_cast<float*>(take((size_t)n * 4));
-    w.g = reinterpret_cast<float*>(take((size_t)n * d * 4));
+    w.wmat = c.take<_Float16>(n * n);
+    w.zt = c.take<_Float16>(n * d);
+    w.lse2 = c.take<float>(n);
+    w.twon = c.take<float>(n);
+    w.g = c.take<float>(n * d);
   }
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
@@ -318,10 +241,7 @@ int sc_run(const void* feat, const int64_t* labels, int64_t b, int v, int d, flo
   sc_launch_prep<T>(feat, labels, b, v, d, normalize, w, st);
   HCIR_LAUNCH_CHECK();
   ScArgs a{w.xn, w.y, w.pm, w.pl, w.ps, w.pc, n, d, inv_t * kLog2e, nullptr, nullptr, nullptr};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((supcon_tiles<T, true>), dim3(nct, nct), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((supcon_tiles<T, false>), dim3(nct, nct), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(supcon_tiles<T, true>, supcon_tiles<T, false>, dim3(nct, nct), a, st);
   HCIR_LAUNCH_CHECK();
   hipLaunchKernelGGL(supcon_rows, dim3((unsigned)hcir_cdiv(n, 256)), dim3(256), 0, st, w.pm, w.pl, w.ps, w.pc, n,
                      nct, t_over_base, w.row_loss, row_lse, row_npos);
@@ -339,14 +259,11 @@ int sc_run_bwd(const void* feat, const int64_t* labels, int64_t b, int v, int d,
   const int nct = (int)hcir_cdiv(n, 128);
   sc_launch_prep<T>(feat, labels, b, v, d, normalize, w, st);
   HCIR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(supcon_bwd_prep<T>, dim3((unsigned)hcir_cdiv(n * d, 256)), dim3(256), 0, st,
-                     static_cast<const T*>(w.xn), row_lse, row_npos, n, d, w.zt, w.lse2, w.twon);
+  hipLaunchKernelGGL((pair_transpose_f16<T, ScRowScalars>), dim3((unsigned)hcir_cdiv(n * d, 256)), dim3(256), 0, st,
+                     static_cast<const T*>(w.xn), n, d, w.zt, ScRowScalars{row_lse, row_npos, w.lse2, w.twon});
   HCIR_LAUNCH_CHECK();
   ScArgs a{w.xn, w.y, nullptr, nullptr, nullptr, nullptr, n, d, inv_t * kLog2e, w.lse2, w.twon, w.wmat};
-  if (d % SimElem<T>::kPerStage == 0)
-    hipLaunchKernelGGL((supcon_tiles<T, true, true>), dim3(nct, nct), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((supcon_tiles<T, false, true>), dim3(nct, nct), dim3(256), 0, st, a);
+  pair_launch_tiles<T>(supcon_tiles<T, true, true>, supcon_tiles<T, false, true>, dim3(nct, nct), a, st);
   HCIR_LAUNCH_CHECK();
   // g[N][D] = W[N][N] . X[N][D]  ==  hcir_gemm_f16(A = W, "weights" = X^T [D][N])
   const int rc = hcir_gemm_f16(w.wmat, n, w.zt, n, nullptr, nullptr, n, d, (int32_t)n, HCIR_EPI_BIAS_F32, w.g, d, st);
@@ -360,7 +277,7 @@ int sc_run_bwd(const void* feat, const int64_t* labels, int64_t b, int v, int d,
 
 bool sc_shape_ok(int64_t b, int32_t v, int32_t d, float inv_t) {
   if (b <= 0 || v <= 0 || d <= 0 || (d & 7) || b * v < 2 || b * v > 0x7fffffff) return false;
-  return inv_t == inv_t && inv_t != 0.f;
+  return hcir_inv_t_ok(inv_t);
 }
 
 }  // namespace
@@ -377,15 +294,12 @@ int hcir_supcon_fwd(const void* feat, const int64_t* labels, int64_t b, int32_t 
                     void* workspace, size_t workspace_bytes, void* stream) {
   HCIR_ENTER();
   if (!feat || !loss || !sc_shape_ok(b, v, d, inv_t)) return HCIR_ERR_INVALID;
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const ScWorkspace w = sc_carve(workspace, b * v, d, dtype, false);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32)
-    return sc_run<float>(feat, labels, b, v, d, inv_t, t_over_base, normalize, loss, row_lse, row_npos, w, st);
-  if (dtype == HCIR_F16)
-    return sc_run<_Float16>(feat, labels, b, v, d, inv_t, t_over_base, normalize, loss, row_lse, row_npos, w, st);
-  return sc_run<__bf16>(feat, labels, b, v, d, inv_t, t_over_base, normalize, loss, row_lse, row_npos, w, st);
+  return HCIR_DISPATCH_DTYPE(dtype, sc_run, feat, labels, b, v, d, inv_t, t_over_base, normalize, loss, row_lse,
+                             row_npos, w, st);
 }
 
 int hcir_supcon_bwd(const void* feat, const int64_t* labels, int64_t b, int32_t v, int32_t d, int dtype, float inv_t,
@@ -394,18 +308,12 @@ int hcir_supcon_bwd(const void* feat, const int64_t* labels, int64_t b, int32_t 
   HCIR_ENTER();
   if (!feat || !row_lse || !row_npos || !dfeat || !sc_shape_ok(b, v, d, inv_t) || ((b * v) & 7))
     return HCIR_ERR_INVALID;
-  if (dtype != HCIR_F32 && dtype != HCIR_F16 && dtype != HCIR_BF16) return HCIR_ERR_UNSUPPORTED;
+  if (!hcir_float_dtype_ok(dtype)) return HCIR_ERR_UNSUPPORTED;
   const ScWorkspace w = sc_carve(workspace, b * v, d, dtype, true);
   if (!workspace || workspace_bytes < w.bytes) return HCIR_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == HCIR_F32)
-    return sc_run_bwd<float>(feat, labels, b, v, d, inv_t, inv_base, normalize, row_lse, row_npos, grad_out, dfeat,
-                             w, st);
-  if (dtype == HCIR_F16)
-    return sc_run_bwd<_Float16>(feat, labels, b, v, d, inv_t, inv_base, normalize, row_lse, row_npos, grad_out,
-                                dfeat, w, st);
-  return sc_run_bwd<__bf16>(feat, labels, b, v, d, inv_t, inv_base, normalize, row_lse, row_npos, grad_out, dfeat, w,
-                            st);
+  return HCIR_DISPATCH_DTYPE(dtype, sc_run_bwd, feat, labels, b, v, d, inv_t, inv_base, normalize, row_lse, row_npos,
+                             grad_out, dfeat, w, st);
 }
 
 }  // extern "C"
