@@ -423,6 +423,7 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegBatch a) {
 struct Plan {
   int64_t coef_stride, dc_stride, plane_stride, ilv_stride;  // elements per image (int16, int16, uint8, uint32)
   int32_t max_wblocks, huff_threads;
+  int32_t color_pix;  // output pixels per thread of the colour kernel: 4 (packed dword stores) needs win_w % 4 == 0
   bool fast;  // every table in use of every image resolves its long codes in the second lookup level
   int64_t max_words;
   size_t bytes(int64_t b) const {
@@ -436,6 +437,7 @@ int make_plan(const hcir_jpeg_header* hdrs, int64_t b, int32_t win_h, int32_t wi
   // 512 threads: four workgroups per CU, a batch of ~1000 images resident at once; small batches take the shorter
   // subsequences of 1024 threads (latency)
   p->huff_threads = b >= 384 ? 512 : 1024;
+  p->color_pix = win_w % 4 == 0 ? 4 : 1;
   p->fast = true;
   for (int64_t i = 0; i < b; ++i) {
     const hcir_jpeg_header& h = hdrs[i];
@@ -500,6 +502,18 @@ extern "C" size_t hcir_jpeg_workspace_bytes(const hcir_jpeg_header* hdrs_host, i
   return p.bytes(b);
 }
 
+extern "C" int hcir_jpeg_plan(const hcir_jpeg_header* hdrs_host, int64_t b, int32_t win_h, int32_t win_w,
+                              int32_t* huff_threads, int32_t* fast, int32_t* color_pix) {
+  if (!hdrs_host || !huff_threads || !fast || !color_pix || b <= 0 || win_h <= 0 || win_w <= 0) return HCIR_ERR_INVALID;
+  Plan p;
+  const int rc = make_plan(hdrs_host, b, win_h, win_w, &p);
+  if (rc != HCIR_OK) return rc;
+  *huff_threads = p.huff_threads;
+  *fast = p.fast ? 1 : 0;
+  *color_pix = p.color_pix;
+  return HCIR_OK;
+}
+
 extern "C" int hcir_jpeg_decode_window_u8(const void* blob_dev, const hcir_jpeg_header* hdrs_host, int64_t b,
                                           int32_t win_h, int32_t win_w, uint8_t* out, int32_t* status_dev,
                                           void* workspace, size_t workspace_bytes, void* stream) {
@@ -550,7 +564,7 @@ extern "C" int hcir_jpeg_decode_window_u8(const void* blob_dev, const hcir_jpeg_
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)hcir_cdiv(p.max_wblocks, 256), (unsigned)b), dim3(256), 0, st, a);
     HCIR_LAUNCH_CHECK();
   }
-  if (win_w % 4 == 0)
+  if (p.color_pix == 4)
     hipLaunchKernelGGL(jpeg_color_kernel<4>, dim3((unsigned)hcir_cdiv((int64_t)win_h * (win_w / 4), 256), (unsigned)b),
                        dim3(256), 0, st, a);
   else

@@ -136,6 +136,16 @@ def host_window(file: Bytes, size: Tuple[int, int] = (224, 224)) -> torch.Tensor
         return center_window_u8(im, size[0])
 
 
+def plan(staged: StagedBatch, size: Union[int, Tuple[int, int]] = 224) -> Tuple[int, bool, int]:
+    """(huff_threads, fast, color_pix): the kernels `decode_windows(staged, size)` would launch (hcir_jpeg_plan).
+    Host only; works on a staged batch wherever its blob is."""
+    win_h, win_w = (size, size) if isinstance(size, int) else size
+    t, f, c = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.lib().hcir_jpeg_plan(staged._host_headers.data_ptr(), staged.b, win_h, win_w, ctypes.byref(t),
+                                    ctypes.byref(f), ctypes.byref(c)), "hcir_jpeg_plan")
+    return t.value, bool(f.value), c.value
+
+
 _ws = {}
 
 

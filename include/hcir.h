@@ -786,6 +786,12 @@ int hcir_jpeg_stage_batch(const uint8_t* const* files, const size_t* nbytes, int
                           size_t blob_cap, size_t* blob_used, int32_t* status, int32_t nthreads);
 /* HOST.  Workspace bytes for a batch (per-image strides are the maxima over the batch). */
 size_t hcir_jpeg_workspace_bytes(const hcir_jpeg_header* hdrs_host, int64_t b, int32_t win_h, int32_t win_w);
+/* HOST.  Which kernels hcir_jpeg_decode_window_u8 would launch for this batch and window (the same plan, no launch):
+ * *huff_threads = 1024 or 512 threads of the Huffman workgroup, *fast = 1 when every table in use resolves its long
+ * codes in the second lookup level (the branch-free decode loop), else 0 (the generic loop), *color_pix = 4 or 1
+ * output pixels per thread of the colour kernel. */
+int hcir_jpeg_plan(const hcir_jpeg_header* hdrs_host, int64_t b, int32_t win_h, int32_t win_w, int32_t* huff_threads,
+                   int32_t* fast, int32_t* color_pix);
 /* blob_dev: DEVICE copy of the staging blob (headers first); hdrs_host: the same headers on the host (grid
  * sizing only).  out [b][win_h][win_w][3] uint8 = the CenterCrop((win_h, win_w)) window of every decoded
  * image, zero where the window leaves the image (torchvision pads before cropping).  status_dev [b]

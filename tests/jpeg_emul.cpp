@@ -24,7 +24,9 @@ int emul_parse(const uint8_t* file, size_t n, hcir_jpeg_header* h) {
 
 // Decode the CenterCrop((win_h, win_w)) window of one file with `nthreads` emulated threads.
 // stats[0] = hand-over iterations of the sync loop, stats[1] = subsequence bits, stats[2] = active threads,
-// stats[3] = blocks counted over the whole stream.
+// stats[3] = blocks counted over the whole stream, stats[4] = chains still live after round 1 (what the kernel
+// compares with kT / 4 to choose between its compaction queue and carrying on in place), stats[5] = words per
+// subsequence, stats[6] = subsequence row pitch nx, stats[7] = 1 when the fast decode loop ran.  stats: int32[8].
 int emul_decode_window(const uint8_t* file, size_t n, int32_t win_h, int32_t win_w, int32_t nthreads, uint8_t* out,
                        int32_t* stats) {
   hcir_jpeg_header h;
@@ -76,7 +78,7 @@ int emul_decode_window(const uint8_t* file, size_t n, int32_t win_h, int32_t win
     sinfo[t] = jpeg_state_key(ctx[t]);
   }
   // ---- sync loop: in iteration k thread t decodes subsequence t + k from its own chain ----
-  int iters = 0;
+  int iters = 0, live1 = 0;
   for (uint32_t k = 1;; ++k) {
     bool any = false;
     for (uint32_t t = 0; t < nact; ++t) any |= !done[t] && (t + k < nact);
@@ -91,11 +93,15 @@ int emul_decode_window(const uint8_t* file, size_t n, int32_t win_h, int32_t win
       if (sinfo[m] == key) done[t] = 1; else sinfo[m] = key;
       cnt[m] = nb;
     }
+    if (k == 1)
+      for (uint32_t t = 0; t + 2 < nact; ++t) live1 += !done[t];
   }
   // ---- exclusive scan of the block counts ----
   std::vector<uint32_t> first(nact + 1, 0);
   for (uint32_t t = 0; t < nact; ++t) first[t + 1] = first[t] + cnt[t];
-  if (stats) { stats[0] = iters; stats[1] = (int32_t)S; stats[2] = (int32_t)nact; stats[3] = (int32_t)first[nact]; }
+  if (stats) { stats[0] = iters; stats[1] = (int32_t)S; stats[2] = (int32_t)nact; stats[3] = (int32_t)first[nact];
+    stats[4] = live1; stats[5] = (int32_t)sq.wps; stats[6] = (int32_t)sq.nx; stats[7] = fast ? 1 : 0;
+  }
   const uint32_t total_blocks = (uint32_t)h.mcus_x * h.mcus_y * h.blocks_per_mcu;
   if (first[nact] != total_blocks) return HCIR_ERR_INVALID;
 

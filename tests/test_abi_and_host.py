@@ -32,6 +32,7 @@ def test_argument_validation_without_gpu(hcir_built):
     assert L.hcir_gemm_f16(None, 8, None, 8, None, None, 1, 8, 8, 0, None, 8, None) == -1
     assert L.hcir_attn_fwd(None, 1, 1, 1, 64, 1.0, 1, None, None) == -1
     assert L.hcir_topk_merge(None, None, 1, 1, 1, 1, None, None, None) == -1
+    assert L.hcir_jpeg_plan(None, 1, 224, 224, None, None, None) == -1   # host-only plan query: no launch either
 
 
 def test_no_cpu_fallback():

@@ -35,7 +35,7 @@ def emul():
 
     def decode(data, wh, ww, threads=1024):
         out = np.zeros((wh, ww, 3), np.uint8)
-        st = np.zeros(4, np.int32)
+        st = np.zeros(8, np.int32)
         rc = L.emul_decode_window(data, len(data), wh, ww, threads, out.ctypes.data, st.ctypes.data)
         return rc, out, st
 
@@ -254,3 +254,176 @@ def test_stage_leaves_rgb_jpegs_to_the_host(hcir_built):
     bad = bytearray(good)
     bad[i + 5 + 16] = 16
     assert jpeg.stage_batch([bytes(bad)], pin=False).status.tolist() == [-1]
+
+
+# ---- hand-built streams (tests/jpeg_writer.py, tests/_jpeg_cases.py) ---------------------------------------------------
+import sys  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _jpeg_cases as jc  # noqa: E402
+
+
+def _accepted():
+    return list(jc.cases().values()) + jc.small_cases()
+
+
+def test_handbuilt_reference_rule():
+    """Where the reference is Pillow, oracle/jpeg.py agrees with it byte for byte (the pin that lets the
+    extreme-magnitude cases rest on the oracle alone); every case states what it is there for."""
+    from oracle import jpeg as oj
+    n = 0
+    for c in _accepted():
+        assert c.why and c.ref in ("pillow", "oracle"), c.name
+        if c.ref == "pillow":
+            np.testing.assert_array_equal(oj.decode(c.data), c.expected(), err_msg=c.name)
+            n += 1
+    assert n >= 60 and sum(c.ref == "oracle" for c in _accepted()) >= 1
+
+
+def test_handbuilt_cases_through_the_emulator(emul):
+    """Every accepted case at 1024, 512, 96 emulated threads and through the generic loop, over the whole image, a
+    window inside it and a window around it; the non-vacuity each case claims of the decode (loop taken, hand-over
+    rounds, chains live after round 1, subsequence geometry)."""
+    seen = set()
+    for c in _accepted():
+        exp = c.expected()
+        h, w = exp.shape[:2]
+        e = c.expect
+        for threads in (1024, 512, 96, -1024):
+            rc, out, st = emul(c.data, h, w, threads)
+            assert rc == 0, (c.name, threads, rc)
+            np.testing.assert_array_equal(out, exp, err_msg=f"{c.name} T={threads}")
+            assert st[7] == (e["fast"] if threads > 0 else 0), (c.name, threads)
+            if threads == 1024:
+                rounds, nact, live1, nx = int(st[0]), int(st[2]), int(st[4]), int(st[6])
+                if "min_rounds_frac" in e:
+                    assert rounds >= e["min_rounds_frac"] * nact and nact > 512, (c.name, rounds, nact)
+                    seen.add("never")
+                if "rounds" in e:
+                    assert e["rounds"][0] <= rounds <= e["rounds"][1], (c.name, rounds)
+                if "live1_over" in e:
+                    assert live1 > e["live1_over"], (c.name, live1)
+                    seen.add("in_place")
+                if "live1_atmost" in e:
+                    assert 0 < live1 <= e["live1_atmost"] and rounds >= 2, (c.name, live1, rounds)
+                    seen.add("queue")
+                if "nact" in e:
+                    assert nact == e["nact"], (c.name, nact)
+                    seen.add(f"nact{nact}")
+                if e.get("nx_off32"):
+                    assert nx % 32 != 0 and nx > 32, (c.name, nx)
+                    seen.add("nx")
+                if e.get("chunk2"):
+                    assert c.stats["blocks"] // 3 > 1024   # MCUs in a window that shows the whole image: chunk >= 2
+                    seen.add("chunk2")
+            if threads == 512 and "wps512_over" in e:
+                assert st[5] > e["wps512_over"], (c.name, st[5])
+                seen.add("wps")
+        for (wh, ww) in (jc.SMALL_WINDOW, (h + 37, w + 22)):
+            rc, out, _ = emul(c.data, wh, ww, 1024)
+            assert rc == 0, c.name
+            np.testing.assert_array_equal(out, c.window(wh, ww), err_msg=f"{c.name} window {wh}x{ww}")
+    assert seen == {"never", "in_place", "queue", "nact1", "nact1024", "nx", "chunk2", "wps"}, seen
+
+
+def test_handbuilt_cases_through_the_stager(hcir_built):
+    """hcir_jpeg_stage_batch on every accepted case: geometry, the tables' use2, nsegments, the segment table and
+    the unstuffed stream bits against the WRITER's own bookkeeping (the bytes it emitted before stuffing)."""
+    from hcir import jpeg
+    cs = _accepted()
+    staged = jpeg.stage_batch([c.data for c in cs], pin=False, threads=4)
+    assert staged.rejected == []
+    hdrs, blob = staged.headers(), staged.blob.numpy()
+    for c, h in zip(cs, hdrs):
+        exp = c.expected()
+        assert (h.height, h.width) == exp.shape[:2], c.name
+        segs = c.stats["segments"]
+        ref = b"".join(segs)
+        assert h.nsegments == len(segs) and h.stream_bits == 8 * len(ref) == 8 * c.stats["stream_bytes"], c.name
+        if "nseg" in c.expect:
+            assert h.nsegments == c.expect["nseg"], (c.name, h.nsegments)
+        assert h.blocks_per_mcu * h.mcus_x * h.mcus_y == c.stats["blocks"], c.name
+        got = blob[h.stage_offset:h.stage_offset + 4 * h.stream_words].view("<u4").astype(">u4").tobytes()
+        assert got[:len(ref)] == ref and set(got[len(ref):]) <= {0xFF} and len(got) >= len(ref) + 16, c.name
+        seg = blob[h.stage_offset + (4 * h.stream_words + 15) // 16 * 16:][:4 * (h.nsegments + 1)].view("<u4")
+        np.testing.assert_array_equal(seg, np.cumsum([0] + [8 * len(s) for s in segs]), err_msg=c.name)
+        used = {h.dc_tab[k] for k in range(h.ncomp)} | {h.ac_tab[k] for k in range(h.ncomp)}
+        assert min(h.huff[t].lut.use2 for t in used) == c.expect["fast"], c.name
+        # jpeg_subseq as the kernels compute it
+        for T in (1024, 512):
+            S = max(128, (-(-h.stream_bits // T) + 31) // 32 * 32)
+            if T == 1024 and "nact" in c.expect:
+                assert -(-h.stream_bits // S) == c.expect["nact"], c.name
+            if T == 512 and "wps512_over" in c.expect:
+                assert S // 32 > c.expect["wps512_over"], c.name
+    q = hdrs[[c.name for c in cs].index("fmt_sof1_q16")].quant
+    assert max(q[0]) > 255 and q[0][0] == 260
+
+
+def test_handbuilt_rejected_files(hcir_built, emul):
+    from hcir import jpeg
+    rej = jc.rejected_cases()
+    assert [n for n, _, _ in rej] == ["table_id_2", "precision_12", "non_interleaved", "luma_1x2", "luma_4x1",
+                                      "rgb_ids_no_jfif", "too_many_rst"]
+    staged = jpeg.stage_batch([d for _, d, _ in rej] + [jc.cases()["geo_nact1"].data], pin=False)
+    assert staged.status.tolist() == [s for _, _, s in rej] + [0]
+    assert all(h.width == 0 for h in staged.headers()[:len(rej)])
+    L = hcir_built
+    for name, data, status in rej:
+        assert emul(data, 32, 32)[0] == status, name
+        hdr, used = jpeg.JpegHeader(), ctypes.c_size_t(0)
+        blob = np.zeros(len(data) * 2 + 4096, np.uint8)
+        assert L.hcir_jpeg_stage(data, len(data), ctypes.byref(hdr), blob.ctypes.data, 0, blob.size,
+                                 ctypes.byref(used)) == status, name
+
+
+def test_jpeg_plan_reports_every_instantiation(hcir_built):
+    """hcir_jpeg_plan over batches built from the cases: each (threads, fast) pair and both colour kernels, from the
+    plan that hcir_jpeg_decode_window_u8 itself launches by."""
+    from hcir import HcirError, jpeg
+    small = jc.small_cases()
+    fast = [c.data for c in small if c.expect["fast"]]
+    slow = jc.cases()["tab_dc_one"].data
+    assert len(fast) == 40
+    got = set()
+    for files, want in [(fast, (1024, True)), (fast + [slow], (1024, False)), (fast * 10, (512, True)),
+                        (fast * 10 + [slow], (512, False)), (fast * 9 + fast[:23], (1024, True)),
+                        (fast * 9 + fast[:24], (512, True))]:
+        st = jpeg.stage_batch(files, pin=False)
+        for size, pix in [(224, 4), (jc.SMALL_WINDOW, 1), ((7, 1), 1), ((224, 222), 1), ((300, 260), 4)]:
+            assert jpeg.plan(st, size) == (want[0], want[1], pix), (len(files), size)
+            got.add((want[0], want[1], pix))
+    assert len(got) == 8
+    # a placeholder of a rejected file and a window that misses an image take no part in the choice of the loop
+    st = jpeg.stage_batch([fast[0], b"not a jpeg", fast[1]], pin=False)
+    assert st.status.tolist() == [0, -1, 0] and jpeg.plan(st, 224) == (1024, True, 4)
+    L = hcir_built
+    z = ctypes.c_int32(0)
+    assert L.hcir_jpeg_plan(None, 1, 224, 224, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == -1
+    assert L.hcir_jpeg_plan(st._host_headers.data_ptr(), 3, 224, 0, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z)) == -1
+    assert L.hcir_jpeg_plan(st._host_headers.data_ptr(), 3, 224, 224, None, ctypes.byref(z), ctypes.byref(z)) == -1
+    bad = jpeg.stage_batch([fast[0]], pin=False)
+    bad.headers()[0].blocks_per_mcu = 9
+    with pytest.raises(HcirError):
+        jpeg.plan(bad, 224)
+
+
+def test_sanitised_stream_check_over_cases_and_truncations(tmp_path):
+    """tests/jpeg_stream_check.cpp under AddressSanitizer + UBSan, as a stand-alone program: every accepted and
+    rejected case parsed, staged and decoded by the host-compiled device code, and again cut at every 97th byte."""
+    exe = os.path.join(ROOT, "tests", "_build", "jpeg_stream_check")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan",   # the runtimes inside the program: nothing to preload
+                           "-Wall", "-Wno-unknown-pragmas", os.path.join(ROOT, "tests", "jpeg_stream_check.cpp"),
+                           "-o", exe])
+    d = tmp_path / "streams"
+    d.mkdir()
+    for c in _accepted():
+        (d / f"{c.name}.jpg").write_bytes(c.data)
+    for name, data, _ in jc.rejected_cases():
+        (d / f"reject_{name}.jpg").write_bytes(data)
+    r = subprocess.run([exe, str(d), "97"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    words = r.stdout.split()
+    assert int(words[1]) == len(_accepted()) + 7 and int(words[3]) > 2000 and int(words[7]) == 0, r.stdout
